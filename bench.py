@@ -3,7 +3,13 @@
 A "step" = one Solver::step() (one frame) = `admm_iters` ADMM iterations {local step, RHS gather,
 global solve} on a device-resident state (no host<->device traffic inside the timed region).
 
-  python bench.py --gpus 1 --steps K --warmup W [--workload blob1m_mix|cube1m_mix|cube1m_nh|cube100k_gs|...]
+  python bench.py --gpus 1 --steps K --warmup W [--workload blob1m_mix|cube1m_mix|cube1m_nh|cube100k_gs|...] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step, with the run's configuration).  --full adds everything else: statistics frames behind the timed ones (phase
+split, iteration counts, convergence and finiteness checks), the contact leg, the PCIe-inclusive rate, the weak leg of an
+N-GPU line, the roofline figures and the CPU baselines.  --dump-outputs DIR writes the state the last timed step computed
+(m_x, m_v: what a caller of Solver::step receives) as DIR/<name>.npy.
 
 Workloads (BASELINE.json `configs`):
   blob1m_mix   configs[2] as named ("1M-tet synthetic bunny/dragon, StVK + Neo-Hookean mix"): the DEFAULT.  Unstructured
@@ -276,6 +282,27 @@ def cpu_calibration(out_path=CALIBRATION_FILE):
     return res
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """Write `arrays` (name -> array with one row per vertex) as out_dir/<name>.npy in float64.  When the files would exceed
+    `limit_bytes` in all, every array keeps the same fixed, seeded sample of rows (in row order).  Returns the kept rows (None: all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    assert len(rows) == 1, "dump_outputs: arrays differ in their number of rows"
+    rows = rows.pop()
+    keep = None
+    header = 256 * len(arrays)            # (np.save: a header of at most a few hundred bytes per file)
+    if sum(a.nbytes for a in arrays.values()) + header > limit_bytes:
+        per_row = sum(a.nbytes for a in arrays.values()) // max(rows, 1)
+        keep = np.sort(np.random.default_rng(seed).choice(rows, size=(limit_bytes - header) // per_row, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if keep is None else a[keep])
+    return keep
+
+
 def pkg_kind(name):
     import admm_elastic_amd as pkg
     return {"neohookean": pkg.TET_NEOHOOKEAN, "linear": pkg.TET_LINEAR, "stvk": pkg.TET_STVK}[name]
@@ -313,6 +340,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--calibrate-cpu-baseline", action="store_true", help="build container only: time the oracle port against the compiled reference pieces -> profiles/")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: statistics frames, contact leg, PCIe-inclusive rate, weak leg (N GPUs), roofline, "
+                         "CPU baselines (--no-cpu-baseline / --no-roofline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step computed (m_x, m_v; rank 0's copy) as DIR/<name>.npy, float64, <= 64 MB in all")
     args = ap.parse_args()
     if not args.n and os.environ.get("ADMM_BENCH_N"):      # (tests: the launcher's own parser trips over `--n`)
         args.n = int(os.environ["ADMM_BENCH_N"])
@@ -403,12 +435,14 @@ def main():
     lt_pairs, lt_ms = 0, 0.0       # the local-step launches of the TIMED region: event pairs, read after it
     if lean:
         # a hipEvent pair attached to the dispatch of every local-step kernel of the timed region (ADMM_BENCH_LOCAL_EVENTS=0 / 1: none /
-        # hipEventRecords around the launch -- same-box A/B of what the instrumentation costs, experiments/r06_a.sh)
+        # hipEventRecords around the launch -- same-box A/B of what the instrumentation costs, experiments/r06_a.sh).  Only `roofline`
+        # (--full) reads them, but a plain run attaches them too: its timed frames stay the very frames every earlier line timed, so
+        # `value` stays comparable with those lines and with the --full line of the same build.
         s.time_local_launches(int(os.environ.get("ADMM_BENCH_LOCAL_EVENTS", "2")))
         s.local_launch_times()     # (clears what the warm-up recorded)
-    uz0 = s.uzawa_cache_stats() if w["linsolver"] == 2 else None
+    uz0 = s.uzawa_cache_stats() if args.full and w["linsolver"] == 2 else None
     has_contact = bool(sc.obstacles or sc.dynamic) and w["linsolver"] != 0
-    ct0 = s.contact_totals() if has_contact else 0       # rows of C (UzawaCG) / rows projected inside the sweeps (GS) so far
+    ct0 = s.contact_totals() if args.full and has_contact else 0       # rows of C (UzawaCG) / rows projected inside the sweeps (GS) so far
     frame_ms = []                                        # HIP-event time of every statistics frame (median: SURVEY 8d)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -422,6 +456,53 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     stats_elapsed = elapsed
+    if args.dump_outputs:
+        # every rank downloads: under the component partition with a communicator admm_hip_get_state is a collective (include/admm_hip.h)
+        if share:
+            # no communicator: a rank's download fills only the vertices it owns, so the ranks' parts are merged here (NaN = not filled)
+            s.m_x[:] = np.nan; s.m_v[:] = np.nan
+            s.download()
+            parts = [None] * world
+            dist.all_gather_object(parts, (s.m_x, s.m_v))
+            for k in (0, 1):
+                merged = parts[0][k].copy()
+                for p in parts[1:]:
+                    merged = np.where(np.isnan(merged), p[k], merged)
+                (s.m_x if k == 0 else s.m_v)[:] = merged
+        else:
+            s.download()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"m_x": s.m_x.reshape(-1, 3), "m_v": s.m_v.reshape(-1, 3)})
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else "cuda:%d" % local_rank)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = 1e3 * elapsed / max(args.steps, 1)
+    # weak scaling: every rank steps its own body, the job's rate is the bodies' ADMM iterations per second, summed
+    value = (world if weak else 1) * iters * args.steps / elapsed
+    out = {
+        "metric": "ADMM iterations/sec", "value": value, "unit": "ADMM it/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        # the DEFAULT lines of --gpus 1, 2, 4, 8 are BASELINE's series: ONE 1 M-tet body at fixed tet count (configs[3]); the weak
+        # series (one such body per GPU) is `weak_value` of the same lines (--full)
+        "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "soft_modes": soft, "pcg_tol": args.pcg_tol,
+        "config": {"workload": args.workload + (" (n=%d override)" % args.n if args.n else ""), "elements": nt, "verts": nv,
+                   "admm_iters_per_step": iters, "global_solver": "multicolor-GS(30 sweeps)" if w["linsolver"] == 1 else
+                   ("UzawaCG, no active constraints: every solve is the prefactored solve (src/UzawaCG.hpp:78-81) = one persistent on-chip two-level pipelined PCG launch, tol=%g max=%d" % (args.pcg_tol, args.pcg_max_iters)
+                    if contact_free else "UzawaCG (Schur-complement CG, <= 20 iterations, stop decided on the device) over the on-chip PCG tol=%g" % args.pcg_tol) if w["linsolver"] == 2 else
+                   "PCG (one persistent on-chip launch per solve: two-level preconditioned pipelined CG, matrix and vectors in LDS) tol=%g max=%d" % (args.pcg_tol, args.pcg_max_iters),
+                   "parallelism": ("whole bodies per rank x%d (component-aware partition, no exchange inside a step)" % world if weak else
+                                   "element-block x%d (RCCL all-reduce of the right-hand side, %s)" % (world,
+                                       "DISTRIBUTED solve: launch-path Jacobi PCG, rows split over the ranks, two all-reduces per PCG iteration (ADMM_HIP_DIST_SOLVE=1)"
+                                       if os.environ.get("ADMM_HIP_DIST_SOLVE") == "1" and not weak else "replicated solve")) if world > 1 else "single-gpu"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     ct1 = s.contact_totals() if has_contact else 0
     uz1 = s.uzawa_cache_stats() if w["linsolver"] == 2 else None
     if lean:
@@ -445,13 +526,6 @@ def main():
         unconv += (tot2[0] - tot1[0]) - (tot2[1] - tot1[1])
     else:
         lt_pairs, lt_ms = iters * args.steps, local_ms
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else "cuda:%d" % local_rank)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    ms_per_step = 1e3 * elapsed / max(args.steps, 1)
-    # weak scaling: every rank steps its own body, the job's rate is the bodies' ADMM iterations per second, summed
-    value = (world if weak else 1) * iters * args.steps / elapsed
     # The WEAK series rides along on the strong default line (`weak_value`): every rank steps ONE whole body of its own (a
     # single-GPU context of the same scene -- what blobs_1m_per_gpu gives each rank), same warm-up, same K frames, barriers,
     # max over ranks; N bodies' ADMM iterations per second, summed.
@@ -515,22 +589,7 @@ def main():
             s.step()
         pcie_value = iters * 2 / (time.perf_counter() - t1)
 
-    out = {
-        "metric": "ADMM iterations/sec", "value": value, "unit": "ADMM it/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        # the DEFAULT lines of --gpus 1, 2, 4, 8 are BASELINE's series: ONE 1 M-tet body at fixed tet count (configs[3]); the weak
-        # series (one such body per GPU) is `weak_value` of the same lines
-        "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "soft_modes": soft, "pcg_tol": args.pcg_tol,
-        "config": {"workload": args.workload + (" (n=%d override)" % args.n if args.n else ""), "elements": nt, "verts": nv,
-                   "admm_iters_per_step": iters, "global_solver": "multicolor-GS(30 sweeps)" if w["linsolver"] == 1 else
-                   ("UzawaCG, no active constraints: every solve is the prefactored solve (src/UzawaCG.hpp:78-81) = one persistent on-chip two-level pipelined PCG launch, tol=%g max=%d" % (args.pcg_tol, args.pcg_max_iters)
-                    if contact_free else "UzawaCG (Schur-complement CG, <= 20 iterations, stop decided on the device) over the on-chip PCG tol=%g" % args.pcg_tol) if w["linsolver"] == 2 else
-                   "PCG (one persistent on-chip launch per solve: two-level preconditioned pipelined CG, matrix and vectors in LDS) tol=%g max=%d" % (args.pcg_tol, args.pcg_max_iters),
-                   "parallelism": ("whole bodies per rank x%d (component-aware partition, no exchange inside a step)" % world if weak else
-                                   "element-block x%d (RCCL all-reduce of the right-hand side, %s)" % (world,
-                                       "DISTRIBUTED solve: launch-path Jacobi PCG, rows split over the ranks, two all-reduces per PCG iteration (ADMM_HIP_DIST_SOLVE=1)"
-                                       if os.environ.get("ADMM_HIP_DIST_SOLVE") == "1" and not weak else "replicated solve")) if world > 1 else "single-gpu"},
+    out.update({
         "ms_per_frame": ms_per_step,
         "split_ms_per_admm_iter": {"local": local_ms / (iters * args.steps), "rhs": rhs_ms / (iters * args.steps),
                                    "global": global_ms / (iters * args.steps)},
@@ -566,7 +625,7 @@ def main():
         # The PCG kernel keeps matrix and vectors on chip; its iteration is bound by one grid barrier, not by HBM.
         "us_per_inner_iter": 1e3 * (global_ms - rhs_ms) / max(inner, 1),
         "finite": finite, "pcie_inclusive_admm_it_per_s": pcie_value,
-    }
+    })
     if weak_value is not None:
         out["weak_value"] = weak_value
         out["weak"] = {"workload": "one blob1m_mix body per GPU (what --workload blobs_1m_per_gpu runs as its whole line)", "ms_per_step": weak_ms,

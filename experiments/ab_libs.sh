@@ -20,7 +20,7 @@ done
 for rep in 1 2; do
 for name in $names; do
   for w in $WLS; do
-  ADMM_HIP_LIB=/tmp/ab/$name.so python bench.py --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  ADMM_HIP_LIB=/tmp/ab/$name.so python bench.py --full --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); g=d.get('roofline_global') or {}
 print('[$name]', '$w', '| local us', round(1000*d['split_ms_per_admm_iter']['local'],2), 'rhs us', round(1000*d['split_ms_per_admm_iter']['rhs'],1), 'solve us', round(g.get('solve_us',0),1), 'its/solve', g.get('iterations_per_solve'), 'it/s', round(d['value'],1), 'frac', round(d['roofline']['frac'],3), 'unconv', d.get('unconverged_solves_in_timed_region'))"

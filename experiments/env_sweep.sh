@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 WL=$1; shift
 python -c "import torch" > /dev/null 2>&1
 for cfg in "" "$@"; do
-  line=$(env $cfg python bench.py --workload $WL --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
+  line=$(env $cfg python bench.py --full --workload $WL --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
   python - "$cfg" <<PY
 import json, sys
 d = json.loads('''$line''') if '''$line''' else None

@@ -441,7 +441,7 @@ def test_bench_two_ranks_share_one_gpu_functional(series):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ADMM_BENCH_SHARE_GPU="1", ADMM_BENCH_N="30")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     if series == "weak":
         cmd += ["--workload", "blobs_1m_per_gpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
@@ -458,6 +458,39 @@ def test_bench_two_ranks_share_one_gpu_functional(series):
     else:
         assert d["config"]["workload"].startswith("blobs_1m_per_gpu")
         assert "whole bodies per rank x2" in d["config"]["parallelism"] and d["expected_speedup"]["vs_one_gpu"] == 2.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("series", ["strong", "weak"])
+def test_bench_two_ranks_share_one_gpu_plain_line_and_dump(series, tmp_path):
+    """The PLAIN `python bench.py --gpus 2` (no --full) on a one-GPU box, as above: the headline line alone, and --dump-outputs with
+    every rank downloading (a collective under the component partition with a communicator).  weak: rank 0's dump holds BOTH bodies
+    stepped -- without a communicator each rank fills only its own body, and bench.py merges the two parts."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, ADMM_BENCH_SHARE_GPU="1", ADMM_BENCH_N="30")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    if series == "weak":
+        cmd += ["--workload", "blobs_1m_per_gpu"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["scaling"] == series and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["metric"] == "ADMM iterations/sec" and d["unit"] == "ADMM it/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    for k in ("split_ms_per_admm_iter", "finite", "weak_value", "expected_speedup", "rccl"):
+        assert k not in d, k
+    nv = d["config"]["verts"]
+    x, v = np.load(tmp_path / "m_x.npy"), np.load(tmp_path / "m_v.npy")
+    assert x.shape == (nv, 3) and v.shape == (nv, 3) and np.isfinite(x).all() and np.isfinite(v).all()
+    halves = (slice(0, nv // 2), slice(nv // 2, nv)) if series == "weak" else (slice(0, nv),)
+    for h in halves:                                   # (weak: two copies of one body, body 0 first)
+        assert np.abs(v[h]).max() > 0, h
+    if series == "weak":                               # the two bodies are the same body 2 m apart, stepped alike
+        assert np.abs(x[halves[1]] - np.array([2.0, 0.0, 0.0]) - x[halves[0]]).max() < 1e-5
 
 
 def test_bench_gpus_flag_starts_that_many_ranks():
