@@ -27,6 +27,8 @@
 #include "uz_persist.hpp"
 
 using namespace admm_k;
+using admm_host::env_flag;
+using admm_host::env_int;
 
 namespace {
 
@@ -127,8 +129,6 @@ struct admm_hip_ctx {
     int linsolver = 0;
     double constraint_w = 1.0;
     int pcg_max_iters = 500; double pcg_tol = 1e-10;
-    double tol_last = 0.0; int tol_last_n = 0;      // experiments: see step_impl
-    std::vector<double> tol_sched;                  // pcg_tol multipliers of the first solves of a step (admm_hip_set_pcg_tol_schedule)
     int gs_max_iters = 30; double gs_tol = 1e-10, gs_omega = 1.9;
     int uz_max_iters = 20; double uz_tol = 1e-10;
     bool state_set = false;
@@ -165,11 +165,8 @@ struct admm_hip_ctx {
     DevBuf<int> t_mat;
     DevBuf<Mat> mats; DevBuf<double> spl_tab;   // tabulated user splines (ADMM_TET_SPLINE_TABLE)
     SellDev t_inc; DevBuf<int> g_order;   // incidence lists, and the vertex every row of them gathers for
-    // the same record lists in the on-chip solver's internal row order: k_pcg2 sums the right-hand side of its own rows (Oc2Args::g_inc) and
-    // the k_gather_rhs launch of the ADMM loop goes away (fuse_rhs_ok: the plan has them; fuse_rhs: armed for the next on-chip solve)
     DevBuf<double> big_agree;     // distributed solve: the ranks' agreement on the solver (launch_pcg)
     bool defl_armed = false;      // launch_pcg2 armed the fused end projection for the solve just launched
-    SellDev oc_inc; std::vector<int32_t> rec_vertex_h; bool fuse_rhs_ok = false, fuse_rhs = false; long long fused_rhs_solves = 0;
     // tris
     int ntri = 0, ldr = 0;
     DevBuf<int4> r_idx;
@@ -218,7 +215,7 @@ struct admm_hip_ctx {
     DevBuf<unsigned long long> oc_prof;   // diagnosis (ADMM_HIP_OC_PROF=1)
     bool oc_debug = false, oc_always_verify = false; int oc_prof_block = 0;
     // general-mesh plan of the on-chip PCG (oc_plan.cpp): internal row order, its SELL, slab shares, two-level data
-    double oc_sm_ab = 0.0, oc_sm_b = 0.0, oc_lam_bb = 0.0, oc_sm_c0 = 0.0, oc_sm_k1 = 0.0, oc_sm_k2 = 0.0;   // block-local smoother of k_pcg2 (pcg_onchip2.hpp: smooth)
+    double oc_sm_ab = 0.0, oc_sm_b = 0.0, oc_lam_bb = 0.0;   // block-local smoother of k_pcg2 (pcg_onchip2.hpp: smooth)
     bool oc_plan = false, oc_coarse = false; int oc_rows = 0, oc_bcols = 0, oc_nc = 0, oc_ncp = 0, oc_veclen = 0;
     SellDev oc_A; DevBuf<int> oc_orig, oc_ldsoff, oc_wls, oc_haloptr, oc_halosrc; DevBuf<unsigned short> oc_col16;
     DevBuf<double> oc_mdiag, oc_ainv, oc_cbuf; DevBuf<float> oc_cwt; bool oc_affine = false;
@@ -233,7 +230,7 @@ struct admm_hip_ctx {
     int wind_n = 0; double wind_dir[3] = {0.0, 0.0, 0.0}; DevBuf<int> wind_tris; SellDev wind_inc; DevBuf<double> wind_force;
     DevBuf<unsigned long long> gs_proj; long long uz_rows_total = 0;   // admm_hip_contact_totals: rows projected inside the GS sweeps (device), rows of C over all UzawaCG solves (host)
     // launch-path two-level PCG (pcg_big.hpp): systems beyond the chip's LDS, and the fall-back of the on-chip kernel
-    bool big_enabled = false, big_tried = false, big_allowed = true; int defl_dbg = 0, defl_start = 2; bool defl_start_hold = false; std::vector<double> xyz_h;
+    bool big_enabled = false, big_tried = false, big_allowed = true; int defl_start = 2; bool defl_start_hold = false; std::vector<double> xyz_h;
     int big_G = 0, big_ra = 0, big_rows = 0, big_nc = 0, big_ncp = 0, big_NBt = 0;
     SellDev big_A; DevBuf<int> big_orig; DevBuf<float> big_ainv;
     DevBuf<double> big_mass, big_dinv, big_cwt, big_xi, big_r, big_u, big_w, big_p, big_s, big_part, big_cvec, big_rho, big_dots; DevBuf<int> big_tick;
@@ -244,9 +241,11 @@ struct admm_hip_ctx {
     int big_its_hist[32] = {};    // iterations the launch-path solve at position s of the previous frame needed (first chunk of the next one)
     int big_row_lo = 0, big_row_hi = 0x7fffffff, big_nif = 0; DevBuf<int> big_if_rows; DevBuf<double> big_ifbuf;      // distributed solve: owned internal rows, interface rows
     // end projection of every PCG solve on soft modes (admm_hip_set_soft_modes; kernels.hpp: k_defl_*)
-    int defl_k = 0, defl_every = 1; bool defl_now = true, defl_fused = false; DevBuf<double> defl_Z, defl_Ginv, defl_part, defl_y, defl_rec; DevBuf<float> defl_Zint;
-    std::vector<int32_t> oc_orig_h;      // internal row -> vertex of the on-chip plan (host copy: the soft modes are stored in that order for k_pcg2)      // defl_every: experiments (ADMM_HIP_DEFL_EVERY=n: only every n-th solve of a step)
+    int defl_k = 0; bool defl_fused = false; DevBuf<double> defl_Z, defl_Ginv, defl_part, defl_y, defl_rec; DevBuf<float> defl_Zint;
+    std::vector<int32_t> oc_orig_h;      // internal row -> vertex of the on-chip plan (host copy: the soft modes are stored in that order for k_pcg2)
     long long oc_launches = 0, gsp_launches = 0;   // persistent launches since create (admm_hip_persistent_launches)
+    bool kernel_clock = false;      // ADMM_HIP_KERNEL_CLOCK=1: wall-clock stamps of the local-step launches (step_impl)
+    bool uz_lanes_debug = false;    // ADMM_HIP_UZ_LANES_DEBUG=1: the column lanes report on stderr
     int test_abort_seq = 0;   // tests only (ADMM_HIP_TEST_ABORT_SOLVE=k): the k-th on-chip solve of the context finds its barrier aborted
     int test_abort_uzp = 0;   // tests only (ADMM_HIP_TEST_ABORT_SCHUR=k): the k-th persistent Schur launch finds its hand-off given up
     int n_cus = 256;   // multiProcessorCount of the device (persistent kernels need all their blocks resident at once)
@@ -261,7 +260,7 @@ struct admm_hip_ctx {
     static constexpr int kRcSlots = kRc + 1;
     DevBuf<double> rc_buf, rc_r0, rc_xs, rc_part, rc_coef;
     int rc_iter = 0, rc_frame = 0, rc_prev_valid = 0, NBR = 1; // pairs of the previous frame valid for s < rc_prev_valid
-    int rc_pairs = kRc; bool rc_adapt = false, rc_decided = false; long long rc_snap[2] = {0, 0};   // pairs per projection: see step_impl
+    int rc_pairs = kRc; bool rc_decided = false; long long rc_snap[2] = {0, 0};   // pairs per projection: see step_impl
     bool rc_enabled = true;
     // Slots: the pairs of the FIRST kRc solves of a frame have slots of their own (0 .. kRc - 1), later solves share a ring of
     // kRcSlots behind them.  Slot j < kRc therefore keeps "the most recent pair of solve index j" across the frame boundary: when
@@ -276,18 +275,15 @@ struct admm_hip_ctx {
     // tolerance the first five solves of a frame were 60 % of its PCG iterations (body: 31 56 25 43 25 of ~300); two frames of
     // history bring solves 2-4 to 10-12 (frame total ~225, -25 %; 2 123 -> 2 404 ADMM it/s same-box).  For later solves the frame's own
     // most recent pairs are worth more than any history (cube, history for all 20 solves: 556 -> 735 iterations per frame).
-    // Round 6 measured history for MORE solves (ADMM_HIP_RC_HIST_N = 8, 12, 20) with three and four pairs: on the bench body 8.68 -> 7.32 iterations
+    // Round 6 measured history for MORE solves (8, 12, 20 solves) with three and four pairs: on the bench body 8.68 -> 7.32 iterations
     // per solve in the driver's window, 2 500 -> 2 660 ADMM it/s -- and the 200-frame drift goes from 3.2e-6 to 8.3e-6 (8 solves), 2.4e-5 (12),
     // 3.4e-5 (20): OVER the bar.  The history pairs are nearly the same from frame to frame, so what the projection leaves behind is the SAME
     // error every frame -- a bias that enters the velocity and accumulates, where the error of plain PCG iterations is spread over the spectrum.
     // At equal drift (tolerance tightened to 2-3e-10) the longer history is no faster (profiles/r06_history_sweep.txt).  Five stays.
-    int kRcHist = 5;      // (ADMM_HIP_RC_HIST_N)
-    int rc_hist = 0, rc_prev2_valid = 0;
-    // rc_depth: frames the history keeps (this one included; ADMM_HIP_RC_DEPTH, default 3); rc_vb[d]: solves of frame - d whose pairs are valid;
-    // rc_order[s] (s = 0, 1; ADMM_HIP_RC_ORDER0 / 1, experiments): the basis of solve s as a list of tokens "oK" = this frame's solve s - K,
-    // "pQ.D" = solve s + Q of frame - D, in order of preference -- unset: the built-in order of launch_pcg_recycled_impl
-    int rc_depth = 3, rc_vb[8] = {0, 0, 0, 0, 0, 0, 0, 0}; std::vector<std::array<int, 3> > rc_order[3];      // [2]: every later solve (ADMM_HIP_RC_ORDER)
-    int rc_loc(int s, int frame) const { return (rc_hist && s < kRcHist) ? kRcAllSlots + ((frame % rc_depth + rc_depth) % rc_depth) * kRcHist + s : rc_slot(s); }
+    static constexpr int kRcHist = 5;
+    static constexpr int kRcDepth = 3;      // frames the history keeps (this one included)
+    int rc_hist = 0, rc_prev2_valid = 0;    // rc_hist: set by the plan (on-chip kernel with its plan), 0 after an aborted solve
+    int rc_loc(int s, int frame) const { return (rc_hist && s < kRcHist) ? kRcAllSlots + ((frame % kRcDepth + kRcDepth) % kRcDepth) * kRcHist + s : rc_slot(s); }
     double *rc_Ef(int s, int frame) { return rc_buf.p + ((size_t)rc_loc(s, frame) * 2 + 0) * (size_t)n3i; }
     double *rc_Rf(int s, int frame) { return rc_buf.p + ((size_t)rc_loc(s, frame) * 2 + 1) * (size_t)n3i; }
     // UzawaCG (per-vertex constraint rows)
@@ -602,19 +598,8 @@ int launch_pcg2(admm_hip_ctx *c, const double *b, double *x, int max_iters, cons
     a.skip = rc.skip;
     // (every 16th solve and a context's first 40 verify whatever the rule says: the sample that can revoke the trust, pcg_onchip2.hpp)
     a.trust_short = (c->oc_always_verify || c->oc_launches < 40 || (c->oc_launches & 15) == 0) ? 0 : 1;
-    if (rc.on && c->defl_fused && c->defl_k > 0 && c->defl_now) { c->defl_armed = true; a.defl_dbg = c->defl_dbg; a.defl_k = c->defl_k; a.defl_Z = c->defl_Zint.p; a.defl_Ginv = c->defl_Ginv.p; a.defl_rec = c->defl_rec.p; }      // (the ADMM loop's solves only: not the K^-1 columns of UzawaCG)
-    a.sm_ab = c->oc_sm_ab; a.sm_b = c->oc_sm_b; a.sm_c0 = c->oc_sm_c0; a.sm_k1 = c->oc_sm_k1; a.sm_k2 = c->oc_sm_k2;
-    if (c->fuse_rhs) {      // armed by step_impl for exactly this solve: the kernel sums its own right-hand side (no k_gather_rhs launch was made)
-        c->fuse_rhs = false;
-        if (ln || b != c->b.p || !c->fuse_rhs_ok) return -1;
-        a.g_ptr = c->oc_inc.ptr.p; a.g_w = c->oc_inc.w.p; a.g_inc = c->oc_inc.idx.p; a.g_pad = c->n_rec; a.g_rec = c->t_rec.p; a.g_Mxbar = c->Mxbar.p; a.g_b = c->b.p;
-        if (c->npin_terms > 0) {
-            a.g_pin_nrm = c->has_slide ? c->pin_nrm.p : nullptr;
-            a.g_vert_pin = c->vert_pin.p; a.g_pin_xyz = c->pin_xyz.p; a.g_pin_active = c->pin_active.p;
-            a.g_pin_u = c->pin_u.p; a.g_pin_z = c->pin_z.p; a.g_pin_sc = c->dt * c->dt * c->pin_weight * c->pin_weight;
-        }
-        c->fused_rhs_solves += 1;
-    }
+    if (rc.on && c->defl_fused && c->defl_k > 0) { c->defl_armed = true; a.defl_k = c->defl_k; a.defl_Z = c->defl_Zint.p; a.defl_Ginv = c->defl_Ginv.p; a.defl_rec = c->defl_rec.p; }      // (the ADMM loop's solves only: not the K^-1 columns of UzawaCG)
+    a.sm_ab = c->oc_sm_ab; a.sm_b = c->oc_sm_b;
     c->oc_launches += 1;
     if (ln) {      // a side-stream solve (UzawaCG's columns): the lane's own copies of everything the kernel writes, no diagnosis
         a.u_out = ln->u; a.ubuf = ln->ubuf; a.part = ln->part; a.bar = ln->bar; a.flags = c->oc_flags.p ? ln->flags : nullptr;
@@ -637,8 +622,7 @@ int launch_pcg_onchip(admm_hip_ctx *c, const double *b, double *x, int max_iters
 // Decide whether the system fits the chip: one SELL slice per wave, <= 16 waves per block, one block per CU.
 hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
     c->oc_enabled = false;
-    const char *env = getenv("ADMM_HIP_PCG_LAUNCHES");
-    if (env && env[0] == '1') return hipSuccess;
+    if (env_flag("ADMM_HIP_PCG_LAUNCHES", false)) return hipSuccess;
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, c->device);
     if (e != hipSuccess) return e;
@@ -647,34 +631,31 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
     int G = std::min(cus, ns);
     int spb = (ns + G - 1) / G;
     if (spb > 16) return hipSuccess;
-    {   // ADMM_HIP_OC_PLAN=0: no on-chip solve (A/B against the launch-per-iteration path, like ADMM_HIP_PCG_LAUNCHES=1)
-        const char *pe = getenv("ADMM_HIP_OC_PLAN");
-        if (pe && pe[0] == '0') return hipSuccess;
-    }
+    if (!env_flag("ADMM_HIP_OC_PLAN", true)) return hipSuccess;      // no on-chip solve (A/B against the launch-per-iteration path, like ADMM_HIP_PCG_LAUNCHES=1)
     // the two-level preconditioner lets every thread handle two coarse unknowns (4 G <= 2 x 64 spb); small systems therefore
     // use fewer, larger blocks (which also makes their grid barrier cheaper)
     while (spb < 16 && (ns + spb - 1) / spb > 32 * spb) ++spb;
     {   // ADMM_HIP_OC_SPB=n: slices (waves) per block forced (experiments: barrier cost against block-local work on small systems)
-        const char *se = getenv("ADMM_HIP_OC_SPB");
-        if (se && atoi(se) >= 1 && atoi(se) <= 16 && (ns + atoi(se) - 1) / atoi(se) <= cus) spb = atoi(se);
+        const int se = env_int("ADMM_HIP_OC_SPB", 0);
+        if (se >= 1 && se <= 16 && (ns + se - 1) / se <= cus) spb = se;
     }
     G = (ns + spb - 1) / spb;
     const int T = 64 * spb;
     size_t lds_max = std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024);
-    {   // ADMM_HIP_OC_LDS_KB=n: plan for less LDS (experiments, tests of the slab's streamed tail: more of the matrix comes from L2)
-        const char *le = getenv("ADMM_HIP_OC_LDS_KB");
-        if (le && atoi(le) >= 32) lds_max = std::min<size_t>(lds_max, (size_t)atoi(le) * 1024);
+    {   // ADMM_HIP_OC_LDS_KB=n (>= 32): plan for less LDS (experiments, tests of the slab's streamed tail: more of the matrix comes from L2)
+        const int kb = env_int("ADMM_HIP_OC_LDS_KB", 0);
+        if (kb >= 32) lds_max = std::min<size_t>(lds_max, (size_t)kb * 1024);
     }
     size_t lds = 0;
     // The plan: compact blocks by graph bisection, rows sorted by length, local vector + halo list + slab in LDS,
     // two-level preconditioner (ADMM_HIP_OC_COARSE=0: Jacobi on the same layout) -- oc_plan.cpp, pcg_onchip2.hpp.
     admm_host::OcPlan plan;
     {
-        const char *ce = getenv("ADMM_HIP_OC_COARSE");
+        const bool coarse = env_flag("ADMM_HIP_OC_COARSE", true);
         {
             std::vector<double> mass(c->n3);
             if ((e = hipMemcpy(mass.data(), c->m.p, mass.size() * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) return e;
-            plan = admm_host::build_oc_plan(c->Ahat, mass.data(), G, spb, (int)lds_max - kOc2Scratch, !(ce && ce[0] == '0'), c->create_xyz);
+            plan = admm_host::build_oc_plan(c->Ahat, mass.data(), G, spb, (int)lds_max - kOc2Scratch, coarse, c->create_xyz);
             if (plan.ok && plan.bcols >= 4) {
                 c->oc_plan = true;
                 c->oc_rows = plan.n_rows; c->oc_bcols = plan.bcols; c->oc_veclen = plan.vec_len;
@@ -707,10 +688,9 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
                 }
                 {   // block-local smoother: degree-2 Chebyshev polynomial of D^-1 A_bb on [hi / ratio, hi], hi = the plan's estimate
                     // of lambda_max + 10 % (the polynomial stays positive up to 1.125 hi); ADMM_HIP_OC_CHEB=0: plain Jacobi
-                    const char *ch = getenv("ADMM_HIP_OC_CHEB"), *cr = getenv("ADMM_HIP_OC_CHEB_RATIO");
                     c->oc_sm_ab = 0.0; c->oc_sm_b = 0.0; c->oc_lam_bb = plan.lam_bb;
-                    if (!(ch && ch[0] == '0') && plan.lam_bb > 0.0) {
-                        const double ratio = cr ? std::max(1.5, atof(cr)) : 400.0;      // (16 until round 6's last session: with the wider interval 1-2.5 % fewer iterations on the 1 M-tet bodies, 200-frame drift unchanged -- profiles/r06_block_smoother_fix.txt)
+                    if (env_flag("ADMM_HIP_OC_CHEB", true) && plan.lam_bb > 0.0) {
+                        const double ratio = 400.0;      // (16 until round 6's last session: with the wider interval 1-2.5 % fewer iterations on the 1 M-tet bodies, 200-frame drift unchanged -- profiles/r06_block_smoother_fix.txt)
                         // upper end of the interval: the plan's estimate of lambda_max(D^-1 A_bb) (power iterations from three
                         // starts, run until they stagnate) + 10 %, never above the plan's rigorous Gershgorin bound; the polynomial
                         // stays positive up to 1.125 x this value
@@ -718,26 +698,6 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
                         const double sg = th / de, r0 = 1.0 / sg, r1 = 1.0 / (2.0 * sg - r0);
                         const double al = (1.0 + r1 * r0) / th + 2.0 * r1 / de, be = 2.0 * r1 / (de * th);
                         c->oc_sm_ab = al - be; c->oc_sm_b = be;
-                        // ADMM_HIP_OC_CHEB=3: three Chebyshev steps = a degree-2 polynomial Z(B) = c0 + c1 B + c2 B^2 of B = D^-1 A_bb
-                        // (two block-local products per application).  The coefficients come from running the three-term
-                        // recurrence on polynomials: z = Z(B) y, D^-1 res = R(B) y with y = D^-1 r, R = 1 - B Z.  The kernel applies
-                        // it in Horner form, Z y = c0 y + B (c1 y + c2 B y):  v1 = (c1 + c2) y + c2 N y,  Z y = c0 y + v1 + N v1,
-                        // N = D^-1 offdiag(A_bb).  An odd-degree residual polynomial keeps Z positive above the interval too.
-                        c->oc_sm_c0 = c->oc_sm_k1 = c->oc_sm_k2 = 0.0;
-                        if (ch && ch[0] == '3') {
-                            double Z[3] = {0, 0, 0}, R[3] = {1, 0, 0}, P[3] = {1, 0, 0};
-                            double alpha = 1.0 / th, beta = 0.0;
-                            for (int k = 0; k < 3; ++k) {
-                                if (k > 0) {
-                                    beta = k > 1 ? 0.25 * (de * alpha) * (de * alpha) : 0.5 * (de * alpha) * (de * alpha);
-                                    alpha = 1.0 / (th - beta / alpha);
-                                    for (int i = 0; i < 3; ++i) P[i] = R[i] + beta * P[i];
-                                }
-                                for (int i = 0; i < 3; ++i) Z[i] += alpha * P[i];
-                                for (int i = 2; i > 0; --i) R[i] -= alpha * P[i - 1];
-                            }
-                            c->oc_sm_c0 = Z[0]; c->oc_sm_k1 = Z[1] + Z[2]; c->oc_sm_k2 = Z[2];
-                        }
                     }
                 }
                 if (getenv("ADMM_HIP_OC_DIAG"))
@@ -764,35 +724,18 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
     if ((e = c->oc_bar.alloc(2 * 32 * 16)) != hipSuccess) return e;
     if ((e = c->oc_bar.zero()) != hipSuccess) return e;
     if ((e = hipMemset(c->oc_ubuf.p, 0, c->oc_ubuf.n * sizeof(double))) != hipSuccess) return e;
-    {   // diagnosis switches, read once
-        const char *pe = getenv("ADMM_HIP_OC_PROF"), *pb = getenv("ADMM_HIP_OC_PROF_BLOCK"), *pd = getenv("ADMM_HIP_OC_DEBUG");
-        c->oc_debug = pd && pd[0] == '1';
-        { const char *ve = getenv("ADMM_HIP_OC_VERIFY"); c->oc_always_verify = ve && ve[0] == '1'; }   // A/B, tests: verify every pass (pcg_onchip2.hpp: kOc2TrustIters)
-        c->oc_prof_block = pb ? atoi(pb) : 0;
-        if (pe && pe[0] == '1') { if ((e = c->oc_prof.alloc(64 * 8)) != hipSuccess) return e; if ((e = c->oc_prof.zero()) != hipSuccess) return e; }
-    }
-    {   // which blocks does every block gather from?  (ADMM_HIP_OC_NO_NBR=1: every gather waits for a grid barrier instead)
-        const char *off = getenv("ADMM_HIP_OC_NO_NBR");
-        if (!(off && off[0] == '1') && plan.nbr_ok) {
-            if ((e = c->oc_nbr.upload(plan.nbr)) != hipSuccess) return e;
-            if ((e = c->oc_flags.alloc((size_t)8 * G)) != hipSuccess) return e;
-            if ((e = c->oc_flags.zero()) != hipSuccess) return e;
-        }
+    // diagnosis switches
+    c->oc_debug = env_flag("ADMM_HIP_OC_DEBUG", false);
+    c->oc_always_verify = env_flag("ADMM_HIP_OC_VERIFY", false);      // A/B, tests: verify every pass (pcg_onchip2.hpp: kOc2TrustIters)
+    c->oc_prof_block = env_int("ADMM_HIP_OC_PROF_BLOCK", 0);
+    if (env_flag("ADMM_HIP_OC_PROF", false)) { if ((e = c->oc_prof.alloc(64 * 8)) != hipSuccess) return e; if ((e = c->oc_prof.zero()) != hipSuccess) return e; }
+    if (plan.nbr_ok) {      // which blocks does every block gather from?
+        if ((e = c->oc_nbr.upload(plan.nbr)) != hipSuccess) return e;
+        if ((e = c->oc_flags.alloc((size_t)8 * G)) != hipSuccess) return e;
+        if ((e = c->oc_flags.zero()) != hipSuccess) return e;
     }
     c->oc_enabled = true;
-    { const char *ta = getenv("ADMM_HIP_TEST_ABORT_SOLVE"); c->test_abort_seq = ta ? atoi(ta) : 0; }
-    {   // the record lists in internal row order (tets only: triangles and hinges keep the gather launch).  OPT-IN (ADMM_HIP_FUSE_RHS=1): built
-        // and measured in round 6 (and, differently, in round 3) -- correct, bit-identical right-hand sides, and ~1 % SLOWER on the bench body:
-        // inside k_pcg2 the gather costs 16 us of the fill phase (8 -> 24 us, interleaved with the slab loads or not: a wave's 64 rows are a
-        // length-sorted sample of its block, their 32-byte records share no cache lines -- k_gather_rhs walks the records in vertex order on
-        // 32 waves per CU and takes 10.4 us) against the 10.4 us kernel + ~3 us launch gap it replaces (profiles/r06_fused_rhs_ab.txt).
-        const char *fe = getenv("ADMM_HIP_FUSE_RHS");
-        if ((fe && fe[0] == '1') && c->nt > 0 && c->ntri == 0 && c->nbend == 0 && c->world == 1 && !c->rec_vertex_h.empty()) {
-            std::vector<int32_t> rv(c->oc_orig_h.begin(), c->oc_orig_h.end());
-            if ((e = c->oc_inc.upload(admm_host::record_incidence(c->nv, c->n_rec, c->rec_vertex_h.data(), c->n_rec, rv.data(), c->oc_rows))) != hipSuccess) return e;
-            c->fuse_rhs_ok = true;
-        }
-    }
+    c->test_abort_seq = env_int("ADMM_HIP_TEST_ABORT_SOLVE", 0);
     return hipSuccess;
 }
 
@@ -839,8 +782,7 @@ bool ensure_big_plan(admm_hip_ctx *c) {
     if (!c->big_allowed) return false;      // ADMM_HIP_BIG=0 at create: the Jacobi PCG of rounds 1-4 (A/B, tests)
     std::vector<double> mass(c->n3);
     if (hipMemcpy(mass.data(), c->m.p, mass.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return false;
-    const char *ma = getenv("ADMM_HIP_BIG_AGGREGATES");
-    const admm_host::BigPlan P = admm_host::build_big_plan(c->Ahat, mass.data(), c->xyz_h.size() == (size_t)c->n3 ? c->xyz_h.data() : nullptr, ma ? std::max(1, atoi(ma)) : 1024);
+    const admm_host::BigPlan P = admm_host::build_big_plan(c->Ahat, mass.data(), c->xyz_h.size() == (size_t)c->n3 ? c->xyz_h.data() : nullptr, env_int("ADMM_HIP_BIG_AGGREGATES", 1024, 1));
     if (!P.ok) return false;
     auto ok = [](hipError_t e) { return e == hipSuccess; };
     const size_t n3r = 3 * (size_t)P.n_rows;
@@ -963,14 +905,12 @@ int launch_pcg_big(admm_hip_ctx *c, const double *b, double *x, int max_iters) {
     // chunks of 8 cost a late solve of an ADMM frame (1-5 iterations) 11-15 idle iterations = 33-45 empty launches.  Since round 6 the FIRST chunk
     // is what the solve at the same position of the previous frame needed (+ 1: the iteration that reports convergence), the chunks behind it
     // are short (an iteration is >= 70 us of kernels at these sizes; the host needs ~ 20 us to see a mark and launch the next chunk).
-    // ADMM_HIP_BIG_CHUNK=8: the fixed chunks of round 5 (A/B).
-    static const int fixed_chunk = [] { const char *e = getenv("ADMM_HIP_BIG_CHUNK"); return e ? std::max(1, atoi(e)) : 0; }();
-    static const int tail_chunk = [] { const char *e = getenv("ADMM_HIP_BIG_TAIL"); return e ? std::max(1, atoi(e)) : 2; }();
+    constexpr int tail_chunk = 2;
     const int pos = std::min(std::max(c->rc_iter, 0), (int)(sizeof(c->big_its_hist) / sizeof(c->big_its_hist[0])) - 1);
-    const int first = fixed_chunk ? fixed_chunk : (c->big_its_hist[pos] > 0 ? c->big_its_hist[pos] + 1 : 8);
+    const int first = c->big_its_hist[pos] > 0 ? c->big_its_hist[pos] + 1 : 8;
     bool seen = false;
     while (launched < max_iters) {
-        const int n = std::min(fixed_chunk ? fixed_chunk : (chunks == 0 ? first : tail_chunk), max_iters - launched);
+        const int n = std::min(chunks == 0 ? first : tail_chunk, max_iters - launched);
         for (int it = launched; it < launched + n; ++it) {
             hipLaunchKernelGGL(k_big_spmv, dim3(c->big_NBt), dim3(256), 0, st, a, it);
             hipLaunchKernelGGL(k_big_vec, dim3(c->big_G), dim3(kBigVecT), 0, st, a, it, (it == launched + n - 1) ? 1 : 0);
@@ -1076,13 +1016,13 @@ int launch_pcg_recycled(admm_hip_ctx *c, const double *b, double *x) {
     // frame's ~190 PCG iterations on the bench body whatever the recycled basis held; with the step in front 18-22 (experiments/iters_log.py),
     // 8.2 -> 5.4 iterations per solve over 200 frames, drift 3.9e-6 -> 3.2e-6 (profiles/r05_drift_start_projection.txt).  In front of the first
     // solve (mask 3) or the third (mask 6) it costs more than it saves.  Three small launches (k_defl_*), ~0.1 ms per frame.
-    if (c->defl_start && !c->defl_start_hold && c->defl_k > 0 && c->defl_now && c->rc_iter < 31 && ((c->defl_start >> c->rc_iter) & 1)) launch_deflation(c, b, x);
+    if (c->defl_start && !c->defl_start_hold && c->defl_k > 0 && c->rc_iter < 31 && ((c->defl_start >> c->rc_iter) & 1)) launch_deflation(c, b, x);
     c->defl_armed = false;
     c->big_rfin_valid = false;
     const int rc = launch_pcg_recycled_impl(c, b, x);
     // (fused into k_pcg2's epilogue when the on-chip kernel ran WITH it -- launch_pcg2 says so: a solve that went there without the recycled
     // basis, ADMM_HIP_NO_RECYCLE=1, or down the launch path gets the separate kernels)
-    if (rc == 0 && c->defl_k > 0 && c->defl_now && !c->defl_armed) launch_deflation(c, b, x, c->big_rfin_valid);
+    if (rc == 0 && c->defl_k > 0 && !c->defl_armed) launch_deflation(c, b, x, c->big_rfin_valid);
     return rc;
 }
 int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
@@ -1098,13 +1038,7 @@ int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
         // own pairs and the history of the same solve index, interleaved by expected value: own(s-1), prev(s), prev2(s), own(s-2),
         // prev(s+1), own(s-3), prev2(s+1), own(s-4)
         auto add = [&](int q, int frame, bool valid) { if (valid && B.cnt < rc_pairs) { B.E[B.cnt] = c->rc_Ef(q, frame); B.R[B.cnt] = c->rc_Rf(q, frame); ++B.cnt; } };
-        const int H = c->kRcHist;
-        if (!c->rc_order[std::min(s, 2)].empty()) {
-            for (auto &t : c->rc_order[std::min(s, 2)]) {
-                if (t[0] == 0) add(s - t[1], fr, t[1] >= 1 && s - t[1] >= 0);
-                else add(s + t[1], fr - t[2], s + t[1] >= 0 && s + t[1] < H && s + t[1] < c->rc_vb[t[2]]);
-            }
-        } else {
+        const int H = admm_hip_ctx::kRcHist;
         add(s - 1, fr, s - 1 >= 0);
         add(s, fr - 1, s < H && s < c->rc_prev_valid);
         add(s, fr - 2, s < H && s < c->rc_prev2_valid);
@@ -1113,7 +1047,6 @@ int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
         add(s - 3, fr, s - 3 >= 0);
         add(s + 1, fr - 2, s + 1 < H && s + 1 < c->rc_prev2_valid);
         add(s - 4, fr, s - 4 >= 0);
-        }
         OcRc rc; rc.on = true; rc.B = B; rc.Eslot = c->rc_Ef(s, fr); rc.Rslot = c->rc_Rf(s, fr);
         const int r = launch_pcg_onchip(c, b, x, c->pcg_max_iters, rc);
         c->rc_iter = s + 1;
@@ -1126,11 +1059,8 @@ int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
     // parallel.  (E, A E) pairs stay exact whatever the state does -- the matrix of a scene never changes -- so this can only
     // help or do nothing.  Round 1 measured "no gain" for this with the Jacobi preconditioner; with the two-level one the CPU
     // prototype (experiments/first_solve_proto.py) gives 53 -> 19..26 iterations for the first solve, 30 -> 11..17 for the second.
-    static const bool rc_prev = [] { const char *e = getenv("ADMM_HIP_RC_PREV"); return !(e && e[0] == '0'); }();
-    if (rc_prev)
-        for (int q = s; q < kRc && q < c->rc_prev_valid && B.cnt < rc_pairs; ++q) { B.E[B.cnt] = c->rc_E(q); B.R[B.cnt] = c->rc_R(q); ++B.cnt; }
-    static const bool rc_kernels = getenv("ADMM_HIP_RC_KERNELS") && getenv("ADMM_HIP_RC_KERNELS")[0] == '1';   // A/B: separate k_rc_* launches
-    if (c->oc_enabled && (!rc_kernels || c->oc_plan)) {   // (the plan's pairs live in its internal row order: k_rc_* cannot read them)   // projection, solve and the new pair in ONE persistent launch
+    for (int q = s; q < kRc && q < c->rc_prev_valid && B.cnt < rc_pairs; ++q) { B.E[B.cnt] = c->rc_E(q); B.R[B.cnt] = c->rc_R(q); ++B.cnt; }
+    if (c->oc_enabled) {   // (the plan's pairs live in its internal row order: k_rc_* cannot read them)   // projection, solve and the new pair in ONE persistent launch
         OcRc rc; rc.on = true; rc.B = B; rc.Eslot = c->rc_E(s); rc.Rslot = c->rc_R(s);
         const int r = launch_pcg_onchip(c, b, x, c->pcg_max_iters, rc);
         c->rc_iter = s + 1;
@@ -1207,16 +1137,14 @@ int uz_make_lanes(admm_hip_ctx *c, int L) {
         c->uz_lanes.emplace_back();
         Lane &ln = c->uz_lanes.back();
         // the runtime keeps separate hardware queues per stream priority: lanes of different priority never share one
-        static const int prio_mode = [] { const char *e = getenv("ADMM_HIP_UZ_LANE_PRIO"); return e ? atoi(e) : 1; }();
         int plo = 0, phi = 0;
         (void)hipDeviceGetStreamPriorityRange(&plo, &phi);      // (lowest, highest): numerically phi <= plo
         const int idx = (int)c->uz_lanes.size() - 1, span = plo - phi + 1;
         // (highest and lowest first, three lanes each, then the default priority: that class also carries the context's own stream and the
         //  process's null stream -- a fourth lane in one class shares a hardware queue with another and the two serialise)
         int prio = 0;
-        if (prio_mode == 2 && span > 1) prio = phi + idx % span;      // plain cycle (A/B)
-        else if (prio_mode && span > 2) { static const int cls[8] = {0, 1, 0, 1, 0, 1, 2, 2}; const int k = cls[idx & 7]; prio = k == 0 ? phi : k == 1 ? plo : (phi + plo) / 2; }
-        else if (prio_mode && span > 1) prio = (idx & 1) ? plo : phi;
+        if (span > 2) { static const int cls[8] = {0, 1, 0, 1, 0, 1, 2, 2}; const int k = cls[idx & 7]; prio = k == 0 ? phi : k == 1 ? plo : (phi + plo) / 2; }
+        else if (span > 1) prio = (idx & 1) ? plo : phi;
         if (hipStreamCreateWithPriority(&ln.st, hipStreamNonBlocking, prio) != hipSuccess || hipEventCreateWithFlags(&ln.done, hipEventDisableTiming) != hipSuccess) return -1;
         size_t off = 0;
         auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -1276,7 +1204,7 @@ int uz_lanes_converged(admm_hip_ctx *c, int L, int *converged) {      // (after 
 // The batch of uz_ensure_columns on L side streams.  *converged = solves that met their tolerance.  0 ok, -1 error.
 int uz_columns_on_lanes(admm_hip_ctx *c, const std::vector<int> &miss, const std::vector<int> &slots, int n_missing, int L, int max_iters,
                         int *launched, int *converged) {
-    static const bool dbg = [] { const char *e = getenv("ADMM_HIP_UZ_LANES_DEBUG"); return e && e[0] == '1'; }();
+    const bool dbg = c->uz_lanes_debug;
     const auto t_enq0 = std::chrono::steady_clock::now();
     if (uz_lanes_enqueue(c, miss, slots, n_missing, L, max_iters, launched)) return -1;
     for (int l = 0; l < L; ++l)
@@ -1307,9 +1235,8 @@ int uz_grow_cols(admm_hip_ctx *c, size_t top) {
     return 1;
 }
 
-double uz_column_tol(const admm_hip_ctx *c) {      // a fraction of the solver's own (ADMM_HIP_UZ_COL_TOL=f, default 0.01), never looser than 1e-10
-    static const double col_factor = [] { const char *e = getenv("ADMM_HIP_UZ_COL_TOL"); const double f = e ? atof(e) : 0.01; return f > 0.0 && f <= 1.0 ? f : 0.01; }();
-    return std::min(col_factor * c->pcg_tol, 1e-10);
+double uz_column_tol(const admm_hip_ctx *c) {      // a hundredth of the solver's own, never looser than 1e-10
+    return std::min(0.01 * c->pcg_tol, 1e-10);
 }
 
 // LOOK-AHEAD.  The columns in flight are done (block: wait for them): commit their slots, or give the look-ahead up when a solve missed
@@ -1324,8 +1251,7 @@ int uz_ahead_harvest(admm_hip_ctx *c, bool block) {
     int conv = 0;
     if (uz_lanes_converged(c, c->pf_lanes, &conv)) return -1;
     const bool aborted = c->h_sig && c->h_sig[2];
-    { static const bool dbg = [] { const char *e = getenv("ADMM_HIP_UZ_LANES_DEBUG"); return e && e[0] == '1'; }();
-      if (dbg) fprintf(stderr, "[uz_ahead] ctx %p frame %d: harvest (%s) of %d columns: %d of %d launches converged%s\n", (void *)c, c->rc_frame, block ? "waited" : "polled",
+    { if (c->uz_lanes_debug) fprintf(stderr, "[uz_ahead] ctx %p frame %d: harvest (%s) of %d columns: %d of %d launches converged%s\n", (void *)c, c->rc_frame, block ? "waited" : "polled",
                        (int)c->pf_v.size(), conv, c->pf_launched, aborted ? ", ABORTED" : ""); }
     if (!aborted && conv == c->pf_launched) {
         for (size_t k = 0; k < c->pf_v.size(); ++k) c->uzc_slot_h[c->pf_v[k]] = c->pf_slot[k];
@@ -1342,11 +1268,11 @@ int uz_ahead_harvest(admm_hip_ctx *c, bool block) {
 // Launch the column solves of the `count` vertices k_uz_near listed, on the lanes, WITHOUT waiting: they run beside the ADMM loop
 // (lanes + the loop's own k_pcg2 <= what the chip holds).  0 ok (also when there was nothing to do), -1 error.
 int uz_ahead_launch(admm_hip_ctx *c, int count) {
-    static const bool dbg = [] { const char *e = getenv("ADMM_HIP_UZ_LANES_DEBUG"); return e && e[0] == '1'; }();
+    const bool dbg = c->uz_lanes_debug;
     if (count <= 0 || !c->pf_v.empty()) return 0;
     // Fewer lanes than a batch the loop WAITS for: the loop's own persistent kernels (k_pcg2, the Schur CG with up to 100 KB of LDS per
-    // block) must find their CUs beside the lanes' blocks (ADMM_HIP_UZ_AHEAD_LANES=n, default 4).
-    static const int ahead_lanes = [] { const char *e = getenv("ADMM_HIP_UZ_AHEAD_LANES"); return e ? std::max(1, std::min(8, atoi(e))) : 4; }();
+    // block) must find their CUs beside the lanes' blocks.
+    constexpr int ahead_lanes = 4;
     const int L = std::min(std::min(c->uz_lanes_cfg > 0 ? c->uz_lanes_cfg : 8, ahead_lanes), uz_lane_fit(c) - 1);
     if (L < 1) { c->pf_on = false; return 0; }
     std::vector<int> list(count);
@@ -1556,11 +1482,9 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
     hipLaunchKernelGGL(k_uz_ct, dim3(gv), dim3(256), 0, st, nv, 0, b, c->uz_cn.p, c->uz_y.p, c->uz_q1.p);       // q1 = b - C^T y
     if (dyn) launch_ct_dyn(c, nq, qlist, 0, c->uz_y.p, dface, dbary, c->uz_q1.p);
     // x = A^-1 q1, warm-started from the current x and -- like the contact-free solves -- projected on the recycled pairs first
-    // (ADMM_HIP_UZ_RECYCLE=0: plain warm start, as in rounds 1-2)
-    static const bool uz_rc = [] { const char *e = getenv("ADMM_HIP_UZ_RECYCLE"); return !(e && e[0] == '0'); }();
     c->defl_start_hold = true;      // (with constraint rows the first solve's right-hand side b - C^T y is the multipliers' kick, not the soft-mode
                                     // transient of the free solve: the step in front buys nothing there -- cube100k_uzawa_floor 1 357 against 1 396)
-    const int rc_first = uz_rc ? launch_pcg_recycled(c, c->uz_q1.p, x) : launch_pcg(c, c->uz_q1.p, x, c->pcg_max_iters);
+    const int rc_first = launch_pcg_recycled(c, c->uz_q1.p, x);
     c->defl_start_hold = false;
     if (rc_first) return -1;
     hipLaunchKernelGGL(k_uz_resid, dim3(gv), dim3(256), 0, st, nv, x, c->uz_cn.p, c->uz_cc.p, c->uz_r.p, c->uz_d.p, dface, dbary, c->uz_scal.p);
@@ -1805,8 +1729,7 @@ void launch_gs_persist(admm_hip_ctx *c, const double *b, double *x) {
 // Plan + buffers of the persistent GS kernel; leaves gsp_enabled = false when the scene does not fit (the colour kernels serve it).
 hipError_t plan_gs_persist(admm_hip_ctx *c) {
     c->gsp_enabled = false;
-    const char *env = getenv("ADMM_HIP_GS_PERSIST");
-    if (env && env[0] == '0') return hipSuccess;
+    if (!env_flag("ADMM_HIP_GS_PERSIST", true)) return hipSuccess;
     static_assert(kGspMaxCK == admm_host::kGspMaxC && kGspHdrK == admm_host::kGspHdr, "gs_persist.hpp and host_setup.hpp disagree on the plan layout");
     if (c->n_colors < 1 || c->n_colors > kGspMaxCK || (int64_t)c->gs_max_iters * c->n_colors >= 2000) return hipSuccess;   // (stamp space of one solve)
     hipDeviceProp_t prop;
@@ -1814,29 +1737,20 @@ hipError_t plan_gs_persist(admm_hip_ctx *c) {
     if (e != hipSuccess) return e;
     const int cus = prop.multiProcessorCount;
     const int lds_max = (int)std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024);
-    const char *rt = getenv("ADMM_HIP_GS_ROWS");
     // (rows per block: 384 through round 5; with the two-granule / whole-sector hand-off of round 6 a phase no longer pays per granule and smaller
     // blocks -- fewer granules to wait for, a shorter fill -- win: cube100k_gs 96 / 128 / 192 / 256 / 320 / 384 / 448 rows = 5 407 / 5 584 / 5 858 /
     // 5 773 / 5 702 / 5 298 / 5 142 ADMM it/s, profiles/r06_gs_rows_per_block.txt; bodies beyond 49 k vertices fill all CUs either way)
-    const int rows_target = rt ? std::max(32, atoi(rt)) : kGspRowsTarget;
+    const int rows_target = env_int("ADMM_HIP_GS_ROWS", kGspRowsTarget, 32);
     std::vector<int32_t> col32(c->color_h.begin(), c->color_h.end());
-    // Blocks: one per CU.  (ADMM_HIP_GS_BLOCKS_PER_CU=2, an experiment of round 6: two per CU for bodies with more than cus x rows_target rows -- the
-    // 200 k-triangle cloth as 512 blocks of 197 rows instead of 256 of 393.  Measured: 3 452 -> 2 850 ADMM it/s; two waves per SIMD stretch every
-    // row's chain and the block barrier (0.03 -> 0.27 us).  Every block of a persistent kernel must be resident at once: the occupancy query decides,
-    // a plan that does not fit two per CU is rebuilt for one.  profiles/r06_gs_rows_per_block.txt)
-    const char *bpc = getenv("ADMM_HIP_GS_BLOCKS_PER_CU");
-    int want_per_cu = bpc ? std::max(1, std::min(2, atoi(bpc))) : 1;
-    admm_host::GsPlan P;
+    // Blocks: one per CU.  (Two per CU for bodies with more than cus x rows_target rows was measured in round 6 -- the 200 k-triangle cloth as
+    // 512 blocks of 197 rows instead of 256 of 393: 3 452 -> 2 850 ADMM it/s; two waves per SIMD stretch every row's chain and the block barrier
+    // (0.03 -> 0.27 us).  profiles/r06_gs_rows_per_block.txt)
+    const admm_host::GsPlan P = admm_host::build_gs_plan(c->Ahat, c->n_colors, col32.data(), cus, rows_target, lds_max);
+    if (!P.ok) return hipSuccess;
     int per_cu = 0;
-    for (;;) {
-        P = admm_host::build_gs_plan(c->Ahat, c->n_colors, col32.data(), cus * want_per_cu, rows_target, lds_max);
-        if (!P.ok) { if (want_per_cu > 1) { want_per_cu = 1; continue; } return hipSuccess; }
-        if ((e = hipFuncSetAttribute((const void *)k_gs_persist, hipFuncAttributeMaxDynamicSharedMemorySize, P.lds_bytes)) != hipSuccess) return e;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gs_persist, kGspT, P.lds_bytes)) != hipSuccess) return e;
-        if (per_cu >= 1 && P.G <= cus * std::min(per_cu, want_per_cu)) break;
-        if (want_per_cu > 1) { want_per_cu = 1; continue; }
-        return hipSuccess;      // every block must be resident at once
-    }
+    if ((e = hipFuncSetAttribute((const void *)k_gs_persist, hipFuncAttributeMaxDynamicSharedMemorySize, P.lds_bytes)) != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gs_persist, kGspT, P.lds_bytes)) != hipSuccess) return e;
+    if (per_cu < 1 || P.G > cus) return hipSuccess;      // every block must be resident at once
     if ((e = c->gsp_hdr.upload(std::vector<int>(P.hdr.begin(), P.hdr.end()))) != hipSuccess) return e;
     if ((e = c->gsp_orig.upload(std::vector<int>(P.orig.begin(), P.orig.end()))) != hipSuccess) return e;
     if ((e = c->gsp_out.upload(std::vector<int>(P.out_idx.begin(), P.out_idx.end()))) != hipSuccess) return e;
@@ -1853,15 +1767,18 @@ hipError_t plan_gs_persist(admm_hip_ctx *c) {
     if ((e = c->gsp_meet.zero()) != hipSuccess) return e;
     if ((e = c->gsp_abort.alloc(16)) != hipSuccess) return e;
     if ((e = c->gsp_abort.zero()) != hipSuccess) return e;
-    { const char *pe = getenv("ADMM_HIP_GSP_PROF"), *pb = getenv("ADMM_HIP_GSP_PROF_BLOCK");
-      if (pe && pe[0] == '1') { if ((e = c->gsp_prof.alloc(16)) != hipSuccess) return e; if ((e = c->gsp_prof.zero()) != hipSuccess) return e; c->gsp_prof_block = pb ? atoi(pb) : 0; } }
+    if (env_flag("ADMM_HIP_GSP_PROF", false)) {
+        if ((e = c->gsp_prof.alloc(16)) != hipSuccess) return e;
+        if ((e = c->gsp_prof.zero()) != hipSuccess) return e;
+        c->gsp_prof_block = env_int("ADMM_HIP_GSP_PROF_BLOCK", 0);
+    }
     c->gsp_G = P.G; c->gsp_C = P.C; c->gsp_lds = (size_t)P.lds_bytes;
     c->gsp_stat[0] = P.G; c->gsp_stat[1] = P.max_rows; c->gsp_stat[2] = P.max_halo; c->gsp_stat[3] = P.max_nbr; c->gsp_stat[4] = P.ob_total; c->gsp_stat[5] = P.lds_bytes;
     if (getenv("ADMM_HIP_OC_DIAG"))
         fprintf(stderr, "[gs_plan] %d blocks x %d threads, <= %d rows and %d halo entries per block, <= %d neighbour blocks, %d outbox nodes, %d bytes of LDS\n",
                 P.G, kGspT, P.max_rows, P.max_halo, P.max_nbr, P.ob_total, P.lds_bytes);
     c->gsp_enabled = true;
-    { const char *ta = getenv("ADMM_HIP_TEST_ABORT_SOLVE"); c->test_abort_seq = ta ? atoi(ta) : 0; }
+    c->test_abort_seq = env_int("ADMM_HIP_TEST_ABORT_SOLVE", 0);
     return hipSuccess;
 }
 
@@ -2203,10 +2120,6 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     c->linsolver = d->linsolver;
     c->pcg_max_iters = d->pcg_max_iters > 0 ? d->pcg_max_iters : 500;
     c->pcg_tol = d->pcg_tol > 0 ? d->pcg_tol : 1e-10;
-    { const char *e1 = getenv("ADMM_HIP_TOL_LAST"), *e2 = getenv("ADMM_HIP_TOL_LAST_N"); c->tol_last = e1 ? atof(e1) : 0.0; c->tol_last_n = e2 ? atoi(e2) : 0; }
-    if (const char *ts = getenv("ADMM_HIP_TOL_SCHED")) {   // experiments: "20,20,5" = the first three solves of a step at 20x, 20x, 5x pcg_tol
-        for (const char *q = ts; *q; ) { char *end = nullptr; const double v = strtod(q, &end); if (end == q) break; c->tol_sched.push_back(v > 0.0 ? v : 1.0); q = *end == ',' ? end + 1 : end; }
-    }
     c->gs_max_iters = d->gs_max_iters > 0 ? d->gs_max_iters : 30;
     c->gs_tol = d->gs_tol >= 0 ? d->gs_tol : 1e-10;
     c->gs_omega = d->gs_omega > 0 ? d->gs_omega : 1.9;
@@ -2236,8 +2149,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     std::vector<int32_t> g_order;
     {
         // (this rank's elements only: the lists are built from them)
-        const char *gw = getenv("ADMM_HIP_GATHER_SORT");
-        g_order = admm_host::incidence_row_order(nv, te - tb, d->tet_idx + 4 * (size_t)tb, re - rb, d->tri_idx + 3 * (size_t)rb, gw ? atoi(gw) : 0);
+        g_order = admm_host::incidence_row_order(nv, te - tb, d->tet_idx + 4 * (size_t)tb, re - rb, d->tri_idx + 3 * (size_t)rb, 0);
         HIP_TRY(c->g_order.upload(std::vector<int>(g_order.begin(), g_order.end())));
     }
     // ---- tets: sort by constitutive model (wave-uniform code paths), build the material table ----
@@ -2289,9 +2201,8 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
         HIP_TRY(c->t_idx.upload(idx)); HIP_TRY(c->t_sc.upload(sc));
         {   // Binv: recomputed by the local step from the rest positions when the tets come from one set of positions (they do
             // when TetEnergyTerm's constructor made them), streamed otherwise.  ADMM_HIP_TET_REST=0: always streamed (A/B, tests).
-            const char *e = getenv("ADMM_HIP_TET_REST");
             std::vector<double> x0((size_t)3 * nv);
-            c->tet_rest_mode = (e && e[0] == '0') ? 0 : admm_host::tet_rest_positions(nv, nt, d->tet_idx + 4 * (size_t)tb, d->tet_Binv + 9 * (size_t)tb, d->vert_xyz, x0.data());   // (this rank's tets)
+            c->tet_rest_mode = !env_flag("ADMM_HIP_TET_REST", true) ? 0 : admm_host::tet_rest_positions(nv, nt, d->tet_idx + 4 * (size_t)tb, d->tet_Binv + 9 * (size_t)tb, d->vert_xyz, x0.data());   // (this rank's tets)
             if (c->tet_rest_mode) HIP_TRY(c->t_x0.upload(x0));
             else HIP_TRY(c->t_Binv.upload(Binv));
         }
@@ -2315,7 +2226,6 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
         HIP_TRY(c->t_rec.alloc((size_t)4 * (ch.n_rec + 1))); HIP_TRY(c->t_rec.zero());     // record n_rec stays zero: the padding of the incidence lists
         HIP_TRY(c->t_inc.upload(admm_host::record_incidence(nv, ch.n_rec, ch.rec_vertex.data(), ch.n_rec, g_order.data())));
         c->n_rec = ch.n_rec;
-        c->rec_vertex_h = ch.rec_vertex;
     }
     // ---- tris ----
     c->ntri = re - rb; c->ldr = c->ntri + 1;
@@ -2481,15 +2391,15 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     HIP_TRY(c->cg_scal.alloc(2)); HIP_TRY(c->cg_scal.zero());
     HIP_TRY(c->counters.alloc(8 + 64 + 8)); HIP_TRY(c->counters.zero());   // [72..74]: totals since create (on-chip PCG); [75] block smoother given up, [76] short-pass trust revoked, [77] failed sample checks (k_pcg2); [78] Schur products (k_uz_persist)
     c->create_xyz = d->vert_xyz;
-    { const char *e = getenv("ADMM_HIP_BIG"); c->big_allowed = !(e && e[0] == '0'); }
-    { const char *e = getenv("ADMM_HIP_DEFL_START"); if (e) c->defl_start = atoi(e); }
-    { const char *e = getenv("ADMM_HIP_DEFL_RESID"); c->defl_use_resid = !(e && e[0] == '0'); }
-    { const char *e = getenv("ADMM_HIP_DEFL_DBG"); if (e) c->defl_dbg = atoi(e); }      // (experiments; bit 3 = the recycled pair carries the soft step: 9.28 -> 8.93 iterations per solve, +1 % ADMM it/s, 200-frame drift 3.9e-6 -> 6.1e-6: off)
+    c->big_allowed = env_flag("ADMM_HIP_BIG", true);
+    c->defl_start = env_int("ADMM_HIP_DEFL_START", c->defl_start);
+    c->defl_use_resid = env_flag("ADMM_HIP_DEFL_RESID", true);
+    c->kernel_clock = env_flag("ADMM_HIP_KERNEL_CLOCK", false);
+    c->uz_lanes_debug = env_flag("ADMM_HIP_UZ_LANES_DEBUG", false);
     if (d->vert_xyz && d->linsolver != 1) c->xyz_h.assign(d->vert_xyz, d->vert_xyz + c->n3);      // (the launch-path two-level PCG plans lazily)
     {   // distributed solve of ONE body (ADMM_HIP_DIST_SOLVE=1, element-block partition): contiguous vertex rows per rank, 64-aligned
-        const char *de = getenv("ADMM_HIP_DIST_SOLVE");
-        const char *fc = getenv("ADMM_HIP_FORCE_COMM");     // (tests: a world of ONE with a communicator runs the same collectives through RCCL)
-        if (de && de[0] == '1' && (c->world > 1 || (fc && fc[0] == '1')) && d->linsolver != 1) {
+        const bool force_comm = env_flag("ADMM_HIP_FORCE_COMM", false);     // (tests: a world of ONE with a communicator runs the same collectives through RCCL)
+        if (env_flag("ADMM_HIP_DIST_SOLVE", false) && (c->world > 1 || force_comm) && d->linsolver != 1) {
             const int ns = (nv + 63) / 64;
             c->row_lo = 64 * (int)((int64_t)ns * c->rank / c->world);
             c->row_hi = c->rank + 1 == c->world ? nv : 64 * (int)((int64_t)ns * (c->rank + 1) / c->world);
@@ -2499,36 +2409,17 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     if (d->linsolver != 1 && !c->dist_solve) HIP_TRY(plan_pcg_onchip(c));
     c->create_xyz = nullptr;
     if (d->linsolver != 1) {
-        const char *env = getenv("ADMM_HIP_NO_RECYCLE");
-        c->rc_enabled = !(env && env[0] == '1');
-        {   // pairs per projection: ADMM_HIP_RC_PAIRS=n fixes the count; otherwise four until the scene has shown how many iterations its
-            // solves need (step_impl).  ADMM_HIP_RC_ADAPT=0: always four.
-            const char *pe = getenv("ADMM_HIP_RC_PAIRS"), *ae = getenv("ADMM_HIP_RC_ADAPT");
-            c->rc_pairs = pe ? std::max(0, std::min(kRc, atoi(pe))) : kRc;
-            // (Round 6 looked at this test again: it is biased -- the start-up transient decays from frame to frame, so the count measured SECOND
-            // looks better, and it picks three on the bench body where four need fewer iterations.  But fewer iterations from a richer basis are
-            // not free: see kRcHist.  The test stays.)
-            c->rc_adapt = !pe && !(ae && ae[0] == '0');
-        }
+        c->rc_enabled = !env_flag("ADMM_HIP_NO_RECYCLE", false);
+        // pairs per projection: four until the scene has shown how many iterations its solves need (step_impl).  (Round 6 looked at this
+        // test again: it is biased -- the start-up transient decays from frame to frame, so the count measured SECOND looks better, and it
+        // picks three on the bench body where four need fewer iterations.  But fewer iterations from a richer basis are not free: see kRcHist.
+        // The test stays.)
+        c->rc_pairs = kRc;
         c->NBR = std::max(1, std::min((nv + 255) / 256, 256));
         c->n3i = std::max(c->n3, 3 * c->oc_rows);
         if (c->rc_enabled) {
-            { const char *he = getenv("ADMM_HIP_RC_HIST"); c->rc_hist = (!(he && he[0] == '0') && c->oc_enabled && c->oc_plan) ? 1 : 0; }   // (=0: round 3's basis, A/B)
-            { const char *hn = getenv("ADMM_HIP_RC_HIST_N"); if (hn) c->kRcHist = std::max(1, std::min(64, atoi(hn))); }
-            { const char *de = getenv("ADMM_HIP_RC_DEPTH"); if (de) c->rc_depth = std::max(3, std::min(8, atoi(de))); }
-            for (int q = 0; q < 3; ++q) {      // ADMM_HIP_RC_ORDER0="p0.1,p0.2,p0.3,p1.1": see rc_order
-                const char *oe = getenv(q == 0 ? "ADMM_HIP_RC_ORDER0" : q == 1 ? "ADMM_HIP_RC_ORDER1" : "ADMM_HIP_RC_ORDER");
-                if (!oe) continue;
-                std::string str(oe); size_t pos = 0;
-                while (pos < str.size()) {
-                    size_t e = str.find(',', pos); if (e == std::string::npos) e = str.size();
-                    const std::string tok = str.substr(pos, e - pos); pos = e + 1;
-                    int a1 = 0, a2 = 0;
-                    if (tok.size() >= 2 && tok[0] == 'o' && sscanf(tok.c_str() + 1, "%d", &a1) == 1) c->rc_order[q].push_back({0, a1, 0});
-                    else if (tok.size() >= 4 && tok[0] == 'p' && sscanf(tok.c_str() + 1, "%d.%d", &a1, &a2) == 2 && a2 >= 1 && a2 < c->rc_depth) c->rc_order[q].push_back({1, a1, a2});
-                }
-            }
-            HIP_TRY(c->rc_buf.alloc((size_t)(admm_hip_ctx::kRcAllSlots + (c->rc_hist ? c->rc_depth * c->kRcHist : 0)) * 2 * c->n3i));
+            c->rc_hist = (c->oc_enabled && c->oc_plan) ? 1 : 0;
+            HIP_TRY(c->rc_buf.alloc((size_t)(admm_hip_ctx::kRcAllSlots + (c->rc_hist ? admm_hip_ctx::kRcDepth * admm_hip_ctx::kRcHist : 0)) * 2 * c->n3i));
             HIP_TRY(c->rc_r0.alloc(c->n3i)); HIP_TRY(c->rc_xs.alloc(c->n3i));
             HIP_TRY(c->rc_part.alloc((size_t)3 * kRcQ * c->NBR)); HIP_TRY(c->rc_coef.alloc(3 * kRc)); HIP_TRY(c->rc_coef.zero());
         }
@@ -2571,8 +2462,8 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
             HIP_TRY(c->gs_sell.upload(g.sell));
             HIP_TRY(c->gs_slot_node.upload(g.slot_node)); HIP_TRY(c->gs_diag.upload(g.diag));
             c->gs_color_slice.assign(g.color_slice.begin(), g.color_slice.end());
-            const char *g3 = getenv("ADMM_HIP_GS_THREE_KERNELS");   // A/B switch, read at create
-            if (c->n_colors == 2 && !(g3 && g3[0] == '1')) {   // two-colour scheme: roll-back copy + partial sums (2 x 2 x nbA last colour, 2 x nbB first colour)
+            const bool three_kernels = env_flag("ADMM_HIP_GS_THREE_KERNELS", false);   // A/B switch
+            if (c->n_colors == 2 && !three_kernels) {   // two-colour scheme: roll-back copy + partial sums (2 x 2 x nbA last colour, 2 x nbB first colour)
                 const int nbB = (c->gs_color_slice[1] - c->gs_color_slice[0] + 3) / 4, nbA = (c->gs_color_slice[2] - c->gs_color_slice[1] + 3) / 4;
                 HIP_TRY(c->gs_xb.alloc(c->n3)); HIP_TRY(c->gs_xb.zero());
                 HIP_TRY(c->gs_part2.alloc(4 * (size_t)nbA + 2 * (size_t)nbB)); HIP_TRY(c->gs_part2.zero());
@@ -2580,9 +2471,8 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
             // three colours (triangulated cloth): the same, generalised (k_gs_colorN): no residual SpMV per sweep.  Every colour kernel
             // pays ~1.3 us for its share of the residual, the SpMV launch it replaces cost 5.6 us: beyond three or four colours the plain
             // sequence is faster (ADMM_HIP_GS_FUSED_MAX=n raises the limit: tests).
-            const char *fm = getenv("ADMM_HIP_GS_FUSED_MAX");
-            const int fused_max = fm ? atoi(fm) : 3;
-            if (c->n_colors >= 3 && c->n_colors <= fused_max && !(g3 && g3[0] == '1')) {
+            const int fused_max = env_int("ADMM_HIP_GS_FUSED_MAX", 3);
+            if (c->n_colors >= 3 && c->n_colors <= fused_max && !three_kernels) {
                 int nE = 0;
                 for (int k = 0; k + 1 < c->n_colors; ++k) nE += (c->gs_color_slice[k + 1] - c->gs_color_slice[k] + 3) / 4;
                 const int nbL = (c->gs_color_slice[c->n_colors] - c->gs_color_slice[c->n_colors - 1] + 3) / 4;
@@ -2609,7 +2499,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     if (d->linsolver == 1) { HIP_TRY(c->gs_proj.alloc(1)); HIP_TRY(c->gs_proj.zero()); }
     if (d->linsolver == 1) HIP_TRY(plan_gs_persist(c));
     if (d->linsolver == 2) {
-        { const char *fz = getenv("ADMM_HIP_UZ_FREEZE"); c->uz_freeze = fz && fz[0] == '1'; }
+        c->uz_freeze = env_flag("ADMM_HIP_UZ_FREEZE", false);
         c->NBU = std::max(1, std::min((nv + 255) / 256, 256));
         HIP_TRY(c->uz_cn.alloc(c->n3)); HIP_TRY(c->uz_cn.zero());
         HIP_TRY(c->uz_q1.alloc(c->n3)); HIP_TRY(c->uz_q2.alloc(c->n3)); HIP_TRY(c->uz_q2.zero());
@@ -2620,24 +2510,24 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
         {   // column cache of the Schur iterations: needs A = K (x) I3 (per-vertex masses, which is all the reference has).
             // ADMM_HIP_UZ_CACHE=0 switches it off (every Schur iteration is then an on-chip PCG solve, as in rounds 1-2),
             // ADMM_HIP_UZ_CACHE_MB bounds its HBM (default 16 GiB of the 288; allocated at the first contact).
-            const char *e = getenv("ADMM_HIP_UZ_CACHE"), *mb = getenv("ADMM_HIP_UZ_CACHE_MB");
+            const char *mb = getenv("ADMM_HIP_UZ_CACHE_MB");
             bool per_vertex = true;
             for (int v = 0; v < nv && per_vertex; ++v)
                 per_vertex = d->masses[3 * (size_t)v] == d->masses[3 * (size_t)v + 1] && d->masses[3 * (size_t)v] == d->masses[3 * (size_t)v + 2];
             const double bytes = (mb ? atof(mb) : 16384.0) * 1048576.0;
             c->uzc_cap = (size_t)std::min<double>((double)nv, std::floor(bytes / (8.0 * nv)));
-            c->uzc_on = !(e && e[0] == '0') && per_vertex && c->uzc_cap >= 3;
+            c->uzc_on = env_flag("ADMM_HIP_UZ_CACHE", true) && per_vertex && c->uzc_cap >= 3;
             if (c->uzc_on) {
                 c->uzc_slot_h.assign(nv, -1);
                 HIP_TRY(c->uzc_slot.upload(c->uzc_slot_h)); HIP_TRY(c->uzc_act.alloc(nv)); HIP_TRY(c->uzc_miss.alloc(nv));
                 HIP_TRY(c->uzc_info.alloc(4)); HIP_TRY(c->uzc_info.zero()); HIP_TRY(c->uzc_flag.alloc(nv));
                 HIP_TRY(c->uzc_pos.alloc(nv)); HIP_TRY(c->uz_y0.alloc(nv));
-                { const char *te = getenv("ADMM_HIP_TEST_UZ_COL_ITERS"); c->uzc_test_iters = te ? atoi(te) : 0; }
-                { const char *ce = getenv("ADMM_HIP_UZ_COMPACT"); c->uzc_compact = !(ce && ce[0] == '0'); }
-                { const char *pe = getenv("ADMM_HIP_UZ_PERSIST"); c->uzp_enabled = !(pe && pe[0] == '0'); }
-                { const char *lb = getenv("ADMM_HIP_UZ_LIST_BLOCKS"); if (lb) c->uzc_one_block_max = std::max(0, atoi(lb)); }
-                { const char *ta = getenv("ADMM_HIP_TEST_ABORT_SCHUR"); c->test_abort_uzp = ta ? atoi(ta) : 0; }
-                { const char *le = getenv("ADMM_HIP_UZ_LANES"); c->uz_lanes_cfg = le ? std::max(1, std::min(8, atoi(le))) : 0; }      // streams of a batch of column solves (uz_lane_count)
+                c->uzc_test_iters = env_int("ADMM_HIP_TEST_UZ_COL_ITERS", 0);
+                c->uzc_compact = env_flag("ADMM_HIP_UZ_COMPACT", true);
+                c->uzp_enabled = env_flag("ADMM_HIP_UZ_PERSIST", true);
+                c->uzc_one_block_max = env_int("ADMM_HIP_UZ_LIST_BLOCKS", c->uzc_one_block_max, 0);
+                c->test_abort_uzp = env_int("ADMM_HIP_TEST_ABORT_SCHUR", 0);
+                c->uz_lanes_cfg = env_int("ADMM_HIP_UZ_LANES", 0, 1, 8);      // streams of a batch of column solves (uz_lane_count)
                 if (d->n_obstacles > 0) {      // a scene with colliders will need columns: the lanes are set up here, not inside its first touchdown
                     const int L = uz_lane_count(c, 8);
                     if (L >= 2 && uz_make_lanes(c, L)) return fail(ADMM_HIP_ERR_DEVICE, "create: streams / memory of the UzawaCG column lanes");
@@ -2650,9 +2540,9 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
                     c->pf_on = L >= 2 && c->pf_frames > 0.0 && uz_lane_fit(c) >= 2;
                     if (c->pf_on) HIP_TRY(c->pf_list.alloc((size_t)nv + 1));
                 }
-                { const char *pr = getenv("ADMM_HIP_UZ_PERSIST_ROWS"); c->uzp_rows = (pr && (atoi(pr) == 8 || atoi(pr) == 16)) ? atoi(pr) : 0; }   // 0: two launches per Schur iteration (A/B, tests)   // 0: full-height column pass in every Schur iteration (A/B)
-                { const char *e1 = getenv("ADMM_HIP_UZ_ONE_MAX"), *e2 = getenv("ADMM_HIP_UZ_COMPACT_MAX");      // test hooks
-                  if (e1) c->uzc_one_max = std::max(0, std::min(1024, atoi(e1))); if (e2) c->uzc_compact_max = std::max(0, atoi(e2)); }
+                { const int pr = env_int("ADMM_HIP_UZ_PERSIST_ROWS", 0); c->uzp_rows = (pr == 8 || pr == 16) ? pr : 0; }   // 0: two launches per Schur iteration (A/B, tests)   // 0: full-height column pass in every Schur iteration (A/B)
+                c->uzc_one_max = env_int("ADMM_HIP_UZ_ONE_MAX", c->uzc_one_max, 0, 1024);      // test hooks
+                c->uzc_compact_max = env_int("ADMM_HIP_UZ_COMPACT_MAX", c->uzc_compact_max, 0);
             }
         }
     }
@@ -2721,7 +2611,7 @@ static int set_state_impl(admm_hip_ctx *c, const double *x, const double *v) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->h_sig && c->h_sig[2]) {   // the steps before this call hit a barrier time-out; their result is overwritten anyway
         c->h_sig[2] = 0; c->oc_gave_up = true; c->oc_enabled = false; c->gsp_enabled = false; c->uzp_enabled = false; c->rc_iter = 0;
-        c->rc_hist = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0; for (int &v : c->rc_vb) v = 0;   // (pairs half-written by the aborted solve, and in the on-chip row order)
+        c->rc_hist = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0;   // (pairs half-written by the aborted solve, and in the on-chip row order)
         if (c->oc_bar.p) HIP_TRY(c->oc_bar.zero());
         if (c->gsp_abort.p) HIP_TRY(c->gsp_abort.zero());
         if (c->uzp_abort.p) HIP_TRY(c->uzp_abort.zero());
@@ -3057,17 +2947,6 @@ static int launch_global(admm_hip_ctx *c, const double *b, double *x) {
 }
 
 // true: launch_global(c, c->b.p, c->curr.p) will reach launch_pcg2 with the recycled basis as the FIRST thing that reads b
-static bool fuse_rhs_route(const admm_hip_ctx *c) {
-    if (!c->fuse_rhs_ok || c->world > 1 || c->comm || c->ar_fn) return false;
-    if (c->linsolver == 1) return false;
-    if (c->linsolver == 2 && (c->obst.n > 0 || !c->dyn.empty() || c->uz_freeze)) return false;      // (contact-free: UzawaCG::solve is the prefactored solve)
-    if (!(c->rc_enabled && c->oc_enabled && c->oc_plan)) return false;
-    const bool defl_now = c->defl_every <= 1;      // (experiments with ADMM_HIP_DEFL_EVERY keep the launch)
-    if (!defl_now) return false;
-    if (c->defl_start && !c->defl_start_hold && c->defl_k > 0 && c->rc_iter < 31 && ((c->defl_start >> c->rc_iter) & 1)) return false;   // the start step reads b first
-    return true;
-}
-
 constexpr int kStepAborted = -100;   // step_impl: a grid barrier of the on-chip PCG timed out (seen at the final synchronisation)
 static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_hip_stats *stats) {
     hipStream_t st = c->stream;
@@ -3081,8 +2960,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     }
     c->timing = timed; c->coll_ms_step = 0.0; c->lk_launch = 0;
     // opt-in (ADMM_HIP_KERNEL_CLOCK=1): the stamps themselves cost the local-step launch ~1.4 us (2 %)
-    static const bool kernel_clock = [] { const char *e = getenv("ADMM_HIP_KERNEL_CLOCK"); return e && e[0] == '1'; }();
-    if (timed && c->nt > 0 && kernel_clock) {
+    if (timed && c->nt > 0 && c->kernel_clock) {
         const int tsn = 4 * (blocks_for(c->nt) + 4), cap = 2 * admm_iters;
         if (c->lk_tsn != tsn || c->lk_cap < cap) {
             c->lk_ts.release(); c->lk_out.release();
@@ -3100,18 +2978,15 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     c->uz_iters_step = 0; c->uz_detected = false;
     struct InStep { admm_hip_ctx *c; ~InStep() { c->in_step = false; } } in_step_guard{c};
     c->in_step = true;
-    for (int d = 7; d >= 2; --d) c->rc_vb[d] = c->rc_vb[d - 1];
-    c->rc_vb[1] = c->rc_iter;
     c->rc_prev2_valid = c->rc_prev_valid; c->rc_prev_valid = c->rc_iter; c->rc_frame += 1; c->rc_iter = 0;   // this frame's pairs become "previous frame"
     // How many pairs a projection uses is decided ONCE per context, from the scene's own behaviour: four pairs cost ~4 us per solve
     // more than three (8.8 MB of reads, 20 block sums) and pay when solves need many iterations (Kuhn cube: 17.4 -> 13.9 per solve),
     // not when they need few (unstructured body at 1e-8: 4.25 vs 4.35).  Decided from measurement, then fixed: deterministic.
-    // ADMM_HIP_RC_PAIRS=n fixes it from the start.
     // Round 4 (tighter bench tolerance, 13 instead of 4 iterations per solve on the body): which count needs fewer iterations is
     // not monotone in the iteration count (body: 12.8 with three pairs, 13.9 with four; cube: the other way round), so BOTH are
     // measured -- frame 3 with four pairs, frame 4 with three -- and the fifth frame starts with the better one (three on a tie within
     // 2 %: they are cheaper).  Three stream synchronisations in the life of a context.
-    if (c->rc_adapt && !c->rc_decided && c->linsolver != 1 && c->oc_enabled && c->oc_plan && c->rc_frame >= 3 && c->rc_frame <= 5) {
+    if (!c->rc_decided && c->linsolver != 1 && c->oc_enabled && c->oc_plan && c->rc_frame >= 3 && c->rc_frame <= 5) {
         int h[3] = {0, 0, 0};
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpy(h, c->counters.p + 72, sizeof(h), hipMemcpyDeviceToHost));
@@ -3154,21 +3029,10 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         }
         if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * s + 1], st));
         // passive collisions are resolved inside the GS sweeps (linsolver 1, Solver.cpp:76)
-        // The contact-free on-chip solves of one GPU sum their own right-hand side (Oc2Args::g_inc): no gather launch.  Decided HERE, from
-        // exactly the conditions that lead launch_global to launch_pcg2 with the recycled basis; every other route gets the launch.
-        const bool fuse = fuse_rhs_route(c);
-        if (fuse) c->fuse_rhs = true;
-        else if (int rr = launch_rhs(c))             // Solver.cpp:98
+        if (int rr = launch_rhs(c))             // Solver.cpp:98
             return fail(rr == -2 ? ADMM_HIP_ERR_STATE : ADMM_HIP_ERR_COMM, rr == -2 ? "step: world_size > 1 but neither admm_hip_comm_init nor admm_hip_set_rhs_allreduce was called" : "all-reduce of the right-hand side failed");
         if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * s + 2], st));
-        // experiments (ADMM_HIP_TOL_LAST=tol, ADMM_HIP_TOL_LAST_N=k): the last k solves of a step at another tolerance
-        const double keep_tol = c->pcg_tol;
-        if (c->tol_last > 0.0 && s >= admm_iters - c->tol_last_n) c->pcg_tol = c->tol_last;
-        if ((size_t)s < c->tol_sched.size()) c->pcg_tol = keep_tol * c->tol_sched[s];
-        c->defl_now = c->defl_every <= 1 || ((s + 1) % c->defl_every) == 0;
         const int grc = launch_global(c, c->b.p, c->curr.p);   // Solver.cpp:99
-        c->pcg_tol = keep_tol;
-        if (c->fuse_rhs) { c->fuse_rhs = false; return fail(ADMM_HIP_ERR_STATE, "step: the solve that was to sum its right-hand side did not run (internal)"); }
         if (grc == -2) return kStepAborted;       // a grid barrier timed out in a column solve of UzawaCG: same recovery as any aborted on-chip solve
         if (grc) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
     }
@@ -3256,7 +3120,7 @@ static int recover_from_abort(admm_hip_ctx *c, admm_hip_stats *stats_of_last) {
         return fail(ADMM_HIP_ERR_DEVICE, "PCG: a grid barrier of the on-chip solve timed out (is another persistent kernel sharing the GPU?)");
     if (!c->oc_gave_up) fprintf(stderr, "[admm_hip] on-chip PCG: a grid barrier timed out (blocks not co-resident?) -- falling back to the launch-per-iteration PCG and replaying %d step(s)\n", (int)c->pending.size());
     c->oc_gave_up = true; c->oc_enabled = false; c->gsp_enabled = false; c->uzp_enabled = false;
-    c->rc_hist = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0; for (int &v : c->rc_vb) v = 0;   // the history slots may hold pairs half-written by the aborted solve, in the on-chip kernel's row order
+    c->rc_hist = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0;   // the history slots may hold pairs half-written by the aborted solve, in the on-chip kernel's row order
     c->defl_fused = false;      // (the end projection on the soft modes goes on as separate launches)
     if (c->gsp_abort.p) HIP_TRY(c->gsp_abort.zero());
     if (c->uzp_abort.p) HIP_TRY(c->uzp_abort.zero());
@@ -3477,8 +3341,7 @@ int admm_hip_set_soft_modes(admm_hip_ctx *c, int32_t k, const double *Z) {
     // The fused epilogue of k_pcg2 keeps the modes in SINGLE precision (half the bytes of the step's two passes over them).  The step stays an
     // exact Galerkin step because everything below -- K Z, G = Z^T K Z, the copy the separate kernels use -- is formed from the ROUNDED vectors.
     std::vector<double> Zr;
-    const char *fe0 = getenv("ADMM_HIP_DEFL_FUSED");
-    const bool want_fused = !(fe0 && fe0[0] == '0') && c->oc_enabled && c->oc_plan && k <= kOc2DeflMax && !c->oc_orig_h.empty();
+    const bool want_fused = env_flag("ADMM_HIP_DEFL_FUSED", true) && c->oc_enabled && c->oc_plan && k <= kOc2DeflMax && !c->oc_orig_h.empty();
     if (want_fused) { Zr.assign(Z, Z + (size_t)k * nv); for (double &z : Zr) z = (double)(float)z; Z = Zr.data(); }
     // exact pairs: K Z on the host, G = Z^T K Z, its inverse
     std::vector<double> KZ((size_t)k * nv), G((size_t)k * k, 0.0);
@@ -3516,9 +3379,7 @@ int admm_hip_set_soft_modes(admm_hip_ctx *c, int32_t k, const double *Z) {
     HIP_TRY(c->defl_Ginv.upload(G));
     HIP_TRY(c->defl_part.alloc((size_t)3 * k * c->NB)); HIP_TRY(c->defl_y.alloc((size_t)3 * k));
     c->defl_fused = false;
-    { const char *fe = getenv("ADMM_HIP_DEFL_FUSED");      // (=0: the separate k_defl_* launches, the A/B and the checker of the fused epilogue)
-      if (want_fused) {
-        (void)fe;
+    if (want_fused) {      // (ADMM_HIP_DEFL_FUSED=0: the separate k_defl_* launches, the A/B and the checker of the fused epilogue)
         std::vector<float> Zi((size_t)k * c->oc_rows, 0.0f);      // [mode][internal row] (pcg_onchip2.hpp)
         for (int q = 0; q < k; ++q)
             for (int r = 0; r < c->oc_rows; ++r) { const int v = c->oc_orig_h[r]; if (v >= 0) Zi[(size_t)q * c->oc_rows + r] = (float)Z[(size_t)q * nv + v]; }
@@ -3526,9 +3387,8 @@ int admm_hip_set_soft_modes(admm_hip_ctx *c, int32_t k, const double *Z) {
         HIP_TRY(c->defl_Zint.upload(Zi));
         HIP_TRY(c->defl_rec.alloc((size_t)2 * 3 * kOc2DeflMax * c->oc_G)); HIP_TRY(c->defl_rec.zero());
         c->defl_fused = true;
-      } }
+    }
     c->defl_k = k;
-    { const char *e = getenv("ADMM_HIP_DEFL_EVERY"); c->defl_every = e ? std::max(1, atoi(e)) : 1; }
     return ADMM_HIP_OK;
 }
 
@@ -3706,10 +3566,8 @@ int admm_hip_probe_sync(admm_hip_ctx *c, int32_t n, double *us_all_to_all, doubl
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     double out[2] = {0.0, 0.0};
-    const char *pm = getenv("ADMM_HIP_PROBE_A2A_MODE");      // (experiments: another record layout in the all-to-all probe, pcg_onchip2.hpp)
-    const int a2a_mode = pm ? atoi(pm) : 0;
     for (int slot = 0; slot < 2; ++slot) {
-        const int mode = slot == 0 ? a2a_mode : 1;
+        const int mode = slot;
         Oc2Args a{};
         a.n_rows = c->oc_rows; a.halo_ptr = c->oc_haloptr.p; a.halo_src = c->oc_halosrc.p; a.vec_len = c->oc_veclen;
         a.ubuf = c->oc_ubuf.p; a.part = c->oc_part.p; a.bar = c->oc_bar.p; a.nbr = c->oc_nbr.p; a.flags = c->oc_flags.p;
@@ -3802,7 +3660,7 @@ int admm_hip_comm_init(admm_hip_ctx *c, const char *id128, int rank, int world_s
     // a world of one needs no communicator; ADMM_HIP_FORCE_COMM=1 builds (and uses) one anyway so that the RCCL
     // binding, the in-place all-reduce on the context's stream and its ordering against the persistent PCG kernel
     // can be exercised on a single GPU (tests/test_multi_gpu.py)
-    if (c->world <= 1 && !(getenv("ADMM_HIP_FORCE_COMM") && getenv("ADMM_HIP_FORCE_COMM")[0] == '1')) return ADMM_HIP_OK;
+    if (c->world <= 1 && !env_flag("ADMM_HIP_FORCE_COMM", false)) return ADMM_HIP_OK;
     if (!g_rccl.load()) return fail(ADMM_HIP_ERR_COMM, "cannot load librccl");
     HIP_TRY(hipSetDevice(c->device));
     ncclUniqueId id;

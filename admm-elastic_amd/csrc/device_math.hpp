@@ -127,13 +127,11 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
         float a00 = (float)(d0 * inv), a01 = (float)(c01 * inv), a02 = (float)(c02 * inv);
         float a11 = (float)(d1 * inv), a12 = (float)(c12 * inv), a22 = (float)(d2 * inv);
         float w0[3] = {1.f, 0.f, 0.f}, w1[3] = {0.f, 1.f, 0.f}, w2[3] = {0.f, 0.f, 1.f};
-#ifndef ADMM_F32_OFF2
-#define ADMM_F32_OFF2 2e-13f
-#endif
+        constexpr float kF32Off2 = 2e-13f;      // off-diagonal mass below which the three sweeps suffice
 #define ADMM_F32_SWEEP() { ADMM_COUNT(0); jacobi_rotate_f32(a00, a11, a01, a02, a12, w0, w1); jacobi_rotate_f32(a00, a22, a02, a01, a12, w0, w2); \
                            jacobi_rotate_f32(a11, a22, a12, a01, a02, w1, w2); }
         ADMM_F32_SWEEP(); ADMM_F32_SWEEP(); ADMM_F32_SWEEP();
-        if (__any(fmaf(a01, a01, fmaf(a02, a02, a12 * a12)) > ADMM_F32_OFF2)) ADMM_F32_SWEEP();
+        if (__any(fmaf(a01, a01, fmaf(a02, a02, a12 * a12)) > kF32Off2)) ADMM_F32_SWEEP();
 #undef ADMM_F32_SWEEP
         // (2) orthonormalise in FP64 (Gram-Schmidt; the columns are unit vectors to 1e-7: 1/sqrt(1 + e) by its series)
 #pragma unroll
@@ -159,11 +157,9 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
         b1[r] = fma(F[r], v1[0], fma(F[3 + r], v1[1], F[6 + r] * v1[2]));
         b2[r] = fma(F[r], v2[0], fma(F[3 + r], v2[1], F[6 + r] * v2[2]));
     }
-    // (3) FP64 one-sided sweeps until every pair of columns is orthogonal: cos^2 <= ADMM_SVD_TOL2.  Then F = U diag(S) V^T to
+    // (3) FP64 one-sided sweeps until every pair of columns is orthogonal: cos^2 <= kSvdTol2.  Then F = U diag(S) V^T to
     // ~3e-14 |F| whatever the order of the columns in the Gram-Schmidt below.
-#ifndef ADMM_SVD_TOL2
-#define ADMM_SVD_TOL2 1e-27
-#endif
+    constexpr double kSvdTol2 = 1e-27;
     double n0, n1, n2;
 #pragma unroll 1
     for (int sweep = 0; sweep < 12; ++sweep) {
@@ -174,7 +170,7 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
         n0 = dot3(b0, b0); n1 = dot3(b1, b1); n2 = dot3(b2, b2);
         const double g01 = dot3(b0, b1), g02 = dot3(b0, b2), g12 = dot3(b1, b2);
         ADMM_RECORD(8 + sweep, fmax(g01 * g01 / fmax(n0 * n1, 1e-300), fmax(g02 * g02 / fmax(n0 * n2, 1e-300), g12 * g12 / fmax(n1 * n2, 1e-300))));
-        const bool open = g01 * g01 > ADMM_SVD_TOL2 * n0 * n1 || g02 * g02 > ADMM_SVD_TOL2 * n0 * n2 || g12 * g12 > ADMM_SVD_TOL2 * n1 * n2;
+        const bool open = g01 * g01 > kSvdTol2 * n0 * n1 || g02 * g02 > kSvdTol2 * n0 * n2 || g12 * g12 > kSvdTol2 * n1 * n2;
         if (!__any(open)) break;
     }
     // (4) U by Gram-Schmidt on b0, b1; u2 = u0 x u1.  A column that is round-off (flat or collapsed element) must not be one

@@ -83,10 +83,7 @@ __device__ __forceinline__ void gsp_store(__amdgpu_buffer_rsrc_t rs, int byte_of
     __builtin_amdgcn_raw_buffer_store_b128(g, rs, byte_off, 0, 16 /* sc1: write-through */);
 }
 
-#ifndef ADMM_GSP_PACK2
-#define ADMM_GSP_PACK2 1
-#endif
-// ADMM_GSP_PACK2: the three values of a boundary row in TWO granules instead of three -- four 8-byte units (each single-copy atomic) of 48 payload
+// The three values of a boundary row in TWO granules -- four 8-byte units (each single-copy atomic) of 48 payload
 // bits + the low 16 bits of the stamp: x | y | z as one 192-bit string cut into four.  16 bits tell the phases of one solve apart and sixteen
 // consecutive solves (stamp = solve x 4096 + 1 + phase, phase < 4048); every slot is rewritten in every solve.
 __device__ __forceinline__ void gsp_pack3(const double *v, unsigned stamp, v4u &ga, v4u &gb) {
@@ -108,43 +105,13 @@ __device__ __forceinline__ void gsp_unpack3(v4u ga, v4u gb, double *v) {
     z.u[0] = (gb.y & 0xffffu) | (gb.z << 16);   z.u[1] = (gb.z >> 16) | (gb.w << 16);
     v[0] = x.d; v[1] = y.d; v[2] = z.d;
 }
-constexpr int kGspGran = ADMM_GSP_PACK2 ? 2 : 3;      // granules per (outbox node, sweep parity)
-#ifndef ADMM_GSP_SOA
-#define ADMM_GSP_SOA 1
-#endif
-// Byte offset of granule k of outbox node `node`, sweep parity `par`.  ADMM_GSP_SOA: [parity][granule][node] -- the rows a wave publishes have
+constexpr int kGspGran = 2;      // granules per (outbox node, sweep parity)
+// Byte offset of granule k of outbox node `node`, sweep parity `par`: [parity][granule][node] -- the rows a wave publishes have
 // consecutive outbox nodes (the plan numbers a block's boundary rows colour by colour), so ONE store instruction covers whole 32-byte sectors and
-// whole lines, and the consumer's lanes (halo lists sorted by source block and row) read them the same way; 0: [node][parity][granule], a wave's
-// store instruction touches one 16-byte half sector per row, 96 bytes apart (half-written sectors drain slowly: pcg_onchip2.hpp, publish()).
+// whole lines, and the consumer's lanes (halo lists sorted by source block and row) read them the same way (half-written sectors drain
+// slowly: pcg_onchip2.hpp, publish()).
 __device__ __forceinline__ int gsp_box_off(int node, int par, int k, int n_nodes) {
-#if ADMM_GSP_SOA
     return ((par * kGspGran + k) * n_nodes + node) * 16;
-#else
-    (void)n_nodes;
-    return ((node * 2 + par) * kGspGran + k) * 16;
-#endif
-}
-
-#ifndef ADMM_GSP_PIPE
-#define ADMM_GSP_PIPE 0
-#endif
-#ifndef ADMM_GSP_PIPE_D
-#define ADMM_GSP_PIPE_D 3
-#endif
-#ifndef ADMM_GSP_PIPE_D0
-#define ADMM_GSP_PIPE_D0 0
-#endif
-constexpr int kGspPipeD = ADMM_GSP_PIPE_D, kGspPipeD0 = ADMM_GSP_PIPE_D0, kGspPipeChain = 10;      // (s_sleep periods of 64 clocks; checks in the chain)
-struct GspSet2 { v4u g[2]; };
-__device__ __forceinline__ void gsp_poll2(__amdgpu_buffer_rsrc_t rs, int off, int off1, GspSet2 &p) { p.g[0] = gsp_load(rs, off); p.g[1] = gsp_load(rs, off1); }
-template <int K> __device__ __forceinline__ bool gsp_chain2(__amdgpu_buffer_rsrc_t rs, int off, int off1, unsigned want, const GspSet2 &pa, const GspSet2 &pb, GspSet2 &out) {
-    if (gsp_ok3(pa.g[0], pa.g[1], want)) { out = pa; return true; }
-    if constexpr (K == 0) { out = pa; return false; }
-    else {
-        GspSet2 pn;
-        gsp_poll2(rs, off, off1, pn);
-        return gsp_chain2<K - 1>(rs, off, off1, want, pb, pn, out);
-    }
 }
 
 struct GspObstOne {      // Obstacles with exactly one entry (k_gs_persist: in SGPRs; kernels.hpp: ObstSingle)
@@ -316,47 +283,17 @@ __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
     auto fetch_halo = [&](int cp, int par, unsigned want, bool keep_old) {
         const int h0 = ih[21 + cp], h1 = ih[21 + cp + 1];
         for (int hh = h0 + t; hh < h1; hh += kGspT) {
-            const int off = gsp_box_off(hl[hh], par, 0, a.n_box), off1 = gsp_box_off(hl[hh], par, 1, a.n_box), off2 = gsp_box_off(hl[hh], par, kGspGran - 1, a.n_box);
-            v4u g0, g1, g2;
+            const int off = gsp_box_off(hl[hh], par, 0, a.n_box), off1 = gsp_box_off(hl[hh], par, 1, a.n_box);
+            v4u g0, g1;
             unsigned spins = 0;
-#if ADMM_GSP_PACK2 && ADMM_GSP_PIPE >= 2
-            // (experiment, OFF: ADMM_GSP_PIPE polls in flight, the oldest checked and re-issued -- a CHAIN of checks, not a loop: register sets carried
-            // around a back edge are copied there, and the copy waits for every poll in flight.  profiles/r06_gs_granules_ab.txt)
-            bool have = false;
-            {
-                GspSet2 p0, p1, out;
-                if (kGspPipeD0 > 0) __builtin_amdgcn_s_sleep(kGspPipeD0);
-                gsp_poll2(rbox, off, off1, p0);
-                __builtin_amdgcn_s_sleep(kGspPipeD);
-                gsp_poll2(rbox, off, off1, p1);
-                have = gsp_chain2<kGspPipeChain>(rbox, off, off1, want, p0, p1, out);
-                g0 = out.g[0]; g1 = out.g[1];
-            }
-            while (!have) {
-                g0 = gsp_load(rbox, off); g1 = gsp_load(rbox, off1);
-                if (gsp_ok3(g0, g1, want)) break;
-                if (poll_failed(spins)) break;
-            }
-#elif ADMM_GSP_PACK2
             while (true) {
                 g0 = gsp_load(rbox, off); g1 = gsp_load(rbox, off1);
                 if (gsp_ok3(g0, g1, want)) break;
                 if (poll_failed(spins)) break;
             }
-#else
-            while (true) {
-                g0 = gsp_load(rbox, off); g1 = gsp_load(rbox, off1); g2 = gsp_load(rbox, off2);
-                if (gsp_ok(g0, want) && gsp_ok(g1, want) && gsp_ok(g2, want)) break;
-                if (poll_failed(spins)) break;
-            }
-#endif
             const int j = 3 * (n_own + hh);
             if (keep_old) { xo[j] = xl[j]; xo[j + 1] = xl[j + 1]; xo[j + 2] = xl[j + 2]; }
-#if ADMM_GSP_PACK2
             { double v3[3]; gsp_unpack3(g0, g1, v3); xl[j] = v3[0]; xl[j + 1] = v3[1]; xl[j + 2] = v3[2]; }
-#else
-            xl[j] = gsp_val(g0); xl[j + 1] = gsp_val(g1); xl[j + 2] = gsp_val(g2);
-#endif
         }
     };
     // cur = sum_k Ahat(row, k) x_k of row i of colour c (entries in CSR order: the sums of k_gs_color).  BOTH: also old = the same sum
@@ -446,11 +383,7 @@ __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
                 const int v = a.orig[row_base + li];
                 gs_pin_value(2, a.pin_xyz + 3 * (size_t)v, a.pin_nrm + 3 * (size_t)v, bi, LUx, iaii, nx);
             } else if (pflag) { // :111-117
-#ifdef ADMM_GSP_OB_GLOBAL
-                if (true) {
-#else
                 if (first_sweep) {
-#endif
                     const int v = a.orig[row_base + li];
 #pragma unroll
                     for (int q = 0; q < 3; ++q) nx[q] = a.pin_xyz[3 * (size_t)v + q];
@@ -459,24 +392,16 @@ __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
                     for (int q = 0; q < 3; ++q) nx[q] = cx[q];
                 }
             }
-#ifdef ADMM_GSP_OB_GLOBAL      // (same-box A/B only: the obstacles through the argument pointer, as before round 4's second session)
-            else if (gs_relax(*a.ob, a.omega, bi, LUx, iaii, cx, nx)) __hip_atomic_fetch_add(&ctl[10], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
             else if (!has_ob) {      // no passive obstacle in the scene (uniform): :210 alone
 #pragma unroll
                 for (int q = 0; q < 3; ++q) nx[q] = fma(a.omega, (bi[q] - LUx[q]) * iaii[q], (1.0 - a.omega) * cx[q]);
             }
             else if (one_ob) { if (gs_relax(ob1, a.omega, bi, LUx, iaii, cx, nx)) __hip_atomic_fetch_add(&ctl[10], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
             else if (gs_relax(*obl, a.omega, bi, LUx, iaii, cx, nx)) __hip_atomic_fetch_add(&ctl[10], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (LDS add: rows projected, counted below)
-#endif
             GSP_FLAP(2);
             if (o >= 0) {      // the neighbours wait for these: out first, the block's own copies after
                 const int off = gsp_box_off(ob_base + o, par, 0, a.n_box), off1 = gsp_box_off(ob_base + o, par, 1, a.n_box);
-#if ADMM_GSP_PACK2
                 { v4u ga, gb; gsp_pack3(nx, stamp, ga, gb); gsp_store(rbox, off, ga); gsp_store(rbox, off1, gb); }
-#else
-                gsp_store(rbox, off, gsp_pack(nx[0], stamp)); gsp_store(rbox, off1, gsp_pack(nx[1], stamp)); gsp_store(rbox, gsp_box_off(ob_base + o, par, 2, a.n_box), gsp_pack(nx[2], stamp));
-#endif
             }
             if (keep_old) { xo[3 * li] = cx[0]; xo[3 * li + 1] = cx[1]; xo[3 * li + 2] = cx[2]; }
             xl[3 * li] = nx[0]; xl[3 * li + 1] = nx[1]; xl[3 * li + 2] = nx[2];

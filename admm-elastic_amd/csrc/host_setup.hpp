@@ -1,10 +1,24 @@
 // host_setup.hpp -- host-side set-up structures shared by the C ABI (no GPU code here).
 #pragma once
+#include <algorithm>
+#include <climits>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 #include <string>
 
 namespace admm_host {
+
+// Environment switches (INTEGRATION.md lists them), read once per context.  env_flag: unset gives dflt; a default-on switch is off
+// when its value starts with '0', a default-off switch is on when it starts with '1'.  env_int: unset gives dflt, a value is clamped to [lo, hi].
+inline bool env_flag(const char *name, bool dflt) {
+    const char *e = std::getenv(name);
+    return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
+}
+inline int env_int(const char *name, int dflt, int lo = INT_MIN, int hi = INT_MAX) {
+    const char *e = std::getenv(name);
+    return e ? std::max(lo, std::min(hi, std::atoi(e))) : dflt;
+}
 
 struct Csr {
     int32_t n = 0;
@@ -62,7 +76,7 @@ struct TetChunks {
 };
 TetChunks tet_chunks(int32_t n_tets, const int32_t *tet_idx, const int32_t kind_begin[6]);
 // vertex -> records incidence lists (row r gathers for vertex row_vertex[r]); widths are multiples of 4, padding = pad_code
-Sell record_incidence(int32_t n_verts, int32_t n_rec, const int32_t *rec_vertex, int32_t pad_code, const int32_t *row_vertex = nullptr, int32_t n_rows = -1);
+Sell record_incidence(int32_t n_verts, int32_t n_rec, const int32_t *rec_vertex, int32_t pad_code, const int32_t *row_vertex = nullptr);
 std::vector<int32_t> incidence_row_order(int32_t n_verts, int32_t n_tets, const int32_t *tet_idx, int32_t n_tris, const int32_t *tri_idx, int32_t window);
 
 int greedy_coloring(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t *color);

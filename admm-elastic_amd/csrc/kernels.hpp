@@ -243,20 +243,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t soa_rsrc(const void *p) {
 }
 // cache policy of the per-element STREAMS (read or written exactly once per launch) -- gfx950 aux bits: 1 = sc0, 2 = nt
 // (non-temporal: first in line for eviction), 16 = sc1.  The gathered vertex positions keep the default policy.
-#ifndef ADMM_STREAM_LD_AUX
-#define ADMM_STREAM_LD_AUX 0
-#endif
-#ifndef ADMM_STREAM_ST_AUX
-#define ADMM_STREAM_ST_AUX 0
-#endif
+constexpr int kStreamLdAux = 0, kStreamStAux = 0;
 __device__ __forceinline__ double buf_ld_stream(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     union { double d; bv2u v; } t;
-    t.v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, ADMM_STREAM_LD_AUX);
+    t.v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, kStreamLdAux);
     return t.d;
 }
 __device__ __forceinline__ void buf_st_stream(__amdgpu_buffer_rsrc_t rs, int voff, int soff, double x) {
     union { double d; bv2u v; } t; t.d = x;
-    __builtin_amdgcn_raw_buffer_store_b64(t.v, rs, voff, soff, ADMM_STREAM_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(t.v, rs, voff, soff, kStreamStAux);
 }
 __device__ __forceinline__ double buf_ld(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     union { double d; bv2u v; } t;
@@ -379,7 +374,7 @@ __device__ __forceinline__ void tet_compute_store(const TetArgs &a, int t, bool 
     const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk + 1]) - r0;
     const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
     union { bv4u v; unsigned short h[8]; } e;
-    e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + (int)threadIdx.x) * 16, 0, ADMM_STREAM_LD_AUX);
+    e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + (int)threadIdx.x) * 16, 0, kStreamLdAux);
     // dt^2 w^2 of this tet: needed after the prox, fetched across it like the list (two registers less across the SVD: the fused
     // kernel sits exactly on its 128)
     const double s = buf_ld_stream(soa_rsrc(a.sc), valid ? t8 : 0, 0);
@@ -397,10 +392,7 @@ __device__ __forceinline__ void tet_compute_store(const TetArgs &a, int t, bool 
         // minimisation AND the general Newton loop outlined (device_math.hpp: newton_stretch_general) -- inlined, that rare
         // path dictated 166 VGPRs = 3 waves/SIMD; forcing 128 then spilled on the common path and was slower (measured in both
         // rounds).  Same box, 1 M tets: 3 waves 68.4 us, 4 waves with spills 71.8 us, 4 waves + V parked + outlined loop 65.4 us.
-#ifndef ADMM_PARK_V_NH
-#define ADMM_PARK_V_NH 1
-#endif
-        constexpr bool kParkV = (KIND == 2) || (KIND == 3) || (KIND == 1 && ADMM_PARK_V_NH != 0);
+        constexpr bool kParkV = (KIND == 1) || (KIND == 2) || (KIND == 3);
         if (kParkV) {
 #pragma unroll
             for (int c = 0; c < 9; ++c) sV[c * kChunkLdK] = V[c];
@@ -459,7 +451,7 @@ __device__ __forceinline__ void tet_compute_store(const TetArgs &a, int t, bool 
         const __amdgpu_buffer_rsrc_t rr = soa_rsrc(a.rec);
         const LdsDk *base = sL;
         for (int g = g0; g < g1; ++g) {
-            if (g > g0) e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g * 256 + (int)threadIdx.x) * 16, 0, ADMM_STREAM_LD_AUX);
+            if (g > g0) e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g * 256 + (int)threadIdx.x) * 16, 0, kStreamLdAux);
             double s0 = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
             for (int i = 0; i < kChunkFanK; ++i) {
@@ -470,8 +462,8 @@ __device__ __forceinline__ void tet_compute_store(const TetArgs &a, int t, bool 
             if (j < nrec) {
                 union { double d[2]; bv4u v; } p0; p0.d[0] = s0; p0.d[1] = s1;
                 union { double d; bv2u v; } p1; p1.d = s2;
-                __builtin_amdgcn_raw_buffer_store_b128(p0.v, rr, (r0 + j) * 32, 0, ADMM_STREAM_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b64(p1.v, rr, (r0 + j) * 32 + 16, 0, ADMM_STREAM_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(p0.v, rr, (r0 + j) * 32, 0, kStreamStAux);
+                __builtin_amdgcn_raw_buffer_store_b64(p1.v, rr, (r0 + j) * 32 + 16, 0, kStreamStAux);
             }
         }
     }
@@ -503,12 +495,10 @@ __device__ __forceinline__ void local_tet_body(const TetArgs &a, int t, int t_en
 }
 
 // one constitutive model per launch (used when a scene has a single model, and by the parity entry point)
+constexpr int kNhWaves = 4;      // waves per SIMD of the Neo-Hookean launches
 template <int KIND, bool WRITE_Z, bool REST>
-#ifndef ADMM_NH_WAVES
-#define ADMM_NH_WAVES 4
-#endif
-__global__ __launch_bounds__(256, (KIND == 1 ? ADMM_NH_WAVES : KIND == 4 ? 2 : 4)) void k_local_tets(int t0, int t1, TetArgs a) {
-    __shared__ double sLm[((KIND == 2 || KIND == 3 || (KIND == 1 && ADMM_PARK_V_NH != 0)) ? 18 : 12) * kChunkLdK];     // rows 0..8: Binv; 9..: V (parked); 0..11: corner forces
+__global__ __launch_bounds__(256, (KIND == 1 ? kNhWaves : KIND == 4 ? 2 : 4)) void k_local_tets(int t0, int t1, TetArgs a) {
+    __shared__ double sLm[((KIND == 1 || KIND == 2 || KIND == 3) ? 18 : 12) * kChunkLdK];     // rows 0..8: Binv; 9..: V (parked); 0..11: corner forces
     LdsDk *sL = (LdsDk *)sLm;
     const int blk = xcd_block();
     ts_enter(a);
@@ -520,7 +510,7 @@ __global__ __launch_bounds__(256, (KIND == 1 ? ADMM_NH_WAVES : KIND == 4 ? 2 : 4
 // Avoids the ramp-down / ramp-up between per-model launches of a mixed scene.  (Chunks are numbered model by model in this
 // order, so the block index is the chunk index.)
 template <bool WRITE_Z, bool REST>
-__global__ __launch_bounds__(256, ADMM_NH_WAVES) void k_local_tets_fused(int b0, int b1, int b2, int b3, int nb0, int nb1, TetArgs a) {
+__global__ __launch_bounds__(256, kNhWaves) void k_local_tets_fused(int b0, int b1, int b2, int b3, int nb0, int nb1, TetArgs a) {
     __shared__ double sLm[18 * kChunkLdK];
     LdsDk *sL = (LdsDk *)sLm;
     const int blk = xcd_block();

@@ -283,7 +283,6 @@ OcPlan build_oc_plan(const Csr &A, const double *mass3, int G, int spb, int lds_
     // whose bank pair is least used in this column so far; rows without entries left pad with a zero times an own entry of
     // the least used bank pair.
     int64_t conflict_sorted = 0, conflict_placed = 0, columns_total = 0;
-    const bool place_by_bank = [] { const char *e = getenv("ADMM_HIP_OC_BANKS"); return !(e && e[0] == '0'); }();
     for (int32_t s = 0; s < S.n_slices; ++s) {
         const int b = s / spb;
         const std::vector<int32_t> &h = halo[b];
@@ -322,14 +321,6 @@ OcPlan build_oc_plan(const Csr &A, const double *mass3, int G, int spb, int lds_
                     conflict_sorted += mx; ++columns_total;
                 }
             }
-            if (!place_by_bank) {
-                for (int l = l0; l < l0 + 32; ++l)
-                    for (int32_t k = 0; k < w; ++k) {
-                        if (k < (int32_t)ent[l].size()) put(l, k, (uint16_t)ent[l][k].first, ent[l][k].second);
-                        else put(l, k, (uint16_t)(64 * s + l - b * T), 0.0);
-                    }
-                continue;
-            }
             std::vector<char> used[32];
             for (int l = l0; l < l0 + 32; ++l) used[l - l0].assign(ent[l].size(), 0);
             int rem[32];
@@ -364,7 +355,7 @@ OcPlan build_oc_plan(const Csr &A, const double *mass3, int G, int spb, int lds_
         }
     }
     P.stat_bank_sorted = columns_total ? (double)conflict_sorted / (double)columns_total : 0.0;
-    P.stat_bank_placed = columns_total ? (double)(place_by_bank ? conflict_placed : conflict_sorted) / (double)columns_total : 0.0;
+    P.stat_bank_placed = columns_total ? (double)conflict_placed / (double)columns_total : 0.0;
     // ---- LDS: the block's local vector (3 axes x (T + halo)) and the slab (10 bytes per entry) ----
     P.vec_len = T + P.nh_cap;
     const int lds_cols = std::max(0, (lds_bytes - 3 * 8 * P.vec_len) / (64 * 10)) / 4 * 4;
@@ -431,7 +422,7 @@ OcPlan build_oc_plan(const Csr &A, const double *mass3, int G, int spb, int lds_
     // Kuhn cube 16.6 -> 12.6 iterations per solve.  A direction in which a block has no extent (flat cloth, tiny blocks) gets a
     // zero weight column: its coarse unknown is empty (unit diagonal below), as an empty aggregate is.
     P.cwt.assign(4 * (size_t)P.n_rows, 0.0f);
-    P.affine = xyz != nullptr && !(getenv("ADMM_HIP_OC_AFFINE") && getenv("ADMM_HIP_OC_AFFINE")[0] == '0');
+    P.affine = xyz != nullptr && env_flag("ADMM_HIP_OC_AFFINE", true);
     static_assert(kOcSub == 4, "four coarse functions per block");
     for (int b = 0; b < G; ++b) {
         const std::vector<int32_t> &mem = blocks[b];

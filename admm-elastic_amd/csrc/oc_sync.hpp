@@ -26,10 +26,7 @@ typedef __attribute__((address_space(3))) double LdsD;
 constexpr int kOcSubK = 4;                // aggregates per block of the two-level preconditioner (= admm_host::kOcSub, pcg_onchip2.hpp)
 constexpr unsigned kOcSpinLimit = 4000000u;
 constexpr double kOcPipeFloor = 1e-18;    // squared relative residual below which the pipelined recurrences are not trusted
-#ifndef ADMM_OC_TRIG
-#define ADMM_OC_TRIG 0.9
-#endif
-constexpr double kOcTrig = ADMM_OC_TRIG;  // the recurrence must report gamma <= kOcTrig tol^2 b.M^-1 b before the true residual is checked
+constexpr double kOcTrig = 0.9;           // the recurrence must report gamma <= kOcTrig tol^2 b.M^-1 b before the true residual is checked
 constexpr int kOcStagnation = 50;         // pipelined iterations without a new residual minimum before switching, once the
                                           // residual is within 100x of kOcPipeFloor (rounding-driven stagnation); above that
                                           // level plateaus of the residual norm are ordinary CG behaviour (measured: 13 of 40

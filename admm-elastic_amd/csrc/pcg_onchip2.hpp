@@ -56,8 +56,6 @@ struct Oc2Args {
     const unsigned short *col16;     // its local column at ptr[s] + ((k / 4) 64 + lane) 4 + k % 4
     const int *lds_off, *wl_s;       // per slice: slab offset (columns) and columns held in LDS
     double sm_ab, sm_b;              // block-local smoother S v = D^-1 (sm_ab v - sm_b offdiag(A_bb) D^-1 v); sm_b = 0: S = D^-1
-    double sm_c0, sm_k1, sm_k2;      // sm_k2 != 0: three Chebyshev steps instead of two (two products): with y = D^-1 v, N = D^-1 offdiag(A_bb):
-                                     // v1 = sm_k1 y + sm_k2 N y,  S v = sm_c0 y + v1 + N v1
     int bcols;                       // slab columns per block
     const int *orig;                 // [n_rows] vertex | aggregate << 28 (-1 = dummy row)
     const int *halo_ptr, *halo_src;  // [G + 1]; internal rows of the halo entries (sorted per block)
@@ -82,34 +80,14 @@ struct Oc2Args {
                          // launch a no-op -- lets the host enqueue outer iterations ahead without synchronising
     // END PROJECTION ON SOFT MODES (admm_hip_set_soft_modes; kernels.hpp: k_defl_* is the same step as separate launches): after a converged
     // solve x += Z (Z^T K Z)^-1 Z^T r on defl_k <= kOc2DeflMax smooth global vectors Z (internal row order, [defl_k][n_rows]).
-    int defl_dbg;      // (experiments: bit 0 no mode loads in the dots, bit 1 no own-row loads, bit 2 no G^-1 staging)
     int defl_k; const float *defl_Z; const double *defl_Ginv; double *defl_rec;      // defl_Z: SINGLE precision (the step stays an exact Galerkin step: G is formed
                                                                                      // from the rounded vectors); defl_rec: [2][3 kOc2DeflMax][G] block sums, by solve parity
-    // THE SOLVE SUMS ITS OWN RIGHT-HAND SIDE (g_inc != nullptr; the ADMM loop's contact-free solves on one GPU): what k_gather_rhs does as a
-    // launch of its own (kernels.hpp; src/Solver.cpp:98) -- b = M x_bar + the records of the local step + the pin terms -- is done by the
-    // thread that owns the row, in the shadow of the LDS fill: the record lists come in the plan's internal row order (one SELL slice per
-    // wave, like the matrix), b is also written to g_b (= b: later readers, the recovery path).  Same lists, same order: the same bits.
-    const int *g_ptr, *g_w, *g_inc; int g_pad; const double *g_rec, *g_Mxbar; double *g_b;      // g_pad: the all-zero record the lists are padded with
-    const int *g_vert_pin; const double *g_pin_xyz; const int *g_pin_active; double *g_pin_u, *g_pin_z; double g_pin_sc; const double *g_pin_nrm;
 };
 constexpr int kOc2DeflMax = 32;
 
-#ifndef ADMM_OC2_ATTR
-#define ADMM_OC2_ATTR
-#endif
-#ifndef ADMM_OC2_LB
-#define ADMM_OC2_LB(t) (t)          // (ISA experiments: another register budget)
-#endif
 constexpr int kOc2Scratch = 4096;
-#ifndef ADMM_OC2_REC_CHUNK
-#define ADMM_OC2_REC_CHUNK 1        // 1: a block's seven sums are ONE 64-byte chunk of the record buffer ([parity][block][8]: two sectors of its own), read
-#endif                              // chunk-wise; 0 (rounds 2-5): [parity][sum][block] -- four blocks on four XCDs share every sector, a wave per sum reads it back
-#ifndef ADMM_OC2_TRUST_SAMPLE
-#define ADMM_OC2_TRUST_SAMPLE 1      // the trust rule checked on a sample of solves, revoked when a check fails
-#endif
-#ifndef ADMM_OC2_TRUST
-#define ADMM_OC2_TRUST 1            // (0: compiled out -- same-box A/B of the code generation)
-#endif
+// records: a block's seven sums are ONE 64-byte chunk of the record buffer ([parity][block][8]: two sectors of its own), read chunk-wise
+// trust rule: checked on a sample of solves, revoked when a check fails
 constexpr double kOc2TrustTol2 = 1e-20;   // ... at a tolerance >= 1e-10 (round 4: the bench tolerance moved from 1e-8 to below 1e-9)
 constexpr int kOc2TrustIters = 40;  // pipelined iterations of a first pass whose recursive residual is believed without verification   // bytes of LDS scratch ahead of the local vector and the matrix slab
 typedef __attribute__((address_space(3))) unsigned long long LdsU64;
@@ -122,7 +100,7 @@ __device__ __forceinline__ void oc2_barrier_arrive(unsigned *bar) {
 }
 
 template <int MAXT>
-__global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Args a) {
+__global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *red = (double *)smem;                   // [16][24] wave totals of up to 24 quantities
     double *res24 = (double *)(smem + 3072);        // [24] their block totals
@@ -181,49 +159,15 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
     const unsigned long long *const cpg_w = (const unsigned long long *)(a.col16 + base);
     LdsD *const lv_w = lv_all + slab_off * 64;
     LdsU64 *const lc_w = lc_all + (slab_off >> 2) * 64;
-    // This row's right-hand side (see Oc2Args::g_inc): records of the local step + pin term + M x_bar, INTERLEAVED with the LDS fill -- as one
-    // dependent chain in front of it (index -> record -> sum: three round trips on 12 waves per CU) the fill phase took 24 us instead of 8
-    // (ADMM_HIP_OC_PROF, round 6), more than the launch it replaces.  Stage A: the first eight list entries; the slab's values; stage C: their
-    // records; the slab's columns; stage E: the sums, in list order (the order of k_gather_rhs: the same bits), longer lists in the plain loop.
-    const bool gon = a.g_inc != nullptr;
-    int ge[8]; const int *ginc = nullptr; int gw = 0;
-    if (gon) {
-        gw = __builtin_amdgcn_readfirstlane(a.g_w[s]);
-        ginc = a.g_inc + __builtin_amdgcn_readfirstlane(a.g_ptr[s]) + lane;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ge[i] = ginc[64 * i];
-#pragma unroll
-        for (int i = 4; i < 8; ++i) ge[i] = gw > 4 ? ginc[64 * i] : a.g_pad;
-    }
     {   // the thread's matrix row -> LDS, once per solve: values
         LdsD *lvw = lv_w + lane;
         const double *vpg = vpg_w + lane;
         for (int k = 0; k < wl_s; ++k) lvw[64 * k] = vpg[64 * k];
     }
-    union { double d[2]; bv4u v; } gr0[8]; union { double d; bv2u v; } gr1[8];
-    if (gon) {
-        const __amdgpu_buffer_rsrc_t rr = soa_rsrc(a.g_rec);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            gr0[i].v = __builtin_amdgcn_raw_buffer_load_b128(rr, ge[i] * 32, 0, 0);
-            gr1[i].v = __builtin_amdgcn_raw_buffer_load_b64(rr, ge[i] * 32 + 16, 0, 0);
-        }
-    }
     {   // ... and its columns
         LdsU64 *lcw = lc_w + lane;
         const unsigned long long *cpg = cpg_w + lane;
         for (int k = 0; k < (wl_s >> 2); ++k) lcw[64 * k] = cpg[64 * k];
-    }
-    if (gon) {
-        double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { acc[0] += gr0[i].d[0]; acc[1] += gr0[i].d[1]; acc[2] += gr1[i].d; }
-        if (gw > 8) gather_records(ginc + 64 * 8, gw - 8, a.g_rec, acc);
-        if (live) {
-            if (a.g_vert_pin) pin_term_update(a.g_vert_pin, a.g_pin_xyz, a.g_pin_active, a.g_pin_u, a.g_pin_z, a.g_pin_sc, a.g_pin_nrm, a.x, vi, true, acc);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a.g_b[3 * (size_t)vi + j] = acc[j] + a.g_Mxbar[3 * (size_t)vi + j];
-        }
     }
     const int hp0 = a.halo_ptr[blockIdx.x], nh = a.halo_ptr[blockIdx.x + 1] - hp0;
     // the halo entries this thread fetches (two per thread cover nh <= 2 T; more are read from the list every time)
@@ -254,7 +198,7 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
     if (blockIdx.x == 0 && tid < 9) a.bar[32 * 16 * ((a.seq & 1) ^ 1) + 16 * (tid < 8 ? tid : 17)] = 0u;
     if (a.skip && *a.skip) return;    // (after the clearing above: the next launch counts on the set this one cleared)
     if (tid < 3 * kOcSubK) { yw[tid] = 0.0; yw[3 * kOcSubK + tid] = 0.0; yz[tid] = 0.0; ycur[tid] = 0.0; }
-    if (tid == 0) ictl[3] = ADMM_OC2_TRUST_SAMPLE ? a.counters[76] : 0;      // trust revoked for this context (a SAMPLED verification of a short first pass failed: below)
+    if (tid == 0) ictl[3] = a.counters[76];      // trust revoked for this context (a SAMPLED verification of a short first pass failed: below)
     int ywp = 0;         // offset of the current y_w buffer (0 or 3 kOcSubK)
     unsigned ph = 0;     // publish phase of the vector: buffer parity = ph & 1, tag of the neighbour flags
     unsigned be = 0;     // grid-barrier epoch (arrivals of this block so far); record parity = be & 1
@@ -269,16 +213,8 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
     // own entries -> local vector and -> this wave's 64 sectors of ubuf: two 16-byte write-through stores per lane, each
     // instruction covering 1 KB of whole sectors (lane pairs write the two halves of a row's sector: half-written sectors
     // from a row-per-lane layout measured 3x slower to drain); transposed through the local vector
-    // layout of the local vector: component j of entry c.  ADMM_OC2_AOS: the three components of an entry side by side (24-byte
-    // stride: the row loop's three reads per matrix entry become one ds_read2_b64 + one ds_read_b64); 0: per-axis arrays
-#ifndef ADMM_OC2_AOS
-#define ADMM_OC2_AOS 0
-#endif
-#if ADMM_OC2_AOS
-#define OC2_VX(c, j) (3 * (c) + (j))
-#else
+    // layout of the local vector: component j of entry c, per-axis arrays
 #define OC2_VX(c, j) ((j) * NV + (c))
-#endif
     auto publish = [&](const double *v) {
         const int tid = otid(), lane = tid & 63;
         const int wb = tid & ~63;
@@ -360,20 +296,6 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
         __syncthreads();
         double acc[3] = {0.0, 0.0, 0.0};
         row_times_local_vector(acc);
-        if (a.sm_k2 != 0.0) {     // (uniform) second product: the halo part of the local vector is still zero
-            __syncthreads();
-            const int tid = otid();
-#pragma unroll
-            for (int j = 0; j < 3; ++j) vec[OC2_VX(tid, j)] = rd[j] * fma(a.sm_k2, acc[j], a.sm_k1 * v[j]);
-            __syncthreads();
-            double acc2[3] = {0.0, 0.0, 0.0};
-            row_times_local_vector(acc2);
-            const int t2 = otid();
-#pragma unroll
-            for (int j = 0; j < 3; ++j) out[j] = fma(rd[j], fma(a.sm_c0, v[j], acc2[j]), vec[OC2_VX(t2, j)]);
-            __syncthreads();
-            return;
-        }
 #pragma unroll
         for (int j = 0; j < 3; ++j) out[j] = rd[j] * fma(-a.sm_b, acc[j], a.sm_ab * v[j]);
         __syncthreads();   // the local vector is rewritten by the next publish
@@ -431,19 +353,14 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
             }
         }, std::integral_constant<int, 3>());
         const int tid = otid();
-#if ADMM_OC2_REC_CHUNK
         if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, res24[tid]);      // (res24[7] = 0: the chunk is written whole)
-#else
-        if (tid < 7) oc_store_sc1(rs_p, ((par * 8 + tid) * a.G + (int)blockIdx.x) * 8, res24[tid]);
-#endif
         else if (with_v && tid >= 8 && tid < 8 + 3 * kOcSubK) {
             const int ag = (tid - 8) / 3, j = (tid - 8) - 3 * ag;
             oc_store_sc1(rs_c, ((par * 3 + j) * a.ncp + (int)blockIdx.x * kOcSubK + ag) * 8, res24[tid]);
         }
     };
     // after the grid barrier: bc[0..nsum) = the global sums of the records of parity par
-#if ADMM_OC2_REC_CHUNK
-    // The records of all blocks, chunk-wise (round 6): the buffer of one parity is 4 G units of 16 bytes (unit o = sums 2 (o & 3), 2 (o & 3) + 1 of block
+    // The records of all blocks, chunk-wise: the buffer of one parity is 4 G units of 16 bytes (unit o = sums 2 (o & 3), 2 (o & 3) + 1 of block
     // o >> 2); thread tid takes the units tid, tid + T, ... -- T is a multiple of four, so all of them carry the SAME pair of sums -- one or two
     // 16-byte loads per thread instead of four 8-byte loads per lane of seven waves, every sector asked for once per block.  rec_reduce then adds
     // up the pairs: over the lanes of equal lane & 3 inside each row of sixteen (two DPP shifts), over the four rows (two lane exchanges), over the
@@ -476,25 +393,10 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
             bc[tid] = sm;
         }
     };
-#endif
     auto reduce_records = [&](int par, int nsum) {
-#if ADMM_OC2_REC_CHUNK
         RecUnit g0, g1;
         rec_issue(par, g0, g1);
         rec_reduce(par, nsum, g0, g1);
-        __syncthreads();
-        return;
-#endif
-        const int tid = otid(), lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-        for (int k = wv; k < nsum; k += nw) {
-            double rec[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const int g = lane + 64 * i; rec[i] = g < a.G ? oc_load_sc1_f64(rs_p, ((par * 8 + k) * a.G + g) * 8) : 0.0; }
-            double sm = (rec[0] + rec[1]) + (rec[2] + rec[3]);
-            for (int g = lane + 256; g < a.G; g += 64) sm += oc_load_sc1_f64(rs_p, ((par * 8 + k) * a.G + g) * 8);
-            sm = wave_sum(sm);
-            if (lane == 0) bc[k] = sm;
-        }
         __syncthreads();
     };
     // The rows of Ac^-1 of this block's aggregates, columns tid and tid + T: constant over the solve, fetched (L2) ahead
@@ -512,40 +414,17 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
     // after the grid barrier: bc[0..nsum) = global sums of the records, ycur = (rows of Ac^-1 of this block's aggregates) x
     // (published coarse vector), all of parity par.  Every global load is issued before the first use.
     auto reduce_and_coarse = [&](int par, int nsum, const AinvRows &ar) {
-        double rec[4] = {0.0, 0.0, 0.0, 0.0}, cn[2][3];
-        const int tid = otid(), lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if ADMM_OC2_REC_CHUNK
+        double cn[2][3];
+        const int tid = otid();
         RecUnit g0, g1;
         if (nsum > 0) rec_issue(par, g0, g1);
-#else
-        if (wv < nsum) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const int g = lane + 64 * i; rec[i] = g < a.G ? oc_load_sc1_f64(rs_p, ((par * 8 + wv) * a.G + g) * 8) : 0.0; }
-        }
-#endif
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int c = tid + it * T;
 #pragma unroll
             for (int j = 0; j < 3; ++j) cn[it][j] = c < a.nc ? oc_load_sc1_f64(rs_c, ((par * 3 + j) * a.ncp + c) * 8) : 0.0;
         }
-#if ADMM_OC2_REC_CHUNK
         if (nsum > 0) rec_reduce(par, nsum, g0, g1);      // (bc is read behind the block barriers of the coarse rows below)
-        (void)rec; (void)lane; (void)wv;
-#else
-        if (wv < nsum) {
-            double sm = (rec[0] + rec[1]) + (rec[2] + rec[3]);
-            for (int g = lane + 256; g < a.G; g += 64) sm += oc_load_sc1_f64(rs_p, ((par * 8 + wv) * a.G + g) * 8);
-            sm = wave_sum(sm);
-            if (lane == 0) bc[wv] = sm;
-        }
-        for (int k = wv + nw; k < nsum; k += nw) {   // blocks with fewer waves than sums
-            double sm = 0.0;
-            for (int g = lane; g < a.G; g += 64) sm += oc_load_sc1_f64(rs_p, ((par * 8 + k) * a.G + g) * 8);
-            sm = wave_sum(sm);
-            if (lane == 0) bc[k] = sm;
-        }
-#endif
         __builtin_amdgcn_sched_barrier(0);     // (the record sums are done and their registers free before the coarse rows start)
         block_sums_gen([&](int h, double *q8) {
 #pragma unroll
@@ -881,7 +760,7 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
                 // a solve's short first pass then fails its verification, block 0 revokes the trust for the context (counters[76]) and every later
                 // solve verifies.  (A 1 k-vertex body at pcg_tol 1e-10: unverified 5e-6 from the 1e-13 trajectory after eight frames, verified 8e-9
                 // -- experiments/r05_small_body_accuracy.py; the 1 M-tet bench body never fails one: its trajectory is bit-identical either way.)
-                const bool trusted = ADMM_OC2_TRUST && a.trust_short && ictl[3] == 0 && passes == 0 && a.tol2 >= kOc2TrustTol2 && target == kOcTrig * a.tol2;
+                const bool trusted = a.trust_short && ictl[3] == 0 && passes == 0 && a.tol2 >= kOc2TrustTol2 && target == kOcTrig * a.tol2;
                 const int pass_it0 = iters;
                 double rho_best = 1e300;
                 int since = 0;
@@ -969,7 +848,7 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
                         const int v = verify();      // leaves u = D^-1 (true residual)
                         if (v < 0) { aborted = true; break; }
                         if (v == 1) { conv = true; break; }
-                        if (ADMM_OC2_TRUST_SAMPLE && passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[76] = 1; atomicAdd(a.counters + 77, 1); }
+                        if (passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[76] = 1; atomicAdd(a.counters + 77, 1); }
                         fresh = true;                // the true residual replaces the recursive one: beta = 0
                         if (++passes >= 4) { go_classic = true; break; }
                         pass_start = 3.0 * ctl[1];   // (the largest axis ratio of the verification, as a bound of the sum)
@@ -1119,11 +998,12 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
             const int q = wv + u * nw;
             const float *zq = a.defl_Z + (size_t)(q < K ? q : 0) * a.n_rows + zrow0 + lane;
 #pragma unroll
-            for (int i = 0; i < SPBMAX; ++i) zw[u][i] = (q < K && i < a.spb && !(a.defl_dbg & 1)) ? zq[64 * i] : 0.0f;
+            for (int i = 0; i < SPBMAX; ++i) zw[u][i] = (q < K && i < a.spb) ? zq[64 * i] : 0.0f;
         }
 #pragma unroll
-        for (int q = 0; q < kOc2DeflMax; ++q) zmine[q] = (live && q < K && !(a.defl_dbg & 2)) ? a.defl_Z[(size_t)q * a.n_rows + row] : 0.0f;
-        if (!(a.defl_dbg & 4)) { if (tid < K * K) gv[0] = a.defl_Ginv[tid]; if (tid + T < K * K) gv[1] = a.defl_Ginv[tid + T]; }
+        for (int q = 0; q < kOc2DeflMax; ++q) zmine[q] = (live && q < K) ? a.defl_Z[(size_t)q * a.n_rows + row] : 0.0f;
+        if (tid < K * K) gv[0] = a.defl_Ginv[tid];
+        if (tid + T < K * K) gv[1] = a.defl_Ginv[tid + T];
     }
     double pe[3] = {0.0, 0.0, 0.0}, pr[3] = {0.0, 0.0, 0.0};
     if (live && a.rc_on) {
@@ -1145,11 +1025,9 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
         }
         // (G^-1 into LDS: the slab's first K K doubles are not needed any more)
         LdsD *ginv_l = lv_all;
-        if (!(a.defl_dbg & 4)) {
-            if (tid < K * K) ginv_l[tid] = gv[0];
-            if (tid + T < K * K) ginv_l[tid + T] = gv[1];
-            for (int o = tid + 2 * T; o < K * K; o += T) ginv_l[o] = a.defl_Ginv[o];      // (small blocks, many modes)
-        }
+        if (tid < K * K) ginv_l[tid] = gv[0];
+        if (tid + T < K * K) ginv_l[tid + T] = gv[1];
+        for (int o = tid + 2 * T; o < K * K; o += T) ginv_l[o] = a.defl_Ginv[o];      // (small blocks, many modes)
         __syncthreads();
         __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc((void *)a.defl_rec, 0, 2 * 3 * kOc2DeflMax * a.G * 8, 0x00020000);
         // modes: [mode][internal row], single precision.  (A [block][mode][row] layout, one contiguous 74-KB slice per block, was SLOWER: 44 us.)
@@ -1174,7 +1052,7 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
             double acc[3] = {0.0, 0.0, 0.0};
             for (int i = 0; i < a.spb; ++i) {
                 const int rl = lane + 64 * i;
-                const double zd = (a.defl_dbg & 1) ? 0.0 : (double)zq[64 * i];
+                const double zd = (double)zq[64 * i];
                 acc[0] = fma(zd, vec[OC2_VX(rl, 0)], acc[0]); acc[1] = fma(zd, vec[OC2_VX(rl, 1)], acc[1]); acc[2] = fma(zd, vec[OC2_VX(rl, 2)], acc[2]);
             }
             acc[0] = wave_sum(acc[0]); acc[1] = wave_sum(acc[1]); acc[2] = wave_sum(acc[2]);
@@ -1225,10 +1103,6 @@ __global__ __launch_bounds__(ADMM_OC2_LB(MAXT)) ADMM_OC2_ATTR void k_pcg2(Oc2Arg
                 if (q < K) {
 #pragma unroll
                     for (int j = 0; j < 3; ++j) rx[j] = fma((double)zmine[q], red[3 * kOc2DeflMax + 3 * q + j], rx[j]);
-                    if (a.defl_dbg & 8) {      // the pair carries the soft step too: e += Z y, A e += K Z y ~ Z (G y) = Z d (Z: Ritz vectors of K)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) { pe[j] = fma((double)zmine[q], red[3 * kOc2DeflMax + 3 * q + j], pe[j]); pr[j] = fma((double)zmine[q], red[3 * q + j], pr[j]); }
-                    }
                 }
             }
         }
@@ -1285,8 +1159,7 @@ __global__ __launch_bounds__(MAXT) void k_sync_probe(Oc2Args a, int n, int mode,
         if (mode == 0) {
             ++be;
             const int par = (int)(be & 1u);
-#if ADMM_OC2_REC_CHUNK      // (as k_pcg2: publish_record, rec_issue, rec_reduce)
-            if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, acc);
+            if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, acc);      // (as k_pcg2: publish_record, rec_issue, rec_reduce)
             if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) break;
             {
                 double sa = 0.0, sb = 0.0;
@@ -1303,44 +1176,6 @@ __global__ __launch_bounds__(MAXT) void k_sync_probe(Oc2Args a, int n, int mode,
                 if (lane >= 12 && lane < 16) { red2[wv * 8 + 2 * (lane & 3)] = sa; red2[wv * 8 + 2 * (lane & 3) + 1] = sb; }
                 __syncthreads();
                 if (tid < 7) { double sm = 0.0; for (int k = 0; k < nw; ++k) sm += red2[k * 8 + tid]; bc[tid] = sm; }
-            }
-#else
-            if (tid < 7) oc_store_sc1(rs_p, ((par * 8 + tid) * a.G + (int)blockIdx.x) * 8, acc);
-            if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) break;
-            if (wv < 7) {
-                double sm = 0.0;
-                for (int g = lane; g < a.G; g += 64) sm += oc_load_sc1_f64(rs_p, ((par * 8 + wv) * a.G + g) * 8);
-                sm = wave_sum(sm);
-                if (lane == 0) bc[wv] = sm;
-            }
-#endif
-            __syncthreads();
-            acc = acc * 0.5 + bc[0] * 1e-300;
-        } else if (mode >= 2) {
-            // (experiments, ADMM_HIP_PROBE_A2A_MODE: the block's 7 sums as ONE 64-byte chunk [parity][block][8] -- whole sectors of its own -- instead of
-            // [parity][sum][block], where four blocks share a sector.  2: read sum by sum (64-byte stride); 3: read chunk-wise, one 16-byte load per thread;
-            // 4: as 3, stored with four 16-byte stores)
-            ++be;
-            const int par = (int)(be & 1u);
-            if (mode == 4) { if (tid < 4) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + 2 * tid) * 8, acc, acc); }
-            else if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, acc);
-            if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) break;
-            if (mode == 2) {
-                if (wv < 7) {
-                    double sm = 0.0;
-                    for (int g = lane; g < a.G; g += 64) sm += oc_load_sc1_f64(rs_p, ((par * a.G + g) * 8 + wv) * 8);
-                    sm = wave_sum(sm);
-                    if (lane == 0) bc[wv] = sm;
-                }
-            } else {
-                double sm = 0.0;
-                for (int o = tid; o < 4 * a.G; o += T) {
-                    union { double d[2]; v4u v; } g;
-                    g.v = __builtin_amdgcn_raw_buffer_load_b128(rs_p, par * a.G * 64 + o * 16, 0, 16);
-                    sm += g.d[0] + g.d[1];
-                }
-                sm = wave_sum(sm);
-                if (lane == 0 && wv < 7) bc[wv] = sm;
             }
             __syncthreads();
             acc = acc * 0.5 + bc[0] * 1e-300;

@@ -76,7 +76,7 @@ def test_signed_svd_is_a_factorisation_to_3e14_on_every_kind_of_element(hm):
         rec = np.linalg.norm(U @ (S[:, :, None] * np.transpose(V, (0, 2, 1))) - F, axis=(1, 2)) / nF
         ou = np.linalg.norm(np.transpose(U, (0, 2, 1)) @ U - np.eye(3), axis=(1, 2))
         ov = np.linalg.norm(np.transpose(V, (0, 2, 1)) @ V - np.eye(3), axis=(1, 2))
-        assert rec.max() < 5e-14, (name, rec.max())                      # the documented bound (ADMM_SVD_TOL2 = 1e-27)
+        assert rec.max() < 5e-14, (name, rec.max())                      # the documented bound (kSvdTol2 = 1e-27)
         assert ou.max() < 1e-14 and ov.max() < 1e-14, (name, ou.max(), ov.max())
         assert np.linalg.det(U).min() > 0.999 and np.linalg.det(V).min() > 0.999, name      # rotations, not reflections
         sv = np.linalg.svd(F, compute_uv=False)
