@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <array>
+#include <atomic>
 #include <map>
 #include <memory>
 #include <numeric>
@@ -46,14 +47,30 @@ int fail(int code, const std::string &msg) {
             return fail(ADMM_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
 
+// live DevBuf allocations of the process (admm_hip_device_buffers)
+std::atomic<int64_t> g_dev_buffers{0}, g_dev_bytes{0};
+
+// One device allocation, owned: freed by the destructor, by release(), and by alloc() before it allocates again.
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
-    hipError_t alloc(size_t count) {
-        n = count;
-        if (count == 0) { p = nullptr; return hipSuccess; }
-        return hipMalloc((void **)&p, count * sizeof(T));
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count) {      // (a failed allocation leaves the buffer empty)
+        release();
+        if (count == 0) return hipSuccess;
+        T *q = nullptr;
+        const hipError_t e = hipMalloc((void **)&q, count * sizeof(T));
+        if (e != hipSuccess) return e;
+        p = q; n = count;
+        g_dev_buffers += 1; g_dev_bytes += (int64_t)(count * sizeof(T));
+        return hipSuccess;
     }
     hipError_t upload(const std::vector<T> &h) {
         hipError_t e = alloc(h.size());
@@ -61,8 +78,12 @@ struct DevBuf {
         return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
     }
     hipError_t zero() { return n ? hipMemset(p, 0, n * sizeof(T)) : hipSuccess; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    void release() {
+        if (p) { (void)hipFree(p); g_dev_buffers -= 1; g_dev_bytes -= (int64_t)(n * sizeof(T)); }
+        p = nullptr; n = 0;
+    }
 };
+static_assert(!std::is_copy_constructible<DevBuf<int> >::value && !std::is_copy_assignable<DevBuf<int> >::value, "DevBuf owns its allocation");
 
 struct SellDev {
     DevBuf<int> ptr, w, idx;
@@ -74,10 +95,8 @@ struct SellDev {
         if ((e = ptr.upload(S.slice_ptr)) != hipSuccess) return e;
         if ((e = w.upload(S.slice_width)) != hipSuccess) return e;
         if ((e = idx.upload(S.idx)) != hipSuccess) return e;
-        if (!S.val.empty() && (e = val.upload(S.val)) != hipSuccess) return e;
-        return hipSuccess;
+        return val.upload(S.val);
     }
-    void release() { ptr.release(); w.release(); idx.release(); val.release(); }
 };
 
 // RCCL is bound lazily (dlopen) so single-GPU use never loads it.
@@ -198,13 +217,12 @@ struct admm_hip_ctx {
     int NB = 1, NBV = 1;
     DevBuf<double> cg_r, cg_u, cg_w, cg_p, cg_s, part, part_b;
     DevBuf<CgScal> cg_scal;
-    DevBuf<int> counters; // [0] total inner iterations of the step, [1] gs done flag, [2] gs sweeps,
-                          // [3] max PCG iterations of one solve, [4] PCG solves that converged
+    DevBuf<int> counters;         // kCntWords words (layout: kernels.hpp, kCnt*)
     // PCG launch control.  Iterations are launched in chunks of kChunk, one chunk speculatively ahead
-    // of the GPU; the vec kernel signals convergence (sig[0] = solve sequence number) and progress
-    // (sig[1] = number of closed chunks) through pinned, device-mapped host memory, so the host stops
+    // of the GPU; the vec kernel signals convergence (kSigConverged) and progress
+    // (kSigChunks) through pinned, device-mapped host memory, so the host stops
     // launching as soon as a solve has converged -- without ever synchronising the stream.
-    int *h_sig = nullptr;         // pinned + mapped: [0] seq of the last converged solve, [1] closed chunks
+    int *h_sig = nullptr;         // pinned + mapped: kSigWords signal words (layout: kernels.hpp, kSig*)
     int *d_sig = nullptr;         // device alias of h_sig
     // on-chip PCG (pcg_onchip2.hpp): one persistent launch per solve when the system fits the chip
     bool oc_enabled = false;
@@ -235,7 +253,7 @@ struct admm_hip_ctx {
     SellDev big_A; DevBuf<int> big_orig; DevBuf<float> big_ainv;
     DevBuf<double> big_mass, big_dinv, big_cwt, big_xi, big_r, big_u, big_w, big_p, big_s, big_part, big_cvec, big_rho, big_dots; DevBuf<int> big_tick;
     long long big_solves = 0;
-    int oc_dbg_sm_off = -1;        // ADMM_HIP_OC_DEBUG: last seen state of counters[75] (block smoother switched off for the context)
+    int oc_dbg_sm_off = -1;        // ADMM_HIP_OC_DEBUG: last seen state of kCntSmootherOff (block smoother switched off for the context)
     bool defl_use_resid = true;    // launch_deflation after a launch-path solve: the solve's own final residual (ADMM_HIP_DEFL_RESID=0 at create: b - A x again)
     bool big_rfin_valid = false;   // c->cg_u holds D^-1 (final residual) of the launch-path solve that has just returned (launch_deflation)
     int big_its_hist[32] = {};    // iterations the launch-path solve at position s of the previous frame needed (first chunk of the next one)
@@ -310,15 +328,13 @@ struct admm_hip_ctx {
         DevBuf<char> slab;      // one allocation per lane (hipMalloc costs ~0.3 ms: a lane is set up inside a frame)
         double *ubuf = nullptr, *part = nullptr, *cbuf = nullptr, *b = nullptr, *x = nullptr, *u = nullptr;
         unsigned *bar = nullptr; unsigned long long *flags = nullptr; CgScal *scal = nullptr; int *counters = nullptr;
-        void release() {
+        ~OcLane() {
             if (st) (void)hipStreamSynchronize(st);      // (look-ahead solves may still be in flight)
-            slab.release();
             if (done) (void)hipEventDestroy(done);
             if (st) (void)hipStreamDestroy(st);
-            done = nullptr; st = nullptr;
         }
     };
-    std::vector<OcLane> uz_lanes; hipEvent_t uz_fork = nullptr; int uz_lanes_cfg = -1;   // uz_lanes_cfg: ADMM_HIP_UZ_LANES (1 = the main stream only; default: what fits, <= 8)
+    std::vector<std::unique_ptr<OcLane> > uz_lanes; hipEvent_t uz_fork = nullptr; int uz_lanes_cfg = -1;   // uz_lanes_cfg: ADMM_HIP_UZ_LANES (1 = the main stream only; default: what fits, <= 8)
     long long uzc_lane_batches = 0;
     // columns solved AHEAD of the contact (uz_ahead_launch): in flight on the lanes while the ADMM loop goes on, committed when they are done
     bool pf_on = false, in_step = false; double pf_frames = 0.0; int uz_fit = -1;
@@ -345,7 +361,6 @@ struct admm_hip_ctx {
     struct DynDev {
         DynMesh m{};
         DevBuf<int4> tet; DevBuf<int> tet_id, face, face_id; DevBuf<double> t_box, f_box, rest;
-        ~DynDev() { tet.release(); tet_id.release(); face.release(); face_id.release(); t_box.release(); f_box.release(); rest.release(); }
     };
     std::vector<std::unique_ptr<DynDev> > dyn;
     DevBuf<int> dyn_face, surf_list; DevBuf<double> dyn_bary, dyn_n, dyn_dx; DevBuf<unsigned char> surf_mask;
@@ -355,42 +370,12 @@ struct admm_hip_ctx {
     DevBuf<int> gsd_int; DevBuf<double> gsd_dbl; DevBuf<int4> gsd_hnode;
     int gsd_last_hits = 0;
 
-    ~admm_hip_ctx() {
+    ~admm_hip_ctx() {      // (every DevBuf member, lane and dynamic collider frees its own memory after this body)
         (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);      // nothing is freed under a kernel still in flight
+        for (const std::unique_ptr<OcLane> &ln : uz_lanes) if (ln->st) (void)hipStreamSynchronize(ln->st);
         if (comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
         if (cm_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(cm_comm);
-        cm_buf.release();
-        x.release(); v.release(); m.release(); Mxbar.release(); curr.release(); b.release(); dinv.release();
-        t_idx.release(); t_Binv.release(); t_u.release(); t_z.release(); t_sc.release(); t_rec.release(); ch_ent.release(); ch_group.release(); ch_rec.release();
-        t_mat.release(); mats.release(); spl_tab.release(); t_inc.release(); g_order.release();
-        r_idx.release(); r_rest.release(); r_u.release(); r_z.release(); r_sc.release(); r_cf.release();
-        r_lmin.release(); r_lmax.release(); r_inc.release();
-        h_idx.release(); h_coef.release(); h_u.release(); h_z.release(); h_sc.release(); h_gam.release(); h_cf.release(); h_inc.release(); pin_nrm.release(); gs_pin_nrm.release();
-        vert_pin.release(); pin_active.release(); pin_xyz.release(); pin_u.release(); pin_z.release();
-        gs_pin_flag.release(); gs_pin_xyz.release();
-        A.release(); csr_rowptr.release(); csr_col.release(); csr_val.release();
-        cg_r.release(); cg_u.release(); cg_w.release(); cg_p.release(); cg_s.release(); part.release(); part_b.release();
-        cg_scal.release(); counters.release(); color_nodes.release(); gs_sell.release(); gs_slot_node.release(); gs_diag.release(); gs_xb.release(); gs_part2.release(); gs_low.release();
-        oc_A.release(); oc_orig.release(); oc_ldsoff.release(); oc_wls.release(); oc_haloptr.release(); oc_halosrc.release(); oc_col16.release();
-        oc_mdiag.release(); oc_ainv.release(); oc_cbuf.release(); oc_cwt.release();
-        bk_x.release(); bk_v.release(); bk_y.release(); wind_tris.release(); wind_inc.release(); wind_force.release();
-        oc_ubuf.release(); oc_part.release(); oc_rc_part.release(); oc_bar.release(); oc_prof.release(); oc_nbr.release(); oc_flags.release();
-        gsp_hdr.release(); gsp_orig.release(); gsp_out.release(); gsp_hbox.release(); gsp_horig.release(); gsp_diag.release(); gsp_vals.release(); gsp_cols.release();
-        obst_gmeta.release(); obst_gdata.release(); obst_dev.release();
-        gsp_box.release(); gsp_part.release(); gsp_meet.release(); gsp_abort.release(); gsp_prof.release(); gs_proj.release();
-        defl_Z.release(); defl_Ginv.release(); defl_part.release(); defl_y.release(); defl_Zint.release(); defl_rec.release();
-        big_A.release(); big_orig.release(); big_ainv.release(); big_mass.release(); big_dinv.release(); big_cwt.release(); big_xi.release(); big_r.release();
-        big_u.release(); big_w.release(); big_p.release(); big_s.release(); big_part.release(); big_dots.release(); big_tick.release(); big_cvec.release(); big_rho.release(); big_if_rows.release(); big_ifbuf.release();
-        rc_buf.release(); rc_r0.release(); rc_xs.release(); rc_part.release(); rc_coef.release();
-        uz_cn.release(); uz_cc.release(); uz_y.release(); uz_r.release(); uz_d.release(); uz_q3.release(); uz_q1.release(); uz_dmax.release(); uz_dacc.release();
-        uz_q2.release(); uz_part.release(); uz_scal.release();
-        uzc_cols.release(); uzc_slot.release(); uzc_act.release(); uzc_miss.release(); uzc_info.release(); uzc_counts.release(); uzc_flag.release();
-        uzc_G.release(); uzc_part.release(); uzc_gq.release(); uz_y0.release(); uzc_pos.release(); uzp_rowlist.release(); uzp_S.release();
-        gsd_hits.release(); gsd_skip.release(); gsd_part.release(); gsd_int.release(); gsd_dbl.release(); gsd_hnode.release();
-        lk_ts.release(); lk_out.release();
-        dyn.clear(); dyn_face.release(); surf_list.release(); dyn_bary.release(); dyn_n.release(); dyn_dx.release(); surf_mask.release();
-        for (OcLane &ln : uz_lanes) ln.release();
-        uz_lanes.clear(); pf_list.release();
         if (uz_fork) (void)hipEventDestroy(uz_fork);
         for (hipEvent_t e : ev_phase) (void)hipEventDestroy(e);
         for (hipEvent_t e : lt_ev) (void)hipEventDestroy(e);
@@ -526,8 +511,8 @@ int oc_diagnostics(admm_hip_ctx *c, int seq) {
         CgScal h;
         if (hipMemcpyAsync(&h, c->cg_scal.p, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
         int sm_off[2] = {0, 0};
-        if (hipMemcpyAsync(sm_off, c->counters.p + 75, sizeof(sm_off), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-        if (sm_off[0] != c->oc_dbg_sm_off) { c->oc_dbg_sm_off = sm_off[0]; fprintf(stderr, "[oc] seq %d: block smoother switched %s for the context (counters[75]), sm_b %.3g, trust revoked %d\n", h.seq, sm_off[0] ? "OFF" : "on", c->oc_sm_b, sm_off[1]); }
+        if (hipMemcpyAsync(sm_off, c->counters.p + kCntSmootherOff, sizeof(sm_off), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        if (sm_off[0] != c->oc_dbg_sm_off) { c->oc_dbg_sm_off = sm_off[0]; fprintf(stderr, "[oc] seq %d: block smoother switched %s for the context (kCntSmootherOff), sm_b %.3g, trust revoked %d\n", h.seq, sm_off[0] ? "OFF" : "on", c->oc_sm_b, sm_off[1]); }
         fprintf(stderr, "[oc] seq %d iters %d (pipelined %d) verifications %d (last: true gamma / (tol^2 gamma_b) = %.2f) phases %d conv %d gamma %.3e %.3e %.3e gb %.3e %.3e %.3e\n", h.seq, h.iters, h.pad_,
                 (int)h.alpha[0], h.alpha[2], (int)h.alpha[1], h.converged, h.gamma[0], h.gamma[1], h.gamma[2], h.gamma_b[0], h.gamma_b[1], h.gamma_b[2]);
     }
@@ -878,13 +863,13 @@ int launch_pcg_big(admm_hip_ctx *c, const double *b, double *x, int max_iters) {
             if (chunks >= 2 && launched < max_iters) {
                 const int need = c->marks_expected - 1;
                 long spins = 0;
-                while (sig[1] < need) { if (++spins > 2000000000L) return -1; }
+                while (sig[kSigChunks] < need) { if (++spins > 2000000000L) return -1; }
                 // Converged inside the chunks that have DRAINED: a fact every rank must read the same way.  The mark the host has just seen is
                 // written by k_big_vec of the previous chunk's LAST iteration (end_prev - 1, 0-based); the verdict of that iteration is written
                 // by the k_big_coarse BEHIND it and may or may not be visible yet -- one rank leaving on it while another launches one more
                 // chunk of collectives is a deadlock (seen once in 40 runs of the suite: a 30-minute gloo time-out).  Verdicts of the iterations
                 // before it (count <= end_prev - 1) precede the mark in stream order: visible to every rank that has seen the mark.
-                if (sig[0] == a.seq && sig[3] <= end_prev - 1) break;
+                if (sig[kSigConverged] == a.seq && sig[kSigConvIter] <= end_prev - 1) break;
             }
         }
         hipLaunchKernelGGL(k_big_scatter, dim3(nbr), dim3(256), 0, st, a, launched & 1);
@@ -922,11 +907,11 @@ int launch_pcg_big(admm_hip_ctx *c, const double *b, double *x, int max_iters) {
         if (chunks >= 2 && launched < max_iters) {
             const int need = c->marks_expected - 1;
             long spins = 0;
-            while (sig[1] < need) { if (++spins > 2000000000L) return -1; }
-            if (sig[0] == a.seq) { seen = true; break; }
+            while (sig[kSigChunks] < need) { if (++spins > 2000000000L) return -1; }
+            if (sig[kSigConverged] == a.seq) { seen = true; break; }
         }
     }
-    if (seen) c->big_its_hist[pos] = std::max(1, (int)sig[3]);      // (the iteration the device converged at: written in front of sig[0])
+    if (seen) c->big_its_hist[pos] = std::max(1, (int)sig[kSigConvIter]);
     else if (launched >= max_iters) c->big_its_hist[pos] = 0;       // (ran to the cap: nothing learnt)
     hipLaunchKernelGGL(k_big_scatter, dim3(nbr), dim3(256), 0, st, a, launched & 1);
     c->last_launched_iters = launched;
@@ -979,10 +964,10 @@ int launch_pcg(admm_hip_ctx *c, const double *b, double *x, int max_iters, const
             // wait until the chunk BEFORE the one just launched has drained, then look at the flag
             const int need = c->marks_expected - 1;
             long spins = 0;
-            while (sig[1] < need) {
+            while (sig[kSigChunks] < need) {
                 if (++spins > 2000000000L) return -1; // the GPU stopped making progress
             }
-            if (sig[0] == seq) break;
+            if (sig[kSigConverged] == seq) break;
         }
     }
     c->last_launched_iters = launched;
@@ -1134,8 +1119,8 @@ int uz_make_lanes(admm_hip_ctx *c, int L) {
     typedef admm_hip_ctx::OcLane Lane;
     if (!c->uz_fork && hipEventCreateWithFlags(&c->uz_fork, hipEventDisableTiming) != hipSuccess) return -1;
     while ((int)c->uz_lanes.size() < L) {
-        c->uz_lanes.emplace_back();
-        Lane &ln = c->uz_lanes.back();
+        c->uz_lanes.emplace_back(new Lane());
+        Lane &ln = *c->uz_lanes.back();
         // the runtime keeps separate hardware queues per stream priority: lanes of different priority never share one
         int plo = 0, phi = 0;
         (void)hipDeviceGetStreamPriorityRange(&plo, &phi);      // (lowest, highest): numerically phi <= plo
@@ -1169,15 +1154,15 @@ int uz_lanes_enqueue(admm_hip_ctx *c, const std::vector<int> &verts, const std::
     if (uz_make_lanes(c, L)) return -1;
     if (hipEventRecord(c->uz_fork, c->stream) != hipSuccess) return -1;
     for (int l = 0; l < L; ++l) {
-        Lane &ln = c->uz_lanes[l];
+        Lane &ln = *c->uz_lanes[l];
         if (hipStreamWaitEvent(ln.st, c->uz_fork, 0) != hipSuccess) return -1;
         if (hipMemsetAsync(ln.counters, 0, c->counters.n * sizeof(int), ln.st) != hipSuccess || hipMemsetAsync(ln.bar, 0, c->oc_bar.n * sizeof(unsigned), ln.st) != hipSuccess) return -1;
-        // [75] the block smoother was given up, [76] the short-pass trust was revoked: the context's findings hold for the lanes too
-        if (hipMemcpyAsync(ln.counters + 75, c->counters.p + 75, 2 * sizeof(int), hipMemcpyDeviceToDevice, ln.st) != hipSuccess) return -1;
+        // the findings that change how k_pcg2 solves (smoother given up, trust revoked) hold for the lanes too
+        if (hipMemcpyAsync(ln.counters + kCntSmootherOff, c->counters.p + kCntSmootherOff, (kCntTrustRevoked + 1 - kCntSmootherOff) * sizeof(int), hipMemcpyDeviceToDevice, ln.st) != hipSuccess) return -1;
     }
     int n = 0;
     for (int k = 0; k < n_verts; k += 3, ++n) {
-        Lane &ln = c->uz_lanes[n % L];
+        Lane &ln = *c->uz_lanes[n % L];
         int v[3], sl[3];
         for (int j = 0; j < 3; ++j) { v[j] = k + j < n_verts ? verts[k + j] : -1; sl[j] = v[j] >= 0 ? slots[k + j] : -1; }
         hipLaunchKernelGGL(k_uz_unit_rhs_x0, dim3(blocks_for(c->n3)), dim3(256), 0, ln.st, (int)c->n3, v[0], v[1], v[2], ln.b, ln.x);
@@ -1187,14 +1172,14 @@ int uz_lanes_enqueue(admm_hip_ctx *c, const std::vector<int> &verts, const std::
     }
     *launched = n;
     for (int l = 0; l < L; ++l)
-        if (hipEventRecord(c->uz_lanes[l].done, c->uz_lanes[l].st) != hipSuccess) return -1;
+        if (hipEventRecord(c->uz_lanes[l]->done, c->uz_lanes[l]->st) != hipSuccess) return -1;
     return 0;
 }
 int uz_lanes_converged(admm_hip_ctx *c, int L, int *converged) {      // (after the lanes are done) solves that met their tolerance
     int conv = 0;
     for (int l = 0; l < L; ++l) {
         int v = 0;
-        if (hipMemcpy(&v, c->uz_lanes[l].counters + 4, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(&v, c->uz_lanes[l]->counters + kCntConverged, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
         conv += v;
     }
     *converged = conv;
@@ -1208,7 +1193,7 @@ int uz_columns_on_lanes(admm_hip_ctx *c, const std::vector<int> &miss, const std
     const auto t_enq0 = std::chrono::steady_clock::now();
     if (uz_lanes_enqueue(c, miss, slots, n_missing, L, max_iters, launched)) return -1;
     for (int l = 0; l < L; ++l)
-        if (hipStreamWaitEvent(c->stream, c->uz_lanes[l].done, 0) != hipSuccess) return -1;
+        if (hipStreamWaitEvent(c->stream, c->uz_lanes[l]->done, 0) != hipSuccess) return -1;
     const auto t_enq1 = std::chrono::steady_clock::now();
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
     if (dbg) fprintf(stderr, "[uz_lanes] ctx %p frame %d: %d solves on %d streams: enqueued in %.2f ms, done after %.2f ms\n", (void *)c, c->rc_frame, *launched, L,
@@ -1228,10 +1213,9 @@ int uz_grow_cols(admm_hip_ctx *c, size_t top) {
     if (cols < top) return 0;
     DevBuf<double> nb;
     if (nb.alloc(cols * (size_t)nv) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { nb.release(); return -1; }
-    if (c->uzc_n > 0 && hipMemcpy(nb.p, c->uzc_cols.p, sizeof(double) * (size_t)c->uzc_n * nv, hipMemcpyDeviceToDevice) != hipSuccess) { nb.release(); return -1; }
-    c->uzc_cols.release();
-    c->uzc_cols = nb;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    if (c->uzc_n > 0 && hipMemcpy(nb.p, c->uzc_cols.p, sizeof(double) * (size_t)c->uzc_n * nv, hipMemcpyDeviceToDevice) != hipSuccess) return -1;
+    c->uzc_cols = std::move(nb);
     return 1;
 }
 
@@ -1244,13 +1228,13 @@ double uz_column_tol(const admm_hip_ctx *c) {      // a hundredth of the solver'
 int uz_ahead_harvest(admm_hip_ctx *c, bool block) {
     if (c->pf_v.empty()) return 1;
     for (int l = 0; l < c->pf_lanes; ++l) {
-        const hipError_t e = block ? hipEventSynchronize(c->uz_lanes[l].done) : hipEventQuery(c->uz_lanes[l].done);
+        const hipError_t e = block ? hipEventSynchronize(c->uz_lanes[l]->done) : hipEventQuery(c->uz_lanes[l]->done);
         if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
         if (e != hipSuccess) return -1;
     }
     int conv = 0;
     if (uz_lanes_converged(c, c->pf_lanes, &conv)) return -1;
-    const bool aborted = c->h_sig && c->h_sig[2];
+    const bool aborted = c->h_sig && c->h_sig[kSigAbort];
     { if (c->uz_lanes_debug) fprintf(stderr, "[uz_ahead] ctx %p frame %d: harvest (%s) of %d columns: %d of %d launches converged%s\n", (void *)c, c->rc_frame, block ? "waited" : "polled",
                        (int)c->pf_v.size(), conv, c->pf_launched, aborted ? ", ABORTED" : ""); }
     if (!aborted && conv == c->pf_launched) {
@@ -1311,7 +1295,7 @@ int uz_ensure_columns(admm_hip_ctx *c, int n_missing) {
     if (!c->pf_v.empty()) {      // columns in flight (look-ahead): wait for them -- some of the missing ones may be among them
         c->pf_waits += 1;
         if (uz_ahead_harvest(c, true) < 0) return -1;
-        if (c->h_sig && c->h_sig[2]) return -2;
+        if (c->h_sig && c->h_sig[kSigAbort]) return -2;
     }
     if (c->pf_batches > 0) {     // (the list was made with the slot table of BEFORE this solve's harvest)
         miss.erase(std::remove_if(miss.begin(), miss.end(), [c](int v) { return c->uzc_slot_h[v] >= 0; }), miss.end());
@@ -1338,11 +1322,11 @@ int uz_ensure_columns(admm_hip_ctx *c, int n_missing) {
     const double keep_tol = c->pcg_tol;
     c->pcg_tol = uz_column_tol(c);
     int rc = 1;
-    // the solver's counters before the batch: [4] solves of this step that met their tolerance -- every column solve must add one --
-    // and [72..74] the totals admm_hip_solve_totals reports, which the column solves must not show up in (the caller's solves only)
-    int cnt0[8], tot0[3];
+    // the solver's counters before the batch: the solves of this step that met their tolerance -- every column solve must add one --
+    // and the totals admm_hip_solve_totals reports, which the column solves must not show up in (the caller's solves only)
+    int cnt0[kCntRing], tot0[kCntTotalsLen];
     if (hipMemcpy(cnt0, c->counters.p, sizeof(cnt0), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(tot0, c->counters.p + 72, sizeof(tot0), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        hipMemcpy(tot0, c->counters.p + kCntTotals, sizeof(tot0), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     int launched = 0, lane_conv = -1;
     const int max_col_iters = c->uzc_test_iters > 0 ? c->uzc_test_iters : std::max(c->pcg_max_iters, 2000);
     const int lanes = uz_lane_count(c, (n_missing + 2) / 3);
@@ -1359,19 +1343,19 @@ int uz_ensure_columns(admm_hip_ctx *c, int n_missing) {
     }
     c->pcg_tol = keep_tol;
     if (rc == 1 && hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    const bool aborted = c->h_sig && c->h_sig[2];     // a grid barrier of one of the solves timed out
+    const bool aborted = c->h_sig && c->h_sig[kSigAbort];     // a grid barrier of one of the solves timed out
     // Did every column solve meet its tolerance?  A column that ran out of iterations would be a wrong Schur operator for every later
     // solve: the batch is then not committed and this solve applies A^-1 by inner PCG solves (rc 0), counted in uzc_unconverged.
     bool all_converged = true;
     if (rc == 1 && !aborted && lane_conv >= 0) all_converged = lane_conv == launched;      // (the lanes count in their own counters: nothing to restore)
     else if (rc == 1 && !aborted) {
-        int cnt1[8];
+        int cnt1[kCntRing];
         if (hipMemcpy(cnt1, c->counters.p, sizeof(cnt1), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
         else {
-            all_converged = cnt1[4] - cnt0[4] == launched;
-            cnt1[0] = cnt0[0]; cnt1[3] = cnt0[3]; cnt1[4] = cnt0[4];      // the step's own statistics do not count the columns either
-            if (hipMemcpy(c->counters.p, cnt1, 5 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(c->counters.p + 72, tot0, sizeof(tot0), hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+            all_converged = cnt1[kCntConverged] - cnt0[kCntConverged] == launched;
+            for (int w : {kCntIters, kCntMaxIters, kCntConverged}) cnt1[w] = cnt0[w];      // the step's own statistics do not count the columns either
+            if (hipMemcpy(c->counters.p, cnt1, kCntStepWords * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(c->counters.p + kCntTotals, tot0, sizeof(tot0), hipMemcpyHostToDevice) != hipSuccess) rc = -1;
         }
     }
     // (the evicted vertices' slots may have been overwritten whatever happened: they are given up in every case)
@@ -1406,18 +1390,18 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
         // Collider::detect at the current iterate + ConstraintSet::make_matrix (ck = sqrt(constraint_w))
         const double ck = std::sqrt(std::max(0.0, c->constraint_w));
         if (c->timing && hipEventRecord(c->ev_coll0, st) != hipSuccess) return -1;
-        // (counters[6], the hit count: cleared by k_uz_act_compact after it has been read when the column cache is on -- see below)
-        if ((!c->uzc_on || !c->uz_hits_cleared) && hipMemsetAsync(c->counters.p + 6, 0, sizeof(int), st) != hipSuccess) return -1;
+        // (kCntHits: cleared by k_uz_act_compact after it has been read when the column cache is on -- see below)
+        if ((!c->uzc_on || !c->uz_hits_cleared) && hipMemsetAsync(c->counters.p + kCntHits, 0, sizeof(int), st) != hipSuccess) return -1;
         c->uz_hits_cleared = false;
         if (c->obst.n > 0)
-            hipLaunchKernelGGL(k_uz_detect, dim3(gv), dim3(256), 0, st, nv, x, c->obst, ck, c->uz_cn.p, c->uz_cc.p, c->counters.p + 6,
+            hipLaunchKernelGGL(k_uz_detect, dim3(gv), dim3(256), 0, st, nv, x, c->obst, ck, c->uz_cn.p, c->uz_cc.p, c->counters.p + kCntHits,
                                c->n_surf > 0 ? c->surf_mask.p : nullptr);
         else if (hipMemsetAsync(c->uz_cn.p, 0, c->n3 * sizeof(double), st) != hipSuccess ||
                  hipMemsetAsync(c->uz_cc.p, 0, nv * sizeof(double), st) != hipSuccess) return -1;
         if (dyn) {
             if (enqueue_dyn_detect(c, x)) return -1;
             hipLaunchKernelGGL(k_dyn_rows, dim3(gq), dim3(256), 0, st, nq, qlist, ck, c->uz_cn.p, c->uz_cc.p, c->dyn_face.p, c->dyn_n.p,
-                               c->counters.p + 6);
+                               c->counters.p + kCntHits);
         }
         if (c->timing && hipEventRecord(c->ev_coll1, st) != hipSuccess) return -1;
         int info[3] = {0, 0, 0};
@@ -1428,7 +1412,7 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
             }
             const unsigned char *fl = dyn ? c->uzc_flag.p : (const unsigned char *)nullptr;
             const int nbc = (nv + 4095) / 4096;
-            if (nbc > c->uzc_one_block_max && c->uzc_counts.n < (size_t)2 * nbc) { c->uzc_counts.release(); if (c->uzc_counts.alloc((size_t)2 * nbc) != hipSuccess) return -1; }
+            if (nbc > c->uzc_one_block_max && c->uzc_counts.n < (size_t)2 * nbc && c->uzc_counts.alloc((size_t)2 * nbc) != hipSuccess) return -1;
             // ascending list of the flagged vertices (flag == nullptr: of the vertices whose row of C is not zero)
             auto list = [&](const unsigned char *flag, int *out, int *miss_out, int *pos_out, int *info_out, int *hits) {
                 if (nbc <= c->uzc_one_block_max)
@@ -1438,7 +1422,7 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
                     hipLaunchKernelGGL(k_uz_act_scatter, dim3(nbc), dim3(1024), 0, st, nv, flag, c->uzc_slot.p, c->uz_cn.p, c->uzc_counts.p, out, miss_out, pos_out, info_out, hits);
                 }
             };
-            list(fl, c->uzc_act.p, c->uzc_miss.p, c->uzc_pos.p, c->uzc_info.p, c->counters.p + 6);
+            list(fl, c->uzc_act.p, c->uzc_miss.p, c->uzc_pos.p, c->uzc_info.p, c->counters.p + kCntHits);
             c->uz_hits_cleared = true;
             if (hipMemcpyAsync(info, c->uzc_info.p, sizeof(info), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
             if (dyn && c->uzp_enabled) {     // the ROWS (vertices that carry a row), for the persistent Schur kernel on coupled rows (k_uzc_schur)
@@ -1449,7 +1433,7 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
                     if (hipMemcpyAsync(c->uzp_rowinfo, rl + 3 * (size_t)nv, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
                 }
             }
-        } else if (hipMemcpyAsync(&nh, c->counters.p + 6, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+        } else if (hipMemcpyAsync(&nh, c->counters.p + kCntHits, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
         // LOOK-AHEAD, once per step (its first detect), passive objects: which vertices will touch within pf_frames frames at their current
         // speed and have no column of K^-1?  (c->v: the velocity after the explicit forces of this step.)  Their columns are solved on the
         // lanes while the ADMM loop goes on, so that the touchdown finds them in the cache.
@@ -1462,7 +1446,7 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
             if (hipMemcpyAsync(&pf_count, c->pf_list.p + nv, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
         }
         if (hipStreamSynchronize(st) != hipSuccess) return -1;
-        if (c->h_sig && c->h_sig[2]) return -2;      // an earlier persistent launch (Schur CG, on-chip PCG) was given up: recovery path
+        if (c->h_sig && c->h_sig[kSigAbort]) return -2;      // an earlier persistent launch (Schur CG, on-chip PCG) was given up: recovery path
         if (c->uzc_on && first_detect && !c->pf_v.empty() && uz_ahead_harvest(c, false) < 0) return -1;      // (done by now? then commit; never waits here)
         if (c->uzc_on) nh = info[2];
         if (c->uzc_on) {
@@ -1510,9 +1494,9 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
         nseg = std::max(1, std::min(std::min(16, nbi), 256 / nbi));
         seg_len = (n_act + nseg - 1) / nseg;
         const size_t needG = (size_t)n_act * ldG, needP = (size_t)nseg * n_act * 3;
-        if (c->uzc_G.n < needG) { c->uzc_G.release(); if (c->uzc_G.alloc(needG + needG / 4) != hipSuccess) { (void)hipGetLastError(); c->uzc_G.n = 0; c->uzc_G.p = nullptr; compact = false; } }
-        if (compact && c->uzc_part.n < needP) { c->uzc_part.release(); if (c->uzc_part.alloc(2 * needP) != hipSuccess) return -1; }
-        if (compact && c->uzc_gq.n < (size_t)3 * n_act) { c->uzc_gq.release(); if (c->uzc_gq.alloc((size_t)6 * n_act) != hipSuccess) return -1; }
+        if (c->uzc_G.n < needG && c->uzc_G.alloc(needG + needG / 4) != hipSuccess) { (void)hipGetLastError(); compact = false; }
+        if (compact && c->uzc_part.n < needP && c->uzc_part.alloc(2 * needP) != hipSuccess) return -1;
+        if (compact && c->uzc_gq.n < (size_t)3 * n_act && c->uzc_gq.alloc((size_t)6 * n_act) != hipSuccess) return -1;
     }
     // Passive rows only, <= 1024 active vertices: the whole Schur CG is ONE persistent launch (uz_persist.hpp; ADMM_HIP_UZ_PERSIST=0:
     // two launches per iteration, as before).  Decided before the extraction: the persistent kernel takes S_ij = G_ij (n_i . n_j).
@@ -1531,7 +1515,7 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
         }
         // (its blocks hand granules to each other: all of them must be resident at once -- one block per CU at this LDS size)
         if (persist && (NB > kUzpMaxBlocks || NB > c->n_cus || uzp_lds_bytes(n_rows, R) > (size_t)(160 * 1024 - 256))) persist = false;
-        if (persist && dyn && c->uzp_S.n < (size_t)n_rows * ldS) { c->uzp_S.release(); if (c->uzp_S.alloc((size_t)n_rows * ldS * 2) != hipSuccess) { (void)hipGetLastError(); persist = false; } }
+        if (persist && dyn && c->uzp_S.n < (size_t)n_rows * ldS && c->uzp_S.alloc((size_t)n_rows * ldS * 2) != hipSuccess) { (void)hipGetLastError(); persist = false; }
     }
     if (compact) {
         if (hipMemcpyAsync(c->uz_y0.p, c->uz_y.p, nv * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
@@ -1555,12 +1539,12 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
             ua.dbox = (v4u *)c->uzp_dbox.p; ua.sbox = (v4u *)c->uzp_sbox.p;
             ua.stamp0 = (++c->uzp_seq) * 1024u;      // (four stamps per iteration, < 250 iterations)
             ua.abort_word = c->uzp_abort.p; ua.sig = c->d_sig;
-            ua.iters_step = c->counters.p + 7; ua.applies_total = c->counters.p + 78;      // ([76] is k_pcg2's "trust revoked" word: until round 6 the two shared it -- every Schur launch revoked the trust, a revocation reset the count)
+            ua.iters_step = c->counters.p + kCntSchurIters; ua.applies_total = c->counters.p + kCntSchurProducts;
             if (c->test_abort_uzp > 0 && (int)c->uzp_seq == c->test_abort_uzp)      // test hook: this launch finds its hand-off given up
                 (void)hipMemsetAsync(c->uzp_abort.p, 1, sizeof(unsigned), st);
             hipLaunchKernelGGL(k_uz_persist, dim3(NB), dim3(kUzpT), lds, st, ua);
             c->uzp_launches += 1;
-            // No synchronisation: the verdict stays on the device, the iteration count goes to counters[7] (read with the step's
+            // No synchronisation: the verdict stays on the device, the iteration count goes to kCntSchurIters (read with the step's
             // statistics), a hand-off time-out shows at the next synchronisation like any aborted on-chip solve.
             persist_launched = true;
             launched = c->uz_max_iters;
@@ -1626,12 +1610,12 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
 
 void enqueue_gs(admm_hip_ctx *c, const double *b, double *x) {
     hipStream_t st = c->stream;
-    (void)hipMemsetAsync(c->counters.p + 1, 0, 2 * sizeof(int), st);
+    (void)hipMemsetAsync(c->counters.p + kCntGsDone, 0, (kCntGsSweeps + 1 - kCntGsDone) * sizeof(int), st);
     GsArgs a{};
     a.S = sell_arg(c->gs_sell); a.slot_node = c->gs_slot_node.p; a.diag = c->gs_diag.p; a.m = c->m.p; a.b = b; a.x = x;
     a.pin_flag = c->gs_has_pins ? c->gs_pin_flag.p : nullptr; a.pin_xyz = c->gs_pin_xyz.p; a.pin_nrm = c->gs_pin_nrm.p;
-    a.omega = c->gs_omega; a.done = c->counters.p + 1;
-    a.part = c->part.p; a.NBp = c->NB; a.tol2 = c->gs_tol * c->gs_tol; a.sweeps = c->counters.p + 2; a.total = c->counters.p;
+    a.omega = c->gs_omega; a.done = c->counters.p + kCntGsDone;
+    a.part = c->part.p; a.NBp = c->NB; a.tol2 = c->gs_tol * c->gs_tol; a.sweeps = c->counters.p + kCntGsSweeps; a.total = c->counters.p + kCntIters;
     a.proj = c->gs_proj.p;
     const SellA A = sell_arg(c->A);
     const int check = c->gs_tol > 0.0 ? 1 : 0;
@@ -1683,12 +1667,12 @@ void enqueue_gs(admm_hip_ctx *c, const double *b, double *x) {
             first = false;
         }
         if (check)
-            hipLaunchKernelGGL(k_gs_resid, dim3(c->NB), dim3(256), 0, st, A, c->m.p, b, x, c->part.p, c->NB, c->counters.p + 1,
+            hipLaunchKernelGGL(k_gs_resid, dim3(c->NB), dim3(256), 0, st, A, c->m.p, b, x, c->part.p, c->NB, c->counters.p + kCntGsDone,
                                (const unsigned char *)nullptr);
     }
     // the last sweep is settled by a dedicated one-block kernel
-    hipLaunchKernelGGL(k_gs_check, dim3(1), dim3(256), 0, st, c->part.p, c->NB, c->gs_tol * c->gs_tol, c->counters.p + 1,
-                       c->counters.p + 2, c->counters.p, check);
+    hipLaunchKernelGGL(k_gs_check, dim3(1), dim3(256), 0, st, c->part.p, c->NB, c->gs_tol * c->gs_tol, c->counters.p + kCntGsDone,
+                       c->counters.p + kCntGsSweeps, c->counters.p + kCntIters, check);
 }
 
 // the whole solve as ONE persistent launch (gs_persist.hpp)
@@ -1703,7 +1687,7 @@ void launch_gs_persist(admm_hip_ctx *c, const double *b, double *x) {
     a.omega = c->gs_omega; a.tol2 = c->gs_tol * c->gs_tol; a.max_sweeps = c->gs_max_iters; a.check = c->gs_tol > 0.0 ? 1 : 0;
     a.seq = (unsigned)++c->solve_seq;
     a.box = (v4u *)c->gsp_box.p; a.n_box = (int)std::max<int64_t>(c->gsp_stat[4], 1); a.part = (v4u *)c->gsp_part.p; a.meet = (v4u *)c->gsp_meet.p; a.abort_word = c->gsp_abort.p;
-    a.done = c->counters.p + 1; a.sweeps = c->counters.p + 2; a.total = c->counters.p; a.sig = c->d_sig;
+    a.done = c->counters.p + kCntGsDone; a.sweeps = c->counters.p + kCntGsSweeps; a.total = c->counters.p + kCntIters; a.sig = c->d_sig;
     a.prof = c->gsp_prof.p; a.prof_block = c->gsp_prof_block;
     a.ob = c->obst_dev.p; a.proj = c->gs_proj.p;
     if (c->test_abort_seq > 0 && (int)a.seq == c->test_abort_seq)   // test hook: this solve finds its hand-off given up
@@ -1813,12 +1797,12 @@ int launch_gs_dynamic(admm_hip_ctx *c, const double *b, double *x) {
     const int *qlist = c->n_surf > 0 ? c->surf_list.p : nullptr;
     if (c->timing && hipEventRecord(c->ev_coll0, st) != hipSuccess) return -1;
     if (enqueue_dyn_detect(c, x)) return -1;
-    if (hipMemsetAsync(c->counters.p + 6, 0, sizeof(int), st) != hipSuccess) return -1;
+    if (hipMemsetAsync(c->counters.p + kCntHits, 0, sizeof(int), st) != hipSuccess) return -1;
     hipLaunchKernelGGL(k_dyn_compact, dim3(blocks_for(nq)), dim3(256), 0, st, nq, qlist, c->dyn_face.p, c->dyn_bary.p, c->dyn_n.p,
-                       c->gsd_hits.p, (int)c->gsd_hits.n, c->counters.p + 6);
+                       c->gsd_hits.p, (int)c->gsd_hits.n, c->counters.p + kCntHits);
     if (c->timing && hipEventRecord(c->ev_coll1, st) != hipSuccess) return -1;
     int nh = 0;
-    if (hipMemcpyAsync(&nh, c->counters.p + 6, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+    if (hipMemcpyAsync(&nh, c->counters.p + kCntHits, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
     if (c->timing) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev_coll0, c->ev_coll1) == hipSuccess) c->coll_ms_step += ms; }
     c->gsd_last_hits = nh;
@@ -1891,9 +1875,9 @@ int launch_gs_dynamic(admm_hip_ctx *c, const double *b, double *x) {
     const size_t o_rval = 0, o_hcoef = o_rval + rval.size(), o_hc = o_hcoef + hcoef.size(), o_hn = o_hc + hc.size();
     dbl.insert(dbl.end(), rval.begin(), rval.end()); dbl.insert(dbl.end(), hcoef.begin(), hcoef.end());
     dbl.insert(dbl.end(), hc.begin(), hc.end()); dbl.insert(dbl.end(), hn.begin(), hn.end());
-    if (c->gsd_int.n < ints.size()) { c->gsd_int.release(); if (c->gsd_int.alloc(2 * ints.size()) != hipSuccess) return -1; }
-    if (c->gsd_dbl.n < dbl.size()) { c->gsd_dbl.release(); if (c->gsd_dbl.alloc(2 * dbl.size()) != hipSuccess) return -1; }
-    if (c->gsd_hnode.n < hnode.size()) { c->gsd_hnode.release(); if (c->gsd_hnode.alloc(2 * hnode.size()) != hipSuccess) return -1; }
+    if (c->gsd_int.n < ints.size() && c->gsd_int.alloc(2 * ints.size()) != hipSuccess) return -1;
+    if (c->gsd_dbl.n < dbl.size() && c->gsd_dbl.alloc(2 * dbl.size()) != hipSuccess) return -1;
+    if (c->gsd_hnode.n < hnode.size() && c->gsd_hnode.alloc(2 * hnode.size()) != hipSuccess) return -1;
     std::vector<unsigned char> mask(nv, 0);
     for (int v : touched) mask[v] = 1;
     if (hipMemcpyAsync(c->gsd_int.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -1908,13 +1892,13 @@ int launch_gs_dynamic(admm_hip_ctx *c, const double *b, double *x) {
     d.hnode = c->gsd_hnode.p;
     d.ck2 = std::max(0.0, c->constraint_w);
     // the sweeps (plain launches: the colour structure changes with every solve, so there is nothing to capture)
-    (void)hipMemsetAsync(c->counters.p + 1, 0, 2 * sizeof(int), st);
+    (void)hipMemsetAsync(c->counters.p + kCntGsDone, 0, (kCntGsSweeps + 1 - kCntGsDone) * sizeof(int), st);
     const int NBp = c->NB + 1;
     GsArgs a{};
     a.S = sell_arg(c->gs_sell); a.slot_node = c->gs_slot_node.p; a.diag = c->gs_diag.p; a.m = c->m.p; a.b = b; a.x = x;
     a.pin_flag = c->gs_has_pins ? c->gs_pin_flag.p : nullptr; a.pin_xyz = c->gs_pin_xyz.p; a.pin_nrm = c->gs_pin_nrm.p;
-    a.omega = c->gs_omega; a.done = c->counters.p + 1;
-    a.part = c->gsd_part.p; a.NBp = NBp; a.tol2 = c->gs_tol * c->gs_tol; a.sweeps = c->counters.p + 2; a.total = c->counters.p;
+    a.omega = c->gs_omega; a.done = c->counters.p + kCntGsDone;
+    a.part = c->gsd_part.p; a.NBp = NBp; a.tol2 = c->gs_tol * c->gs_tol; a.sweeps = c->counters.p + kCntGsSweeps; a.total = c->counters.p + kCntIters;
     a.skip = c->gsd_skip.p;
     const SellA A = sell_arg(c->A);
     const int check = c->gs_tol > 0.0 ? 1 : 0;
@@ -1930,13 +1914,13 @@ int launch_gs_dynamic(admm_hip_ctx *c, const double *b, double *x) {
         for (int e = 0; e < n_extra; ++e)
             hipLaunchKernelGGL(k_gs_touched, dim3((cstart[e + 1] - cstart[e] + 63) / 64), dim3(64), 0, st, a, d, cstart[e], cstart[e + 1], c->obst);
         if (check) {
-            hipLaunchKernelGGL(k_gs_resid, dim3(c->NB), dim3(256), 0, st, A, c->m.p, b, x, c->gsd_part.p, NBp, c->counters.p + 1,
+            hipLaunchKernelGGL(k_gs_resid, dim3(c->NB), dim3(256), 0, st, A, c->m.p, b, x, c->gsd_part.p, NBp, c->counters.p + kCntGsDone,
                                (const unsigned char *)c->gsd_skip.p);
             hipLaunchKernelGGL(k_gs_touched_resid, dim3(1), dim3(256), 0, st, a, d, c->gsd_part.p, NBp, c->NB);
         }
     }
-    hipLaunchKernelGGL(k_gs_check, dim3(1), dim3(256), 0, st, c->gsd_part.p, NBp, c->gs_tol * c->gs_tol, c->counters.p + 1,
-                       c->counters.p + 2, c->counters.p, check);
+    hipLaunchKernelGGL(k_gs_check, dim3(1), dim3(256), 0, st, c->gsd_part.p, NBp, c->gs_tol * c->gs_tol, c->counters.p + kCntGsDone,
+                       c->counters.p + kCntGsSweeps, c->counters.p + kCntIters, check);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -2128,8 +2112,8 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&c->ev_step0));
     HIP_TRY(hipEventCreate(&c->ev_step1));
-    HIP_TRY(hipHostMalloc((void **)&c->h_sig, 4 * sizeof(int), hipHostMallocMapped));
-    c->h_sig[0] = c->h_sig[1] = c->h_sig[2] = c->h_sig[3] = 0;
+    HIP_TRY(hipHostMalloc((void **)&c->h_sig, kSigWords * sizeof(int), hipHostMallocMapped));
+    std::memset(c->h_sig, 0, kSigWords * sizeof(int));
     HIP_TRY(hipHostGetDevicePointer((void **)&c->d_sig, c->h_sig, 0));
 
     const double dt2 = c->dt * c->dt;
@@ -2389,7 +2373,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     HIP_TRY(c->cg_p.zero()); HIP_TRY(c->cg_s.zero());
     HIP_TRY(c->part.alloc(6 * (size_t)c->NB)); HIP_TRY(c->part_b.alloc(3 * (size_t)c->NB));
     HIP_TRY(c->cg_scal.alloc(2)); HIP_TRY(c->cg_scal.zero());
-    HIP_TRY(c->counters.alloc(8 + 64 + 8)); HIP_TRY(c->counters.zero());   // [72..74]: totals since create (on-chip PCG); [75] block smoother given up, [76] short-pass trust revoked, [77] failed sample checks (k_pcg2); [78] Schur products (k_uz_persist)
+    HIP_TRY(c->counters.alloc(kCntWords)); HIP_TRY(c->counters.zero());
     c->create_xyz = d->vert_xyz;
     c->big_allowed = env_flag("ADMM_HIP_BIG", true);
     c->defl_start = env_int("ADMM_HIP_DEFL_START", c->defl_start);
@@ -2592,7 +2576,7 @@ int admm_hip_get_state(admm_hip_ctx *c, double *x, double *v) {
         }
         std::vector<double> full(n3g, 0.0);
         for (int i = 0; i < c->nv; ++i) for (int j = 0; j < 3; ++j) full[3 * (size_t)c->cm.l2g[i] + j] = src[3 * (size_t)i + j];
-        if (c->cm_buf.n < n3g) { c->cm_buf.release(); HIP_TRY(c->cm_buf.alloc(n3g)); }
+        if (c->cm_buf.n < n3g) HIP_TRY(c->cm_buf.alloc(n3g));
         HIP_TRY(hipMemcpyAsync(c->cm_buf.p, full.data(), n3g * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (g_rccl.AllReduce(c->cm_buf.p, c->cm_buf.p, n3g, ncclDouble, ncclSum, c->cm_comm, c->stream) != ncclSuccess)
             return fail(ADMM_HIP_ERR_COMM, "get_state: ncclAllReduce (merge of the ranks' bodies) failed");
@@ -2609,8 +2593,8 @@ static int set_state_impl(admm_hip_ctx *c, const double *x, const double *v) {
     if (v) HIP_TRY(hipMemcpyAsync(c->v.p, v, c->n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     else HIP_TRY(hipMemsetAsync(c->v.p, 0, c->n3 * sizeof(double), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->h_sig && c->h_sig[2]) {   // the steps before this call hit a barrier time-out; their result is overwritten anyway
-        c->h_sig[2] = 0; c->oc_gave_up = true; c->oc_enabled = false; c->gsp_enabled = false; c->uzp_enabled = false; c->rc_iter = 0;
+    if (c->h_sig && c->h_sig[kSigAbort]) {   // the steps before this call hit a barrier time-out; their result is overwritten anyway
+        c->h_sig[kSigAbort] = 0; c->oc_gave_up = true; c->oc_enabled = false; c->gsp_enabled = false; c->uzp_enabled = false; c->rc_iter = 0;
         c->rc_hist = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0;   // (pairs half-written by the aborted solve, and in the on-chip row order)
         if (c->oc_bar.p) HIP_TRY(c->oc_bar.zero());
         if (c->gsp_abort.p) HIP_TRY(c->gsp_abort.zero());
@@ -2630,7 +2614,7 @@ static int get_state_impl(admm_hip_ctx *c, double *x, double *v) {
     if (x) HIP_TRY(hipMemcpyAsync(x, c->x.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (v) HIP_TRY(hipMemcpyAsync(v, c->v.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->h_sig && c->h_sig[2]) {   // replay on the launch path, then read the state again
+    if (c->h_sig && c->h_sig[kSigAbort]) {   // replay on the launch path, then read the state again
         if (int rc = recover_from_abort(c, nullptr)) return rc;
         if (x) HIP_TRY(hipMemcpy(x, c->x.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost));
         if (v) HIP_TRY(hipMemcpy(v, c->v.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2766,9 +2750,8 @@ static int set_wind_impl(admm_hip_ctx *c, int32_t n_tris, const int32_t *tris, c
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int rc = settle(c)) return rc;
-    c->wind_tris.release(); c->wind_inc.release(); c->wind_force.release();
     c->wind_n = n_tris;
-    if (n_tris == 0) return ADMM_HIP_OK;
+    if (n_tris == 0) { c->wind_tris.release(); c->wind_inc = SellDev(); c->wind_force.release(); return ADMM_HIP_OK; }
     for (int j = 0; j < 3; ++j) c->wind_dir[j] = direction[j];
     HIP_TRY(c->wind_tris.upload(std::vector<int>(tris, tris + 3 * (size_t)n_tris)));
     HIP_TRY(c->wind_inc.upload(admm_host::incidence_sell(c->nv, n_tris, 3, tris, n_tris * 4)));
@@ -2790,7 +2773,6 @@ int admm_hip_set_surface_inds(admm_hip_ctx *c, int32_t n, const int32_t *inds) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (int rc = settle(c)) return rc;
-        c->surf_list.release(); c->surf_mask.release();
         c->n_surf = 1;             // (the list itself only serves the dynamic queries, which a component-partitioned context does not run)
         HIP_TRY(c->surf_list.upload(std::vector<int>(1, 0)));
         HIP_TRY(c->surf_mask.upload(std::vector<unsigned char>(c->nv, 0)));
@@ -2901,7 +2883,6 @@ int admm_hip_detect_dynamic(admm_hip_ctx *c, const double *x, int32_t cap, int32
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<double> xd;
     HIP_TRY(xd.alloc(c->n3));
-    struct Free { DevBuf<double> &b; ~Free() { b.release(); } } guard{xd};
     HIP_TRY(hipMemcpyAsync(xd.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (enqueue_dyn_detect(c, xd.p)) return fail(ADMM_HIP_ERR_DEVICE, "detect_dynamic: launch failed");
     std::vector<int> hf(3 * (size_t)c->nv), list;
@@ -2963,7 +2944,6 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     if (timed && c->nt > 0 && c->kernel_clock) {
         const int tsn = 4 * (blocks_for(c->nt) + 4), cap = 2 * admm_iters;
         if (c->lk_tsn != tsn || c->lk_cap < cap) {
-            c->lk_ts.release(); c->lk_out.release();
             HIP_TRY(c->lk_ts.alloc((size_t)cap * 2 * tsn)); HIP_TRY(c->lk_out.alloc(2 * (size_t)cap));
             c->lk_tsn = tsn; c->lk_cap = cap;
             int khz = 0;
@@ -2974,7 +2954,6 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     }
     if (timed && !c->ev_coll0) { HIP_TRY(hipEventCreate(&c->ev_coll0)); HIP_TRY(hipEventCreate(&c->ev_coll1)); }
     HIP_TRY(hipEventRecord(c->ev_step0, st));
-    // counters[5] (closed chunks) must stay monotone across steps: only [0..4] are reset
     c->uz_iters_step = 0; c->uz_detected = false;
     struct InStep { admm_hip_ctx *c; ~InStep() { c->in_step = false; } } in_step_guard{c};
     c->in_step = true;
@@ -2987,19 +2966,19 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     // measured -- frame 3 with four pairs, frame 4 with three -- and the fifth frame starts with the better one (three on a tie within
     // 2 %: they are cheaper).  Three stream synchronisations in the life of a context.
     if (!c->rc_decided && c->linsolver != 1 && c->oc_enabled && c->oc_plan && c->rc_frame >= 3 && c->rc_frame <= 5) {
-        int h[3] = {0, 0, 0};
+        int its = 0;
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h, c->counters.p + 72, sizeof(h), hipMemcpyDeviceToHost));
-        if (c->rc_frame == 3) { c->rc_snap[0] = h[2]; c->rc_pairs = kRc; }
-        else if (c->rc_frame == 4) { c->rc_snap[1] = h[2]; c->rc_pairs = 3; }
+        HIP_TRY(hipMemcpy(&its, c->counters.p + kCntTotalIters, sizeof(its), hipMemcpyDeviceToHost));
+        if (c->rc_frame == 3) { c->rc_snap[0] = its; c->rc_pairs = kRc; }
+        else if (c->rc_frame == 4) { c->rc_snap[1] = its; c->rc_pairs = 3; }
         else {
-            const long long its4 = c->rc_snap[1] - c->rc_snap[0], its3 = h[2] - c->rc_snap[1];
+            const long long its4 = c->rc_snap[1] - c->rc_snap[0], its3 = its - c->rc_snap[1];
             c->rc_pairs = (its4 > 0 && (double)its3 > 1.02 * (double)its4) ? kRc : 3;
             c->rc_decided = true;
         }
     }
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * sizeof(int), st));
-    if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + 7, 0, sizeof(int), st));   // Schur iterations of the persistent launches (uz_persist.hpp)
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, kCntStepWords * sizeof(int), st));
+    if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + kCntSchurIters, 0, sizeof(int), st));
     if (c->wind_n > 0) {   // ExplicitForce::project of the wind, Solver.cpp:54 (before gravity and the prediction)
         hipLaunchKernelGGL(k_wind_tris, dim3(blocks_for(c->wind_n)), dim3(256), 0, st, c->wind_n, c->wind_tris.p, c->x.p, c->v.p,
                            c->wind_dir[0], c->wind_dir[1], c->wind_dir[2], c->dt, c->wind_force.p);
@@ -3045,7 +3024,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     HIP_TRY(hipGetLastError());
     if (timed) {
         HIP_TRY(hipEventSynchronize(c->ev_step1));
-        if (c->h_sig && c->h_sig[2]) return kStepAborted;
+        if (c->h_sig && c->h_sig[kSigAbort]) return kStepAborted;
         std::memset(stats, 0, sizeof(*stats));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev_step0, c->ev_step1));
@@ -3065,27 +3044,27 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         // collision_ms = Collider::detect + constraint rows (Solver.cpp:90-95); it runs inside the global phase here
         stats->collision_ms = c->coll_ms_step;
         stats->global_ms = std::max(0.0, stats->global_ms - c->coll_ms_step);
-        int h[8];
-        HIP_TRY(hipMemcpy(h, c->counters.p, 8 * sizeof(int), hipMemcpyDeviceToHost));
+        int h[kCntRing];
+        HIP_TRY(hipMemcpy(h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
         CgScal sc[2];
         HIP_TRY(hipMemcpy(sc, c->cg_scal.p, sizeof(sc), hipMemcpyDeviceToHost));
         stats->admm_iters = admm_iters;
-        if (c->linsolver == 1) { stats->inner_iters = h[0]; stats->last_solve_converged = h[1] != 0; }   // (the done word carries the stamp of the launch that raised it)
+        if (c->linsolver == 1) { stats->inner_iters = h[kCntIters]; stats->last_solve_converged = h[kCntGsDone] != 0; }   // (the done word carries the stamp of the launch that raised it)
         else if (c->linsolver == 2) {
-            stats->inner_iters = c->uz_iters_step + h[7]; // the reference counts Schur-CG iterations (UzawaCG.hpp:124); h[7]: those of the persistent launches
+            stats->inner_iters = c->uz_iters_step + h[kCntSchurIters]; // the reference counts Schur-CG iterations (UzawaCG.hpp:124)
             stats->n_constraints = c->uz_last_hits;
             stats->last_solve_converged = sc[c->last_launched_iters & 1].converged;
             stats->pcg_launched_iters = c->last_launched_iters;
         }
         else {
-            stats->inner_iters = h[0];
+            stats->inner_iters = h[kCntIters];
             stats->last_solve_converged = sc[c->last_launched_iters & 1].converged;
-            stats->unconverged_solves = admm_iters - h[4];
+            stats->unconverged_solves = admm_iters - h[kCntConverged];
             {   // iterations of the last (up to 64) solves of this step, oldest first
-                int ring[64];
-                HIP_TRY(hipMemcpy(ring, c->counters.p + 8, sizeof(ring), hipMemcpyDeviceToHost));
-                const int n = std::min(admm_iters, 64);
-                for (int i = 0; i < n; ++i) stats->pcg_iters_per_solve[i] = ring[(c->solve_seq - n + 1 + i) & 63];
+                int ring[kCntRingLen];
+                HIP_TRY(hipMemcpy(ring, c->counters.p + kCntRing, sizeof(ring), hipMemcpyDeviceToHost));
+                const int n = std::min(admm_iters, kCntRingLen);
+                for (int i = 0; i < n; ++i) stats->pcg_iters_per_solve[i] = ring[(c->solve_seq - n + 1 + i) & kCntRingMask];
             }
             stats->pcg_launched_iters = c->last_launched_iters;
         }
@@ -3112,7 +3091,7 @@ static hipError_t backup_state(admm_hip_ctx *c) {
 // A timed-out grid barrier was seen after a stream synchronisation: give up the persistent kernel, go back to the last
 // good state and replay.  Single-GPU contexts only (a replay on one rank would issue all-reduces the others do not).
 static int recover_from_abort(admm_hip_ctx *c, admm_hip_stats *stats_of_last) {
-    c->h_sig[2] = 0;
+    c->h_sig[kSigAbort] = 0;
     if (c->world > 1 || c->comm || c->ar_fn)     // a replay on one rank would issue all-reduces the other ranks do not: the step is lost, cleanly
         return fail(ADMM_HIP_ERR_COMM, "PCG: a grid barrier of the on-chip solve timed out on a rank of a multi-GPU job; the step cannot be replayed under a "
                                        "communicator -- restore the state on every rank (admm_hip_set_state) and continue");
@@ -3143,7 +3122,7 @@ static int recover_from_abort(admm_hip_ctx *c, admm_hip_stats *stats_of_last) {
 }
 // after a stream synchronisation: everything issued so far is known to be good, or is replayed
 static int settle(admm_hip_ctx *c) {
-    if (c->h_sig && c->h_sig[2]) return recover_from_abort(c, nullptr);
+    if (c->h_sig && c->h_sig[kSigAbort]) return recover_from_abort(c, nullptr);
     c->pending.clear();
     return ADMM_HIP_OK;
 }
@@ -3251,16 +3230,16 @@ int admm_hip_global_solve(admm_hip_ctx *c, const double *b, double *x_inout, int
     HIP_TRY(hipMemcpyAsync(c->curr.p, x_inout, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
     c->uz_iters_step = 0;
     c->rc_prev_valid = 0; c->rc_prev2_valid = 0; c->rc_frame += 1; c->rc_iter = 0;   // stand-alone solve: nothing to recycle
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * sizeof(int), st));
-    if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + 7, 0, sizeof(int), st));   // Schur iterations of the persistent launches (uz_persist.hpp)
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, kCntStepWords * sizeof(int), st));
+    if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + kCntSchurIters, 0, sizeof(int), st));
     if (launch_global(c, c->b.p, c->curr.p)) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(x_inout, c->curr.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    int h[8];
+    int h[kCntRing];
     HIP_TRY(hipMemcpyAsync(h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_sig && c->h_sig[2]) { c->h_sig[2] = 0; return fail(ADMM_HIP_ERR_DEVICE, "PCG: a grid barrier of the on-chip solve timed out (is another persistent kernel sharing the GPU?)"); }
-    if (iters) *iters = (c->linsolver == 1) ? h[2] : (c->linsolver == 2 ? c->uz_iters_step + h[7] : h[0]);
+    if (c->h_sig && c->h_sig[kSigAbort]) { c->h_sig[kSigAbort] = 0; return fail(ADMM_HIP_ERR_DEVICE, "PCG: a grid barrier of the on-chip solve timed out (is another persistent kernel sharing the GPU?)"); }
+    if (iters) *iters = (c->linsolver == 1) ? h[kCntGsSweeps] : (c->linsolver == 2 ? c->uz_iters_step + h[kCntSchurIters] : h[kCntIters]);
     return ADMM_HIP_OK;
 }
 
@@ -3269,8 +3248,8 @@ int admm_hip_solve_totals(admm_hip_ctx *c, int64_t *solves, int64_t *converged, 
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int rc = settle(c)) return rc;
-    int h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(h, c->counters.p + 72, sizeof(h), hipMemcpyDeviceToHost));
+    int h[kCntTotalsLen] = {};
+    HIP_TRY(hipMemcpy(h, c->counters.p + kCntTotals, sizeof(h), hipMemcpyDeviceToHost));
     const bool counted = (c->oc_enabled && c->oc_plan) || c->big_enabled || (c->linsolver != 1 && !c->oc_enabled && !c->dist_solve && ensure_big_plan(c));     // the on-chip PCG and the launch-path two-level PCG keep these totals
     if (solves) *solves = counted ? h[0] : -1;
     if (converged) *converged = counted ? h[1] : -1;
@@ -3374,7 +3353,6 @@ int admm_hip_set_soft_modes(admm_hip_ctx *c, int32_t k, const double *Z) {
         }
         G = inv;
     }
-    c->defl_Z.release(); c->defl_Ginv.release(); c->defl_part.release(); c->defl_y.release();
     HIP_TRY(c->defl_Z.upload(std::vector<double>(Z, Z + (size_t)k * nv)));
     HIP_TRY(c->defl_Ginv.upload(G));
     HIP_TRY(c->defl_part.alloc((size_t)3 * k * c->NB)); HIP_TRY(c->defl_y.alloc((size_t)3 * k));
@@ -3383,7 +3361,6 @@ int admm_hip_set_soft_modes(admm_hip_ctx *c, int32_t k, const double *Z) {
         std::vector<float> Zi((size_t)k * c->oc_rows, 0.0f);      // [mode][internal row] (pcg_onchip2.hpp)
         for (int q = 0; q < k; ++q)
             for (int r = 0; r < c->oc_rows; ++r) { const int v = c->oc_orig_h[r]; if (v >= 0) Zi[(size_t)q * c->oc_rows + r] = (float)Z[(size_t)q * nv + v]; }
-        c->defl_Zint.release(); c->defl_rec.release();
         HIP_TRY(c->defl_Zint.upload(Zi));
         HIP_TRY(c->defl_rec.alloc((size_t)2 * 3 * kOc2DeflMax * c->oc_G)); HIP_TRY(c->defl_rec.zero());
         c->defl_fused = true;
@@ -3441,11 +3418,20 @@ int admm_hip_compute_soft_modes(admm_hip_ctx *c, int32_t k, int32_t iters) {
     int rcode = ADMM_HIP_OK;
     // The solves below are not the scene's: from the second round on their right-hand sides are (nearly) eigenvectors, CG ends after one or two steps
     // and runs on into rounding noise, where the recurrences' r . u can turn negative -- which k_pcg2 reads as "the preconditioner is not positive
-    // definite" and answers by giving up its block smoother FOR THE CONTEXT (counters[75]).  Until round 6 that is what happened to every context
+    // definite" and answers by giving up its block smoother FOR THE CONTEXT (kCntSmootherOff).  Until round 6 that is what happened to every context
     // that computed its modes here: the bench body ran its ADMM loop with S = D^-1 (ADMM_HIP_OC_CHEB=0 and =2 gave the same 8.675 iterations per
-    // solve).  What these solves find out about the context (smoother given up, short-pass trust revoked) is put back afterwards.
-    int found0[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(found0, c->counters.p + 75, sizeof(found0), hipMemcpyDeviceToHost));
+    // solve).  What these solves find out about the context (kCntFindings) is put back on every way out, once the stream has drained.
+    int found0[kCntFindingsLen] = {};
+    HIP_TRY(hipMemcpy(found0, c->counters.p + kCntFindings, sizeof(found0), hipMemcpyDeviceToHost));
+    struct PutBack {
+        admm_hip_ctx *c; const int *w;
+        hipError_t put() {
+            const hipError_t e = hipStreamSynchronize(c->stream), e2 = hipMemcpy(c->counters.p + kCntFindings, w, kCntFindingsLen * sizeof(int), hipMemcpyHostToDevice);
+            c = nullptr;
+            return e != hipSuccess ? e : e2;
+        }
+        ~PutBack() { if (c) (void)put(); }
+    } put_back{c, found0};
     for (int it = 0; it < iters && rcode == ADMM_HIP_OK; ++it) {
         if (!mgs(X)) { rcode = fail(ADMM_HIP_ERR_DEVICE, "compute_soft_modes: the subspace collapsed"); break; }
         for (int c0 = 0; c0 < k3 && rcode == ADMM_HIP_OK; c0 += 3) {      // Y = K^-1 X, three columns = the three axes of one solve
@@ -3454,7 +3440,7 @@ int admm_hip_compute_soft_modes(admm_hip_ctx *c, int32_t k, int32_t iters) {
                 hipMemsetAsync(dx.p, 0, col3.size() * sizeof(double), c->stream) != hipSuccess) { rcode = fail(ADMM_HIP_ERR_DEVICE, "compute_soft_modes: copy failed"); break; }
             if (launch_pcg(c, db.p, dx.p, std::max(c->pcg_max_iters, 2000))) { rcode = fail(ADMM_HIP_ERR_DEVICE, "compute_soft_modes: the solve failed"); break; }
             if (hipMemcpyAsync(col3.data(), dx.p, col3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rcode = fail(ADMM_HIP_ERR_DEVICE, "compute_soft_modes: copy failed"); break; }
-            if (c->h_sig && c->h_sig[2]) { rcode = recover_from_abort(c, nullptr); if (rcode == ADMM_HIP_OK) { c0 -= 3; } continue; }
+            if (c->h_sig && c->h_sig[kSigAbort]) { rcode = recover_from_abort(c, nullptr); if (rcode == ADMM_HIP_OK) { c0 -= 3; } continue; }
             for (int v = 0; v < nv; ++v) for (int j = 0; j < 3; ++j) if (c0 + j < k3) Y[(size_t)(c0 + j) * nv + v] = col3[3 * (size_t)v + j];
         }
         if (rcode != ADMM_HIP_OK) break;
@@ -3501,9 +3487,7 @@ int admm_hip_compute_soft_modes(admm_hip_ctx *c, int32_t k, int32_t iters) {
             }
         }
     }
-    db.release(); dx.release();
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->counters.p + 75, found0, sizeof(found0), hipMemcpyHostToDevice));
+    HIP_TRY(put_back.put());
     if (rcode != ADMM_HIP_OK) return rcode;
     c->rc_iter = 0; c->rc_prev_valid = 0; c->rc_prev2_valid = 0;      // (the recycled basis of the ADMM loop starts clean)
     return admm_hip_set_soft_modes(c, k, X.data());
@@ -3547,11 +3531,17 @@ int admm_hip_pcg_findings(admm_hip_ctx *c, int32_t *smoother_given_up, int32_t *
     if (!c) return fail(ADMM_HIP_ERR_ARG, "pcg_findings: NULL context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(h, c->counters.p + 75, sizeof(h), hipMemcpyDeviceToHost));
+    int h[kCntFindingsLen] = {};
+    HIP_TRY(hipMemcpy(h, c->counters.p + kCntFindings, sizeof(h), hipMemcpyDeviceToHost));
     if (smoother_given_up) *smoother_given_up = h[0] != 0;
     if (trust_revoked) *trust_revoked = h[1] != 0;
     if (failed_checks) *failed_checks = h[2];
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_device_buffers(int64_t *buffers, int64_t *bytes) {
+    if (buffers) *buffers = g_dev_buffers;
+    if (bytes) *bytes = g_dev_bytes;
     return ADMM_HIP_OK;
 }
 int admm_hip_probe_sync(admm_hip_ctx *c, int32_t n, double *us_all_to_all, double *us_exchange, int64_t *plan_stats) {
@@ -3585,7 +3575,7 @@ int admm_hip_probe_sync(admm_hip_ctx *c, int32_t n, double *us_all_to_all, doubl
         out[slot] = 1e3 * (double)ms / (double)n;
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (c->h_sig && c->h_sig[2]) { c->h_sig[2] = 0; return fail(ADMM_HIP_ERR_DEVICE, "probe_sync: a grid barrier timed out"); }
+    if (c->h_sig && c->h_sig[kSigAbort]) { c->h_sig[kSigAbort] = 0; return fail(ADMM_HIP_ERR_DEVICE, "probe_sync: a grid barrier timed out"); }
     if (us_all_to_all) *us_all_to_all = out[0];
     if (us_exchange) *us_exchange = out[1];
     return ADMM_HIP_OK;
@@ -3874,7 +3864,7 @@ int admm_hip_uzawa_cache_stats(admm_hip_ctx *c, int64_t *columns, int64_t *colum
         int dev = 0;      // the persistent Schur launches count on the device
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(&dev, c->counters.p + 78, sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&dev, c->counters.p + kCntSchurProducts, sizeof(int), hipMemcpyDeviceToHost));
         *schur_from_columns = c->uzc_applies + dev;
     }
     if (schur_by_pcg) *schur_by_pcg = c->uzc_pcg_solves;

@@ -20,7 +20,7 @@
 //     (Measured and dropped in the same session: two or three polls of a granule in flight at a time -- the wait is the neighbours' stores
 //     draining, not the sampling instant: -1 % / -8 %; one granule per lane behind a block barrier -- 4 460 on the cube.)
 //   * a consumer polls exactly the granules of its halo entries of that colour (sc1 loads), with bounded spins: a hand-off that
-//     cannot complete aborts the solve (sig[2]) instead of hanging the GPU;
+//     cannot complete aborts the solve (kSigAbort) instead of hanging the GPU;
 //   * two outbox slots per node alternate between sweeps (a block can run at most one sweep ahead of a neighbour: it needs the
 //     neighbour's values of every sweep), four slots for the per-sweep residual partials;
 //   * no grid barrier anywhere on the normal path.
@@ -61,8 +61,8 @@ struct GspArgs {
     v4u *part;                                                // [G][4 sweep slots][2] granules: |r|^2, |b|^2 of the block
     v4u *meet;                                                // [G] granules: the blocks' rendez-vous before a replay
     unsigned *abort_word;                                     // raised by the first block that gives up
-    int *done, *sweeps, *total;                               // counters[1], [2], [0] of the context (as the colour kernels)
-    int *sig;                                                 // host-visible: sig[2] = 1 when the solve was aborted
+    int *done, *sweeps, *total;                               // the context's counters (kernels.hpp: kCntGsDone, kCntGsSweeps, kCntIters)
+    int *sig;                                                 // the signal words (kernels.hpp: kSigAbort)
     const Obstacles *ob;                                      // passive obstacles (device copy: 80 SGPRs as a by-value argument)
     unsigned long long *prof; int prof_block;                 // diagnosis (ADMM_HIP_GSP_PROF=1): wall-clock ticks per part of a phase
     unsigned long long *proj;                                 // rows projected onto a passive obstacle since create (admm_hip_contact_totals)
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
         // a solve of this context has been given up and the host has not recovered yet (steps are issued asynchronously): nothing may
         // run on that state -- every later launch leaves at once, the host replays them after its next synchronisation
         ctl[0] = __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
-        if (ctl[0]) __hip_atomic_store(a.sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (ctl[0]) __hip_atomic_store(a.sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
     if (ctl[0]) return;
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
 
     auto give_up = [&]() {      // (one thread) tell everybody, and the host
         __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     };
     auto poll_failed = [&](unsigned &spins) -> bool {   // one more unsuccessful poll: give up?
         if (++spins > kGspSpin || ((spins & 127u) == 0u && __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {

@@ -22,6 +22,40 @@ namespace admm_k {
 
 using namespace admm_dev;
 
+// ---- counters and signal words: the one layout the host (admm_hip.hip) and every kernel share ----
+// counters: kCntWords ints per context, zeroed at create; a column lane of UzawaCG has a copy of its own.
+constexpr int kCntIters = 0;           // inner iterations of the step: PCG iterations, GS sweeps whose test failed
+constexpr int kCntGsDone = 1;          // GS: nonzero once the solve's residual test passed
+constexpr int kCntGsSweeps = 2;        // GS: sweeps of the solve whose test failed
+constexpr int kCntMaxIters = 3;        // most iterations one PCG solve of the step needed
+constexpr int kCntConverged = 4;       // PCG solves of the step that met their tolerance
+constexpr int kCntStepWords = 5;       // [0, kCntStepWords): the per-step words, reset by step_impl and admm_hip_global_solve
+constexpr int kCntChunks = 5;          // chunks closed by the launch-per-iteration PCGs (mirrored to kSigChunks): monotone, never reset
+constexpr int kCntHits = 6;            // UzawaCG: constraint rows found by the detect phase of the solve
+constexpr int kCntSchurIters = 7;      // UzawaCG: Schur iterations of the step's persistent launches (k_uz_persist), reset per step
+constexpr int kCntRing = 8;            // ring of the iteration counts of the last kCntRingLen solves: solve seq at kCntRing + (seq & kCntRingMask)
+constexpr int kCntRingLen = 64;
+constexpr int kCntRingMask = kCntRingLen - 1;
+constexpr int kCntTotals = kCntRing + kCntRingLen;   // totals since create (on-chip and launch-path two-level PCG, admm_hip_solve_totals):
+constexpr int kCntSolves = kCntTotals + 0;           //   solves
+constexpr int kCntSolvesConverged = kCntTotals + 1;  //   solves that met their tolerance
+constexpr int kCntTotalIters = kCntTotals + 2;       //   iterations
+constexpr int kCntTotalsLen = 3;
+constexpr int kCntFindings = kCntTotals + kCntTotalsLen;   // what k_pcg2 found out about the context (admm_hip_pcg_findings):
+constexpr int kCntSmootherOff = kCntFindings + 0;    //   the block smoother was given up for good
+constexpr int kCntTrustRevoked = kCntFindings + 1;   //   the trust in a short first pass was revoked for good
+constexpr int kCntFailedChecks = kCntFindings + 2;   //   sampled verifications of a short first pass that failed
+constexpr int kCntFindingsLen = 3;
+constexpr int kCntSchurProducts = kCntFindings + kCntFindingsLen;   // Schur products S d of the persistent launches since create (k_uz_persist)
+constexpr int kCntWords = 80;          // (the last word is spare)
+static_assert(kCntSchurProducts < kCntWords, "counters layout");
+// signal words: kSigWords ints of pinned, device-mapped host memory per context (h_sig; d_sig is the device alias)
+constexpr int kSigConverged = 0;       // sequence number of the last solve that converged
+constexpr int kSigChunks = 1;          // chunks closed so far (the host waits on it before it looks at kSigConverged)
+constexpr int kSigAbort = 2;           // a persistent launch gave up a grid barrier or hand-off: the host takes the recovery path
+constexpr int kSigConvIter = 3;        // iteration at which the last converged solve of the two-level PCG converged (stored before kSigConverged)
+constexpr int kSigWords = 4;
+
 struct Mat { double mu, la, k, kappa; int type, table; };   // KIND 4: type 0..2 = xu:: spline with a compression term kappa; type 3 = tabulated (user-defined) spline `table`; type 4 = stable Neo-Hookean
 
 constexpr int kMaxObst = 8;
@@ -864,8 +898,8 @@ __global__ __launch_bounds__(256) void k_cg_vec(int it, int nv, int NB, const do
     const CgScal pv = *prev;
     // progress mark for the host (pinned memory): the chunk this kernel closes has (almost) drained
     if (mark_here && blockIdx.x == 0 && threadIdx.x == 0) {
-        const int m = atomicAdd(total_iters + 5, 1) + 1;
-        __hip_atomic_store(sig + 1, m, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        const int m = atomicAdd(total_iters + kCntChunks, 1) + 1;
+        __hip_atomic_store(sig + kSigChunks, m, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (it > 0 && pv.converged) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *next = pv;
@@ -906,10 +940,10 @@ __global__ __launch_bounds__(256) void k_cg_vec(int it, int nv, int NB, const do
             for (int a = 0; a < 3; ++a) { o.gamma[a] = q[a]; o.gamma_b[a] = gb[a]; o.alpha[a] = 0.0; }
             o.converged = 1;
             *next = o;
-            atomicAdd(total_iters + 4, 1);        // solves that met the residual test
-            atomicMax(total_iters + 3, o.iters);  // most iterations any solve of this step needed
-            total_iters[8 + (pv.seq & 63)] = o.iters; // per-solve log (ring of 64)
-            __hip_atomic_store(sig, pv.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); // tell the host
+            atomicAdd(total_iters + kCntConverged, 1);
+            atomicMax(total_iters + kCntMaxIters, o.iters);
+            total_iters[kCntRing + (pv.seq & kCntRingMask)] = o.iters;
+            __hip_atomic_store(sig + kSigConverged, pv.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); // tell the host
         }
         return;
     }
@@ -931,7 +965,7 @@ __global__ __launch_bounds__(256) void k_cg_vec(int it, int nv, int NB, const do
         o.iters = (it == 0 ? 0 : pv.iters) + 1;
         o.seq = pv.seq; o.pad_ = 0;
         *next = o;
-        atomicAdd(total_iters, 1);
+        atomicAdd(total_iters + kCntIters, 1);
     }
     if (!live) return;
     if (v < row_lo || v >= row_hi) {      // distributed solve: another rank's row -- only its u is cleared, for the all-reduce that assembles u

@@ -79,7 +79,7 @@ __device__ __forceinline__ bool oc_barrier(unsigned *bar, unsigned epoch, int G,
             if (++spins > kOcSpinLimit || __any(lane == 8 && v != 0u)) {
                 if (lane == 0) {
                     __hip_atomic_store(bar + 16 * 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 ok = 0;
                 break;
@@ -116,7 +116,7 @@ __device__ __forceinline__ bool oc_announce_and_wait_neighbours(unsigned *bar, u
             if (++spins > kOcSpinLimit || ((spins & 255u) == 0u && __hip_atomic_load(bar + 16 * 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
                 if (lane == 0) {
                     __hip_atomic_store(bar + 16 * 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 ok = 0;
                 break;
@@ -143,7 +143,7 @@ __device__ __forceinline__ bool oc_barrier_wait(unsigned *bar, unsigned epoch, i
             if (++spins > kOcSpinLimit || __any(lane == 8 && v != 0u)) {
                 if (lane == 0) {
                     __hip_atomic_store(bar + 16 * 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 ok = 0;
                 break;

@@ -31,7 +31,7 @@ struct BigArgs {
     double *cvec;                                 // [3][ncp]: c = P^T r
     double *rho;                                  // [3][G]: r.D^-1 r per aggregate
     CgScal *scal;                                 // two slots, alternating by iteration parity
-    int *counters; int *sig;
+    int *counters; int *sig;                      // layouts: kernels.hpp (kCnt*, kSig*)
     double tol2; int seq;
     int row_lo, row_hi;                           // distributed solve: the internal rows this rank owns (aggregate-aligned)
 };
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(kBigVecT) void k_big_vec(BigArgs a, int it, int mar
     const CgScal pv = a.scal[entry ? 0 : (it & 1)];
     CgScal *next = a.scal + (entry ? 0 : ((it + 1) & 1));
     if (mark_here && blockIdx.x == 0 && threadIdx.x == 0) {      // progress mark for the host: the chunk this kernel closes has (almost) drained
-        const int m = atomicAdd(a.counters + 5, 1) + 1;
-        __hip_atomic_store(a.sig + 1, m, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        const int m = atomicAdd(a.counters + kCntChunks, 1) + 1;
+        __hip_atomic_store(a.sig + kSigChunks, m, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (!entry && pv.converged) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *next = pv;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(kBigVecT) void k_big_vec(BigArgs a, int it, int mar
                 for (int j = 0; j < 3; ++j) { o.gamma[j] = q[j]; o.alpha[j] = alpha[j]; }
                 o.converged = 0; o.iters = pv.iters + 1;
                 *next = o;
-                atomicAdd(a.counters, 1);
+                atomicAdd(a.counters + kCntIters, 1);
             }
         }
     }
@@ -316,12 +316,12 @@ __global__ __launch_bounds__(kBigVecT) void k_big_coarse(BigArgs a, int it) {
     if (conv) {
         if (g == 0 && threadIdx.x == 0) {
             cur->converged = 1;
-            atomicAdd(a.counters + 4, 1);
-            atomicMax(a.counters + 3, sc.iters);
-            a.counters[8 + (sc.seq & 63)] = sc.iters;
-            __hip_atomic_store(a.sig + 3, sc.iters, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);      // (the iteration it converged at: the distributed solve's ranks stop at the same chunk)
-            atomicAdd(a.counters + 73, 1);      // converged solves since create (admm_hip_solve_totals; solves and iterations: k_big_scatter)
-            __hip_atomic_store(a.sig, sc.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            atomicAdd(a.counters + kCntConverged, 1);
+            atomicMax(a.counters + kCntMaxIters, sc.iters);
+            a.counters[kCntRing + (sc.seq & kCntRingMask)] = sc.iters;
+            __hip_atomic_store(a.sig + kSigConvIter, sc.iters, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);      // (the iteration it converged at: the distributed solve's ranks stop at the same chunk)
+            atomicAdd(a.counters + kCntSolvesConverged, 1);      // (solves and iterations: k_big_scatter)
+            __hip_atomic_store(a.sig + kSigConverged, sc.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         return;
     }
@@ -373,8 +373,8 @@ __global__ __launch_bounds__(256) void k_big_if_unpack(BigArgs a, const int *__r
 __global__ __launch_bounds__(256) void k_big_scatter(BigArgs a, int final_slot) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {      // totals since create; a solve that ran out of iterations is logged here (a converged one: k_big_coarse)
         const CgScal sc = a.scal[final_slot];
-        atomicAdd(a.counters + 72, 1); atomicAdd(a.counters + 74, sc.iters);
-        if (!sc.converged) { atomicMax(a.counters + 3, sc.iters); a.counters[8 + (sc.seq & 63)] = sc.iters; }
+        atomicAdd(a.counters + kCntSolves, 1); atomicAdd(a.counters + kCntTotalIters, sc.iters);
+        if (!sc.converged) { atomicMax(a.counters + kCntMaxIters, sc.iters); a.counters[kCntRing + (sc.seq & kCntRingMask)] = sc.iters; }
     }
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= a.n_rows) return;

@@ -67,7 +67,7 @@ struct Oc2Args {
     double *part;                    // [2][8][G] per-block partial sums, double-buffered by barrier parity
     unsigned *bar;                   // barrier words (see oc_sync.hpp)
     const int *nbr; unsigned long long *flags;
-    int *counters; CgScal *scal; int *sig;
+    int *counters; CgScal *scal; int *sig;   // layouts: kernels.hpp (kCnt*, kSig*)
     unsigned long long *prof; int prof_block;
     int spb, G, max_iters, seq;
     double tol2;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     if (blockIdx.x == 0 && tid < 9) a.bar[32 * 16 * ((a.seq & 1) ^ 1) + 16 * (tid < 8 ? tid : 17)] = 0u;
     if (a.skip && *a.skip) return;    // (after the clearing above: the next launch counts on the set this one cleared)
     if (tid < 3 * kOcSubK) { yw[tid] = 0.0; yw[3 * kOcSubK + tid] = 0.0; yz[tid] = 0.0; ycur[tid] = 0.0; }
-    if (tid == 0) ictl[3] = a.counters[76];      // trust revoked for this context (a SAMPLED verification of a short first pass failed: below)
+    if (tid == 0) ictl[3] = a.counters[kCntTrustRevoked];      // (a SAMPLED verification of a short first pass failed: below)
     int ywp = 0;         // offset of the current y_w buffer (0 or 3 kOcSubK)
     unsigned ph = 0;     // publish phase of the vector: buffer parity = ph & 1, tag of the neighbour flags
     unsigned be = 0;     // grid-barrier epoch (arrivals of this block so far); record parity = be & 1
@@ -279,10 +279,10 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     // S v = D^-1 (sm_ab v - sm_b offdiag(A_bb) D^-1 v): D^-1 v goes into the local vector with the halo part zeroed, the
     // ordinary row loop does the rest.  S is symmetric positive definite as long as lambda_max(D^-1 A_bb) stays below the
     // bound the host derived the coefficients from (oc_plan.cpp: power iteration + margin).
-    // (counters[75]: set for good by a solve whose pipelined pass broke off with non-finite or negative sums -- the sign of a
+    // (kCntSmootherOff: set for good by a solve whose pipelined pass broke off with non-finite or negative sums -- the sign of a
     // preconditioner that is not positive definite, e.g. a bound of the smoother's interval that was too low; later solves of the
     // context then run with S = D^-1)
-    const bool smoothing = a.sm_b != 0.0 && __builtin_amdgcn_readfirstlane(a.counters[75]) == 0;
+    const bool smoothing = a.sm_b != 0.0 && __builtin_amdgcn_readfirstlane(a.counters[kCntSmootherOff]) == 0;
     auto smooth = [&](const double *v, double *out) {
         if (!smoothing) {
 #pragma unroll
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                 // test_short_pass_needs_no_verification).  Tighter tolerances, later passes (they start after a FAILED verification),
                 // floor-limited targets and ADMM_HIP_OC_VERIFY=1 verify as before.
                 // The rule is an estimate, so it is CHECKED: the host withholds the trust from every 16th solve (and a context's first 40); if such
-                // a solve's short first pass then fails its verification, block 0 revokes the trust for the context (counters[76]) and every later
+                // a solve's short first pass then fails its verification, block 0 revokes the trust for the context (kCntTrustRevoked) and every later
                 // solve verifies.  (A 1 k-vertex body at pcg_tol 1e-10: unverified 5e-6 from the 1e-13 trajectory after eight frames, verified 8e-9
                 // -- experiments/r05_small_body_accuracy.py; the 1 M-tet bench body never fails one: its trajectory is bit-identical either way.)
                 const bool trusted = a.trust_short && ictl[3] == 0 && passes == 0 && a.tol2 >= kOc2TrustTol2 && target == kOcTrig * a.tol2;
@@ -836,7 +836,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                     }
                     const int act = action();
                     if (act == 2) {
-                        if (blockIdx.x == 0 && otid() == 0 && smoothing) a.counters[75] = 1;
+                        if (blockIdx.x == 0 && otid() == 0 && smoothing) a.counters[kCntSmootherOff] = 1;
                         entry_restart = true; go_classic = true; break;
                     }
                     if (act == 4) {                  // converged by the recursive residual of a short first pass: no verification
@@ -848,7 +848,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         const int v = verify();      // leaves u = D^-1 (true residual)
                         if (v < 0) { aborted = true; break; }
                         if (v == 1) { conv = true; break; }
-                        if (passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[76] = 1; atomicAdd(a.counters + 77, 1); }
+                        if (passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[kCntTrustRevoked] = 1; atomicAdd(a.counters + kCntFailedChecks, 1); }
                         fresh = true;                // the true residual replaces the recursive one: beta = 0
                         if (++passes >= 4) { go_classic = true; break; }
                         pass_start = 3.0 * ctl[1];   // (the largest axis ratio of the verification, as a bound of the sum)
@@ -1122,14 +1122,14 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         o.alpha[0] = (double)ictl[1]; o.alpha[1] = (double)be; o.alpha[2] = ctl[1] / a.tol2;
         o.converged = (conv && !aborted) ? 1 : 0; o.iters = iters; o.seq = a.seq; o.pad_ = pipe_iters;
         a.scal[0] = o;
-        atomicAdd(a.counters, iters);
+        atomicAdd(a.counters + kCntIters, iters);
         if (o.converged) {
-            atomicAdd(a.counters + 4, 1);
-            atomicMax(a.counters + 3, iters);
-            a.counters[8 + (a.seq & 63)] = iters;
+            atomicAdd(a.counters + kCntConverged, 1);
+            atomicMax(a.counters + kCntMaxIters, iters);
+            a.counters[kCntRing + (a.seq & kCntRingMask)] = iters;
         }
         // totals since admm_hip_create (never reset: admm_hip_solve_totals)
-        atomicAdd(a.counters + 72, 1); atomicAdd(a.counters + 73, o.converged); atomicAdd(a.counters + 74, iters);
+        atomicAdd(a.counters + kCntSolves, 1); atomicAdd(a.counters + kCntSolvesConverged, o.converged); atomicAdd(a.counters + kCntTotalIters, iters);
     }
     if (prof) a.prof[63 * 8 + 4] = wall_clock64();     // (the profiled block's own epilogue)
 }

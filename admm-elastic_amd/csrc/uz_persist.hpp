@@ -14,7 +14,7 @@
 //     (one hand-off instead of two; a typical Schur iteration shrinks |r|^2 by ~10x, so the cancellation costs one digit of sixteen;
 //     a step that shrinks it by more than 1e3 -- small active sets -- forms both from the updated r in a second round instead);
 //   * x is not touched: x = x0 - A^-1 C^T (y - y0) is applied once after the loop (launch_uzawa), as with the two-launch iterations;
-//   * every poll is bounded: a hand-off that cannot complete raises the abort word and sig[2], the host takes the recovery path;
+//   * every poll is bounded: a hand-off that cannot complete raises the abort word and kSigAbort, the host takes the recovery path;
 //   * the host does not wait for the launch: the stop verdict stays on the device, the iteration count goes to a device counter.
 // Rows that couple several vertices (dynamic rows: hit vertex + the three vertices of a face) run the same kernel: the host lists the
 // ROW vertices and k_uzc_schur (kernels.hpp) forms S on them from the active x active block of K^-1.  At most 1024 rows.
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kUzpT) void k_uz_persist(UzpArgs a) {
     const bool row_on = i < n, leader = row_on && l == 0;
     if (t == 0) {
         ctl[0] = __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
-        if (ctl[0]) __hip_atomic_store(a.sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (ctl[0]) __hip_atomic_store(a.sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
     if (ctl[0] || a.sc->stop) return;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kUzpT) void k_uz_persist(UzpArgs a) {
             if (!ctl[0]) {
                 ctl[0] = 1;
                 __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a.sig + 2, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(a.sig + kSigAbort, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             return true;
         }

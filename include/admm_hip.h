@@ -328,6 +328,10 @@ int admm_hip_persistent_launches(const admm_hip_ctx *ctx, int64_t *pcg, int64_t 
  * they switched the smoother off for every context that computed its modes).  Synchronises the stream. */
 int admm_hip_pcg_findings(admm_hip_ctx *ctx, int32_t *smoother_given_up, int32_t *trust_revoked, int64_t *failed_checks);
 
+/* Device memory the library holds in this process (no reference counterpart; diagnostics, tests): the number of live device buffers of all
+ * contexts and their total size in bytes.  A destroyed context leaves none of its own behind.  Any pointer may be NULL. */
+int admm_hip_device_buffers(int64_t *buffers, int64_t *bytes);
+
 /* Diagnostics of the on-chip PCG (linsolver 0 / 2; no reference counterpart): the latency floor of the two
  * synchronisations one CG iteration consists of, measured on this context's grid with the kernel's own primitives and
  * payloads but no arithmetic, as microseconds per repetition over n repetitions: the all-to-all (block record -> grid barrier

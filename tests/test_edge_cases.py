@@ -325,3 +325,66 @@ def test_solver_params_after_initialize():
     for _ in range(2):
         a.step(); b.step()
     assert scenes.rel_err(a.m_x, b.m_x) < 1e-10
+
+
+@pytest.mark.gpu
+def test_closed_contexts_leave_no_device_buffers(monkeypatch):
+    """Every device buffer of a context is freed with it (admm_hip_device_buffers: the live buffers of the process).  Contexts that
+    between them reach every kind of buffer are created, stepped and closed; the count and the bytes then return to where they were.
+    (While the context freed its buffers from a list kept by hand, the tets' rest positions and the persistent Schur launch's boxes
+    stayed behind.)"""
+    import ctypes as C
+    import gc
+
+    def live():
+        gc.collect()                       # (Solver objects of earlier tests that are still waiting for collection)
+        n, b = C.c_int64(0), C.c_int64(0)
+        capi.check(capi.lib().admm_hip_device_buffers(C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    before = live()
+    # on-chip PCG cube: rest positions of the tets, soft modes
+    s = scenes.cube_scene(5, pkg.TET_NEOHOOKEAN, admm_iters=4, linsolver=0).make_solver(pcg_tol=1e-10, pcg_max_iters=500)
+    assert s.tet_rest_mode() != 0
+    s.compute_soft_modes(6)
+    s.step(); s.step()
+    assert s.persistent_launches()["pcg"] > 0 and live()[0] > before[0]
+    s.close()
+    # launch-per-iteration PCG
+    monkeypatch.setenv("ADMM_HIP_PCG_LAUNCHES", "1")
+    s = scenes.cube_scene(4, pkg.TET_STVK, admm_iters=4, linsolver=0).make_solver()
+    monkeypatch.delenv("ADMM_HIP_PCG_LAUNCHES")
+    s.step(); s.close()
+    # UzawaCG with floor contact: column lanes, column cache, persistent Schur launch
+    sc = scenes.cube_scene(12, pkg.TET_NEOHOOKEAN, pin_face=False, admm_iters=8, linsolver=2, size=0.5)
+    sc.obstacles.append((0, [0.03, 0.0, 0.0, 0.0]))
+    rng = np.random.default_rng(3)
+    x = sc.x.copy(); x[:, 1] -= 0.02 + 0.03 * rng.random(len(x)); x = x.ravel()
+    s = sc.make_solver(pcg_tol=1e-12, pcg_max_iters=400)
+    s.global_solve(sc.make_oracle(mode=1).A @ x, x)
+    st = s.uzawa_cache_stats()
+    assert st["lanes"] >= 2 and st["columns"] > 100 and s.persistent_launches()["schur"] > 0, st
+    s.step(); s.close()
+    # GS cloth on a floor
+    s = scenes.cloth_scene(8, floor=0.45, admm_iters=4, linsolver=1).make_solver()
+    for _ in range(3):
+        s.step()
+    s.close()
+    # dynamic tet-mesh collision, on the GS and on the UzawaCG path
+    for ls in (1, 2):
+        s = scenes.two_blocks_scene(3, linsolver=ls).make_solver()
+        assert len(s.detect_dynamic()) > 0
+        s.step(); s.close()
+    # wind, surface indices and pin normals, each set twice
+    sc = scenes.cloth_scene(6, limits=None, admm_iters=2, linsolver=0)
+    sc.slides[3] = (sc.x[3].copy(), np.array([0.0, 1.0, 0.0]))
+    s = sc.make_solver()
+    _, tris, _, _ = sc.tris[0]
+    for sel, inds, nrm in ((tris[::2], [1, 2, 3], [0.0, 1.0, 0.0]), (tris[1::3], [4, 5, 6, 7, 8], [1.0, 1.0, 0.0])):
+        s.set_wind(sel, [1.5, -0.2, 0.7])
+        si = capi.i32(inds)
+        capi.check(capi.lib().admm_hip_set_surface_inds(s._ctx, len(si), capi.iptr(si)))
+        s.set_slide_pins([3], [sc.x[3]], [nrm])
+        s.step()
+    s.close()
+    assert live() == before

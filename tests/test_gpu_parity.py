@@ -1112,7 +1112,7 @@ def test_short_pass_needs_no_verification(monkeypatch):
 
 def test_trust_rule_is_checked_on_a_sample_and_revoked_when_a_check_fails(monkeypatch):
     """The short-pass trust rule is an estimate: every 16th solve (and a context's first 40) verifies whatever it says, and a failed check
-    revokes the trust for the context (pcg_onchip2.hpp, counters[76]).  A 1 k-vertex swaying body at pcg_tol 1e-10 is the case it was built
+    revokes the trust for the context (pcg_onchip2.hpp, kCntTrustRevoked).  A 1 k-vertex swaying body at pcg_tol 1e-10 is the case it was built
     for: believed unverified, its solves stop early (5e-6 from the 1e-13 trajectory after eight frames); with the check it lands where the
     always-verifying run lands (8e-9).  experiments/r05_small_body_accuracy.py."""
     sc = scenes.blob_scene(20, admm_iters=10, linsolver=0)
