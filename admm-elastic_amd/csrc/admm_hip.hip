@@ -22,6 +22,7 @@
 #include "../../include/admm_hip.h"
 #include "host_setup.hpp"
 #include "kernels.hpp"
+#include "monitor.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
 #include "gs_persist.hpp"
@@ -369,6 +370,12 @@ struct admm_hip_ctx {
     DevBuf<DynHit> gsd_hits; DevBuf<unsigned char> gsd_skip; DevBuf<double> gsd_part;
     DevBuf<int> gsd_int; DevBuf<double> gsd_dbl; DevBuf<int4> gsd_hnode;
     int gsd_last_hits = 0;
+    // energy / ADMM monitor (monitor.hpp; admm_hip_energy, admm_hip_residuals, admm_hip_set_monitor).  h_kst, pin_vert_d: rest data only the
+    // monitor reads (the hinges' stiffness, pin term -> vertex), uploaded at create; everything else is allocated by the first call that needs it
+    int mon_mode = 0, mon_n = 0;      // mode in effect from the next step; records the last step wrote
+    DevBuf<double> h_kst; DevBuf<int> pin_vert_d;
+    DevBuf<double> mon_tzp, mon_rzp, mon_hzp, mon_pzp, mon_pz6;   // z_prev per family (pins: room for the reference's 6 rows), pin z in the reference's row layout
+    DevBuf<double> mon_part, mon_rec, mon_out, mon_term;          // block partials, records [admm_iters][8], one result [8], per-term energies
 
     ~admm_hip_ctx() {      // (every DevBuf member, lane and dynamic collider frees its own memory after this body)
         (void)hipSetDevice(device);
@@ -463,6 +470,64 @@ template <bool WRITE_Z>
 void launch_local(admm_hip_ctx *c) {      // Binv recomputed from the rest positions / streamed: decided once, in admm_hip_create
     if (c->tet_rest_mode) launch_local_impl<WRITE_Z, true>(c);
     else launch_local_impl<WRITE_Z, false>(c);
+}
+
+// ---- energy / ADMM monitor (monitor.hpp) ----
+// single-GPU contexts only: a rank of a multi-GPU job holds a part of the terms (element blocks) or of the bodies (components)
+bool monitor_allowed(const admm_hip_ctx *c) { return c->world == 1 && !c->comm && !c->ar_fn && !c->cm.on; }
+int mon_blocks(const admm_hip_ctx *c, bool nodes) {
+    return blocks_for(c->nt) + blocks_for(c->ntri) + blocks_for(c->nbend) + blocks_for(c->npin_terms) + (nodes ? blocks_for(c->n3) : 0);
+}
+// buffers of the monitor, allocated by the first call that needs them: block partials and the result always, z_prev / the per-term
+// energies on demand
+hipError_t mon_ensure(admm_hip_ctx *c, bool zprev, bool term) {
+    hipError_t e;
+    const size_t np = (size_t)kMonQ * std::max(1, mon_blocks(c, true));
+    if (c->mon_part.n < np && (e = c->mon_part.alloc(np)) != hipSuccess) return e;
+    if (!c->mon_out.p && (e = c->mon_out.alloc(kMonQ)) != hipSuccess) return e;
+    if (zprev) {
+        if (c->nt && !c->mon_tzp.p) { if ((e = c->mon_tzp.alloc((size_t)9 * c->ldt)) != hipSuccess || (e = c->mon_tzp.zero()) != hipSuccess) return e; }
+        if (c->ntri && !c->mon_rzp.p) { if ((e = c->mon_rzp.alloc((size_t)6 * c->ldr)) != hipSuccess || (e = c->mon_rzp.zero()) != hipSuccess) return e; }
+        if (c->nbend && !c->mon_hzp.p) { if ((e = c->mon_hzp.alloc((size_t)3 * c->ldb)) != hipSuccess || (e = c->mon_hzp.zero()) != hipSuccess) return e; }
+        if (c->npin_terms && !c->mon_pzp.p) { if ((e = c->mon_pzp.alloc((size_t)6 * c->npin_terms)) != hipSuccess || (e = c->mon_pzp.zero()) != hipSuccess) return e; }
+    }
+    const size_t nterm = (size_t)c->nt + c->ntri + c->nbend;
+    if (term && nterm && !c->mon_term.p && (e = c->mon_term.alloc(nterm)) != hipSuccess) return e;
+    return hipSuccess;
+}
+// the kernel's view of the context at positions x; the pin rows as the step keeps them (3 per pin)
+MonArgs mon_args(const admm_hip_ctx *c, const double *x, bool nodes) {
+    MonArgs a{};
+    a.x = x; a.dt2 = c->dt * c->dt;
+    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
+    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
+    for (int i = 0; i < 6; ++i) a.kb[i] = c->kind_begin[i];
+    a.t_z = c->t_z.p; a.t_zp = c->mon_tzp.p;
+    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_z = c->r_z.p; a.r_zp = c->mon_rzp.p;
+    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_sc = c->h_sc.p; a.h_k = c->h_kst.p; a.h_z = c->h_z.p; a.h_zp = c->mon_hzp.p;
+    a.npin = c->npin_terms; a.pin_dim = 3; a.pin_vert = c->pin_vert_d.p; a.pin_z = c->pin_z.p; a.pin_zp = c->mon_pzp.p; a.pin_w2 = c->pin_weight * c->pin_weight;
+    a.n3 = c->n3; a.m = nodes ? c->m.p : nullptr; a.Mxbar = c->Mxbar.p;
+    a.nb_t = blocks_for(c->nt); a.nb_r = a.nb_t + blocks_for(c->ntri); a.nb_h = a.nb_r + blocks_for(c->nbend); a.nb_p = a.nb_h + blocks_for(c->npin_terms);
+    a.part = c->mon_part.p; a.term = nullptr;
+    return a;
+}
+// one pass over the terms + the sum of its partials into out [kMonQ] (device)
+template <bool RES, bool ENERGY>
+void launch_monitor(admm_hip_ctx *c, const MonArgs &a, double *out) {
+    const int nb = std::max(1, a.nb_p + (a.m ? blocks_for(a.n3) : 0));
+    hipLaunchKernelGGL((k_monitor<RES, ENERGY, false>), dim3(nb), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_mon_final, dim3(1), dim3(256), 0, c->stream, a.part, nb, out);
+}
+// z_prev <- D x: the reference's curr_z = D m_x at step entry (src/Solver.cpp:70)
+void launch_monitor_init(admm_hip_ctx *c, const double *x) {
+    const MonArgs a = mon_args(c, x, false);
+    if (a.nb_p > 0) hipLaunchKernelGGL((k_monitor<false, false, true>), dim3(a.nb_p), dim3(256), 0, c->stream, a);
+}
+// record s of the running step: after the global solve of ADMM iteration s, x = curr
+void launch_monitor_step(admm_hip_ctx *c, int s) {
+    const MonArgs a = mon_args(c, c->curr.p, c->mon_mode >= 2);
+    if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, c->mon_rec.p + (size_t)kMonQ * s);
+    else launch_monitor<true, false>(c, a, c->mon_rec.p + (size_t)kMonQ * s);
 }
 
 void launch_gather(admm_hip_ctx *c) {
@@ -2261,6 +2326,11 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
             sc[t] = dt2 * w2; gam[t] = w2 / (d->bend_stiffness[o] + w2);
         }
         HIP_TRY(c->h_idx.upload(idx)); HIP_TRY(c->h_coef.upload(coef)); HIP_TRY(c->h_sc.upload(sc)); HIP_TRY(c->h_gam.upload(gam));
+        {   // the hinges' stiffness itself: their energy (monitor.hpp)
+            std::vector<double> kst(ld, 0.0);
+            for (int t = 0; t < n; ++t) kst[t] = d->bend_stiffness[c->bend_perm[t]];
+            HIP_TRY(c->h_kst.upload(kst));
+        }
         HIP_TRY(c->h_u.alloc((size_t)3 * ld)); HIP_TRY(c->h_u.zero());
         HIP_TRY(c->h_z.alloc((size_t)3 * ld)); HIP_TRY(c->h_z.zero());
         HIP_TRY(c->h_cf.alloc((size_t)12 * ld)); HIP_TRY(c->h_cf.zero());
@@ -2297,6 +2367,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
             if (d->pin_active) act[p] = d->pin_active[p] ? 1 : 0;
         }
         c->pin_vert_h.assign(d->pin_vert, d->pin_vert + d->n_pins);
+        HIP_TRY(c->pin_vert_d.upload(std::vector<int>(d->pin_vert, d->pin_vert + d->n_pins)));      // (monitor.hpp: pin term -> vertex)
         HIP_TRY(c->vert_pin.upload(vp)); HIP_TRY(c->pin_active.upload(act)); HIP_TRY(c->pin_xyz.upload(xyz));
         HIP_TRY(c->pin_u.alloc(3 * (size_t)d->n_pins)); HIP_TRY(c->pin_u.zero());
         HIP_TRY(c->pin_z.alloc(3 * (size_t)d->n_pins)); HIP_TRY(c->pin_z.zero());
@@ -2957,6 +3028,15 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     c->uz_iters_step = 0; c->uz_detected = false;
     struct InStep { admm_hip_ctx *c; ~InStep() { c->in_step = false; } } in_step_guard{c};
     c->in_step = true;
+    // monitor (admm_hip_set_monitor): one record per ADMM iteration, written on the stream -- nothing here waits for the device
+    const bool mon = c->mon_mode != 0 && monitor_allowed(c);
+    c->mon_n = 0;
+    if (mon) {
+        HIP_TRY(mon_ensure(c, true, false));
+        if (c->mon_rec.n < (size_t)kMonQ * std::max(1, admm_iters)) HIP_TRY(c->mon_rec.alloc((size_t)kMonQ * std::max(1, admm_iters)));
+        launch_monitor_init(c, c->x.p);
+        c->mon_n = admm_iters;
+    }
     c->rc_prev2_valid = c->rc_prev_valid; c->rc_prev_valid = c->rc_iter; c->rc_frame += 1; c->rc_iter = 0;   // this frame's pairs become "previous frame"
     // How many pairs a projection uses is decided ONCE per context, from the scene's own behaviour: four pairs cost ~4 us per solve
     // more than three (8.8 MB of reads, 20 block sums) and pay when solves need many iterations (Kuhn cube: 17.4 -> 13.9 per solve),
@@ -3000,7 +3080,8 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
             if (c->lt_mode == 2) { c->lt_k0 = c->lt_ev[c->lt_used]; c->lt_k1 = c->lt_ev[c->lt_used + 1]; c->lt_taken = false; }
             else HIP_TRY(hipEventRecord(c->lt_ev[c->lt_used], st));
         }
-        launch_local<false>(c);                 // Solver.cpp:84-87
+        if (mon) launch_local<true>(c);         // (the monitor reads z: the WRITE_Z instantiations of admm_hip_local_step)
+        else launch_local<false>(c);            // Solver.cpp:84-87
         if (lt) {
             if (c->lt_mode == 2) { c->lt_k0 = nullptr; c->lt_k1 = nullptr; }
             else HIP_TRY(hipEventRecord(c->lt_ev[c->lt_used + 1], st));
@@ -3014,6 +3095,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         const int grc = launch_global(c, c->b.p, c->curr.p);   // Solver.cpp:99
         if (grc == -2) return kStepAborted;       // a grid barrier timed out in a column solve of UzawaCG: same recovery as any aborted on-chip solve
         if (grc) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
+        if (mon) launch_monitor_step(c, s);     // x = x^{s+1}, z = z^{s+1}, z_prev = z^s
     }
     c->timing = false;
     if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * admm_iters], st));
@@ -3254,6 +3336,106 @@ int admm_hip_solve_totals(admm_hip_ctx *c, int64_t *solves, int64_t *converged, 
     if (solves) *solves = counted ? h[0] : -1;
     if (converged) *converged = counted ? h[1] : -1;
     if (inner_iters) *inner_iters = counted ? h[2] : -1;
+    return ADMM_HIP_OK;
+}
+
+// ---- energy / residuals / monitor (monitor.hpp) ----
+static int mon_refuse(const admm_hip_ctx *c, const char *who) {
+    if (c->cm.on) return fail(ADMM_HIP_ERR_STATE, std::string(who) + ": this context holds only its rank's bodies; energies and residuals are sums over the whole scene (single-GPU contexts only)");
+    if (!monitor_allowed(c)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": single-GPU contexts only (world_size > 1, a communicator or a caller all-reduce splits the terms over ranks)");
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_energy(admm_hip_ctx *c, const double *x, double *totals4, double *per_term) {
+    if (!c || !totals4) return fail(ADMM_HIP_ERR_ARG, "energy: NULL argument");
+    if (int rc = mon_refuse(c, "energy")) return rc;
+    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, "energy: no device-resident state yet (admm_hip_set_state), and x is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = settle(c)) return rc;
+    HIP_TRY(mon_ensure(c, false, per_term != nullptr));
+    const double *xd = c->x.p;
+    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    MonArgs a = mon_args(c, xd, false);
+    a.term = per_term ? c->mon_term.p : nullptr;
+    launch_monitor<false, true>(c, a, c->mon_out.p);
+    HIP_TRY(hipGetLastError());
+    double h[kMonQ];
+    const size_t nterm = (size_t)c->nt + c->ntri + c->nbend;
+    std::vector<double> term(per_term ? nterm : 0);
+    HIP_TRY(hipMemcpyAsync(h, c->mon_out.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    if (per_term && nterm) HIP_TRY(hipMemcpyAsync(term.data(), c->mon_term.p, nterm * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    totals4[0] = h[4]; totals4[1] = h[5]; totals4[2] = h[6]; totals4[3] = (h[4] + h[5]) + h[6];
+    if (per_term) {      // device order (tets sorted by model, every family by its lowest vertex) -> the caller's term order
+        for (int n = 0; n < c->nt; ++n) per_term[c->tet_perm[n]] = term[n];
+        double *r = per_term + c->nt_total;
+        for (int t = 0; t < c->ntri; ++t) r[c->tri_perm[t]] = term[(size_t)c->nt + t];
+        r += c->ntri_total;
+        for (int t = 0; t < c->nbend; ++t) r[c->bend_perm[t]] = term[(size_t)c->nt + c->ntri + t];
+    }
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_residuals(admm_hip_ctx *c, const double *x, const double *z, const double *z_prev, double *out4) {
+    if (!c || !x || !z || !z_prev || !out4) return fail(ADMM_HIP_ERR_ARG, "residuals: NULL argument");
+    if (int rc = mon_refuse(c, "residuals")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = settle(c)) return rc;
+    HIP_TRY(mon_ensure(c, true, false));
+    if (c->npin_terms && !c->mon_pz6.p) HIP_TRY(c->mon_pz6.alloc((size_t)6 * c->npin_terms));
+    std::vector<double> tz, rz, pz, hz, tp, rp, pp, hp;
+    rows_to_dev(c, z, tz, rz, pz, hz);
+    rows_to_dev(c, z_prev, tp, rp, pp, hp);
+    const size_t pin0 = 9 * (size_t)c->nt_total + 6 * (size_t)c->ntri_total + 3 * (size_t)c->nbend_total;      // the pins keep all six rows here
+    HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (c->nt) { HIP_TRY(hipMemcpyAsync(c->t_z.p, tz.data(), tz.size() * sizeof(double), hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(c->mon_tzp.p, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, st)); }
+    if (c->ntri) { HIP_TRY(hipMemcpyAsync(c->r_z.p, rz.data(), rz.size() * sizeof(double), hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(c->mon_rzp.p, rp.data(), rp.size() * sizeof(double), hipMemcpyHostToDevice, st)); }
+    if (c->nbend) { HIP_TRY(hipMemcpyAsync(c->h_z.p, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(c->mon_hzp.p, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, st)); }
+    if (c->npin_terms) {
+        HIP_TRY(hipMemcpyAsync(c->mon_pz6.p, z + pin0, (size_t)6 * c->npin_terms * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->mon_pzp.p, z_prev + pin0, (size_t)6 * c->npin_terms * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    MonArgs a = mon_args(c, c->curr.p, false);
+    a.pin_dim = 6; a.pin_z = c->mon_pz6.p;
+    launch_monitor<true, false>(c, a, c->mon_out.p);
+    HIP_TRY(hipGetLastError());
+    double h[kMonQ];
+    HIP_TRY(hipMemcpyAsync(h, c->mon_out.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) out4[i] = std::sqrt(h[i]);
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_set_monitor(admm_hip_ctx *c, int32_t mode) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "set_monitor: NULL context");
+    if (mode < 0 || mode > 2) return fail(ADMM_HIP_ERR_ARG, "set_monitor: mode must be 0 (off), 1 (residuals) or 2 (residuals + objective)");
+    if (mode != 0) { if (int rc = mon_refuse(c, "set_monitor")) return rc; }
+    c->mon_mode = mode;
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_get_monitor(admm_hip_ctx *c, int32_t cap, int32_t *n, double *records) {
+    if (!c || !n || cap < 0 || (cap > 0 && !records)) return fail(ADMM_HIP_ERR_ARG, "get_monitor: bad argument");
+    if (int rc = mon_refuse(c, "get_monitor")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = settle(c)) return rc;      // (a replayed step has rewritten its records)
+    *n = c->mon_n;
+    const int m = std::min((int)cap, c->mon_n);
+    if (m <= 0) return ADMM_HIP_OK;
+    std::vector<double> h((size_t)kMonQ * m);
+    HIP_TRY(hipMemcpy(h.data(), c->mon_rec.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const double half_idt2 = 0.5 / (c->dt * c->dt);
+    for (int s = 0; s < m; ++s) {
+        const double *q = h.data() + (size_t)kMonQ * s;
+        double *r = records + 8 * (size_t)s;
+        for (int i = 0; i < 4; ++i) r[i] = std::sqrt(q[i]);
+        r[4] = (q[4] + q[5]) + q[6]; r[5] = half_idt2 * q[7]; r[6] = r[4] + r[5]; r[7] = 0.0;
+    }
     return ADMM_HIP_OK;
 }
 

@@ -20,7 +20,7 @@ namespace solver_detail {
 
 // Solver::Settings (src/Solver.hpp:39-50): command-line switches in the comments
 struct SolverSettings {
-    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0) {}
+    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0), monitor(0) {}
     double timestep_s;   // -dt
     int verbose;         // -v
     int admm_iters;      // -it
@@ -29,6 +29,7 @@ struct SolverSettings {
     double constraint_w; // -ck  (-1 = automatic)
     int soft_modes;      // -sm  (GPU build, appended: the reference's fields keep their order) every PCG solve ends with an exact Galerkin step on
                          //      the k softest modes of the system matrix (admm_hip_compute_soft_modes at initialize); 0 = off
+    int monitor;         //      (GPU build, appended) ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
     void help();
     bool parse_args(int argc, char **argv);   // true when help() was printed
 };
@@ -41,12 +42,18 @@ struct SolverRuntimeData {
     void print(const SolverSettings &settings);
 };
 
+// One ADMM iteration of the last step as the monitor recorded it (Settings::monitor; include/admm_hip.h: admm_hip_get_monitor), taken after
+// the iteration's global solve: primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x|; elastic energy, inertia term
+// 1/(2 dt^2) |x - x_bar|^2_M and their sum, the objective (the last three 0 with monitor = 1).
+struct AdmmRecord { double primal, dz, wz, wdx, energy, inertia, objective; };
+
 } // namespace solver_detail
 
 class Solver {
 public:
     typedef solver_detail::SolverSettings Settings;
     typedef solver_detail::SolverRuntimeData RuntimeData;
+    typedef solver_detail::AdmmRecord AdmmRecord;
 
     Solver();
     virtual ~Solver();
@@ -89,6 +96,10 @@ public:
     bool build_global_matrices;                                   // initialize() fills m_D / m_Dt / m_W_diag / solver_Dt_Wt_W (default true, like
                                                                   // the reference; the GPU path itself never reads them -- switch off for very large scenes)
     std::shared_ptr<LinearSolver> linear_solver() { return m_linsolver; }
+    // Sum of EnergyTerm::energy(D, x) over all terms (pins have none), reduced on the device (admm_hip_energy); after initialize()
+    double energy(const VecX &x);
+    // the records of the last step(), one per ADMM iteration; empty with Settings::monitor = 0
+    const std::vector<AdmmRecord> &admm_history() { return m_history; }
     void *context() { return m_ctx; }                             // the admm_hip_ctx behind this solver (include/admm_hip.h), for the C ABI's extras
 
 protected:
@@ -97,6 +108,7 @@ protected:
     bool initialized;
     Settings m_settings;
     RuntimeData m_runtime;
+    std::vector<AdmmRecord> m_history;
     // Global matrices of src/Solver.hpp:115-121, for subclasses that read them (the reference's own step() is their only other user;
     // here the device holds its own copies in kernel layouts): reduction matrix D (rows x dof) and its transpose, the weights W,
     // dt^2 D^T W^T W (dof x rows).

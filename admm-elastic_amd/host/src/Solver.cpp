@@ -276,7 +276,14 @@ bool TriEnergyTerm::flatten(FlatTerm &o) const {
     o.weight = weight; o.limit_min = lame.limit_min; o.limit_max = lame.limit_max;
     return true;
 }
-double TriEnergyTerm::energy(const VecX &) { throw std::runtime_error("TriEnergyTerm::energy: debugging aid not provided in the MI355X build"); }
+double TriEnergyTerm::energy(const VecX &F) { // src/TriEnergyTerm.cpp:104-114: k / 2 area |F - P|^2 = k / 2 area sum_{i<2} (sigma_i - 1)^2, strain limits ignored
+    // singular values of the 3x2 F in closed form: sigma_1^2 = the larger eigenvalue of F^T F, sigma_1 sigma_2 = |f_0 x f_1|
+    const double c00 = F[0] * F[0] + F[1] * F[1] + F[2] * F[2], c01 = F[0] * F[3] + F[1] * F[4] + F[2] * F[5], c11 = F[3] * F[3] + F[4] * F[4] + F[5] * F[5];
+    const double cr[3] = {F[1] * F[5] - F[2] * F[4], F[2] * F[3] - F[0] * F[5], F[0] * F[4] - F[1] * F[3]};
+    const double s1 = std::sqrt(0.5 * (c00 + c11 + std::sqrt((c00 - c11) * (c00 - c11) + 4.0 * c01 * c01)));
+    const double s2 = s1 > 0.0 ? std::sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) / s1 : 0.0;
+    return 0.5 * lame.bulk_modulus() * area * ((s1 - 1.0) * (s1 - 1.0) + (s2 - 1.0) * (s2 - 1.0));
+}
 double TriEnergyTerm::gradient(const VecX &, VecX &) { throw std::runtime_error("**TriEnergyTerm TODO: gradient function"); }
 
 bool SpringPin::flatten(FlatTerm &o) const {
@@ -574,6 +581,8 @@ bool Solver::initialize(const Settings &settings_) { // src/Solver.cpp:167-261
     check(admm_hip_get_matrix(ctx, rp.data(), ci.data(), va.data(), &nnz), "Solver::initialize");
     la::set_csr(solver_termA, d.n_verts, std::vector<int>(rp.begin(), rp.end()), std::vector<int>(ci.begin(), ci.end()), va);
     m_linsolver->update_system(solver_termA);
+    if (m_settings.monitor) check(admm_hip_set_monitor(ctx, (int32_t)m_settings.monitor), "Solver::initialize (monitor)");
+    m_history.clear();
     if (m_settings.verbose >= 1) printf("%d nodes, %d energy terms\n", (int)m_x.size() / 3, (int)energyterms.size());
     initialized = true;
     return true;
@@ -593,7 +602,25 @@ void Solver::step() { // src/Solver.cpp:35-110
     m_runtime = RuntimeData();
     m_runtime.global_ms = st.global_ms; m_runtime.local_ms = st.local_ms; m_runtime.collision_ms = st.collision_ms;
     m_runtime.inner_iters = st.inner_iters;
+    m_history.clear();
+    if (m_settings.monitor) {
+        int32_t n = 0;
+        std::vector<double> rec(8 * (size_t)std::max(1, m_settings.admm_iters));
+        check(admm_hip_get_monitor(ctx, (int32_t)(rec.size() / 8), &n, rec.data()), "Solver::step (monitor)");
+        for (int s = 0; s < std::min((int)n, (int)(rec.size() / 8)); ++s) {
+            const double *r = rec.data() + 8 * (size_t)s;
+            m_history.push_back(AdmmRecord{r[0], r[1], r[2], r[3], r[4], r[5], r[6]});
+        }
+    }
     if (m_settings.verbose > 0) m_runtime.print(m_settings);
+}
+
+double Solver::energy(const VecX &x) {
+    if (!initialized) throw std::runtime_error("Solver::energy: initialize() first");
+    if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::energy: x must hold three values per node");
+    double tot[4] = {0.0, 0.0, 0.0, 0.0};
+    check(admm_hip_energy((admm_hip_ctx *)m_ctx, x.data(), tot, nullptr), "Solver::energy");
+    return tot[3];
 }
 
 void Solver::save_matrix(const std::string &filename) { // src/Solver.cpp:264-269 (Ahat; A = diag(m) + Ahat (x) I3)

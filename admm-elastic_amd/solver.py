@@ -64,6 +64,7 @@ class Settings:
         self.device = 0
         self.rank = 0
         self.world_size = 1
+        self.monitor = 0             # GPU build: ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown setting " + k)
@@ -480,6 +481,8 @@ class Solver:
                                                      iptr(o.tets), o.faces.shape[0], iptr(o.faces)))
         if s.soft_modes > 0 and s.linsolver != 1 and not (s.world_size > 1 and os.environ.get("ADMM_HIP_DIST_SOLVE") == "1"):
             check(lib().admm_hip_compute_soft_modes(ctx, int(s.soft_modes), 0))
+        if s.monitor:
+            check(lib().admm_hip_set_monitor(ctx, int(s.monitor)))
         self.initialized = True
         return True
 
@@ -567,6 +570,54 @@ class Solver:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().admm_hip_solve_totals(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    # ---- energy and ADMM residuals on the device (csrc/monitor.hpp) -----------------------------------
+    def energy(self, x=None, per_term=False):
+        """EnergyTerm::energy (src/EnergyTerm.hpp:142-147) of every term at x (default: the device-resident state), reduced on the
+        device: dict(tets, tris, hinges, total); with per_term=True also `terms` [n_tets + n_tris + n_bends] in the order the terms
+        were added (tets, tris, hinges).  Pins have no energy."""
+        self._need_ctx()
+        xc = None if x is None else f64(x).ravel().copy()
+        if xc is not None and xc.size != self.m_x.size:
+            raise ValueError("energy: x must hold 3 values per node")
+        tot = np.zeros(4)
+        f = getattr(self, "_flat", None) or self.flatten()
+        terms = np.zeros(f["tet_idx"].shape[0] + f["tri_idx"].shape[0] + f["bend_idx"].shape[0]) if per_term else None
+        check(lib().admm_hip_energy(self._ctx, dptr(xc), dptr(tot), dptr(terms)))
+        out = dict(tets=tot[0], tris=tot[1], hinges=tot[2], total=tot[3])
+        if per_term:
+            out["terms"] = terms
+        return out
+
+    def residuals(self, x, z, z_prev):
+        """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""
+        self._need_ctx()
+        R = self.num_rows()
+        x = f64(x).ravel().copy(); z = f64(z).ravel().copy(); zp = f64(z_prev).ravel().copy()
+        if x.size != self.m_x.size or z.size != R or zp.size != R:
+            raise ValueError("residuals: x needs 3 values per node, z and z_prev num_rows() values")
+        out = np.zeros(4)
+        check(lib().admm_hip_residuals(self._ctx, dptr(x), dptr(z), dptr(zp), dptr(out)))
+        return tuple(out)
+
+    def set_monitor(self, mode):
+        """admm_hip_set_monitor: 0 off, 1 residuals, 2 residuals + objective per ADMM iteration; in effect from the next step."""
+        self._need_ctx()
+        check(lib().admm_hip_set_monitor(self._ctx, int(mode)))
+        self._settings.monitor = int(mode)
+
+    def admm_history(self):
+        """Records of the last step (admm_hip_get_monitor), one entry per ADMM iteration, taken after its global solve: dict of arrays
+        primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x|, energy, inertia = 1/(2 dt^2) |x - x_bar|^2_M,
+        objective = energy + inertia (the last three zero in mode 1).  Empty arrays when the step ran with the monitor off."""
+        self._need_ctx()
+        n = C.c_int32(0)
+        check(lib().admm_hip_get_monitor(self._ctx, 0, C.byref(n), None))
+        rec = np.zeros((n.value, 8))
+        if n.value:
+            check(lib().admm_hip_get_monitor(self._ctx, n.value, C.byref(n), dptr(rec)))
+        keys = ("primal", "dz", "wz", "wdx", "energy", "inertia", "objective")
+        return {k: rec[:, i].copy() for i, k in enumerate(keys)}
 
     def set_solver_params(self, kind, max_iters=0, tol=-1.0, omega=0.0):
         """admm_hip_set_solver_params: the LinearSolver objects' public tuning members after initialize (the reference reads them on

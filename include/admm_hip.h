@@ -282,6 +282,27 @@ int admm_hip_global_solve(admm_hip_ctx *ctx, const double *b, double *x_inout, i
  * does not use the general-mesh on-chip PCG. */
 int admm_hip_solve_totals(admm_hip_ctx *ctx, int64_t *solves, int64_t *converged, int64_t *inner_iters);   /* returns ADMM_HIP_OK; the three values are -1 when this context's solver keeps no totals */
 
+/* EnergyTerm::energy (src/EnergyTerm.hpp:82,142-147; src/TetEnergyTerm.cpp:94-100,138-149; src/TriEnergyTerm.cpp:104-114) of every term at x, on
+ * the device.  x [3*n_verts] host, or NULL = the device-resident state.  totals[4] = tets, tris, hinges, their sum.  per_term: NULL or
+ * [n_tets + n_tris + n_bends] in the CALLER's term order (not the library's kind-sorted order).  Pins have no energy (the reference throws,
+ * src/SpringEnergyTerm.hpp:63-66).  Every tet kind of ADMM_TET_*; triangles ignore their strain limits like the reference.  The sums are
+ * bit-reproducible from run to run (no floating-point atomics).  Single-GPU contexts only.  Synchronises the stream. */
+int admm_hip_energy(admm_hip_ctx *ctx, const double *x, double *totals4, double *per_term);
+
+/* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
+ * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
+int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
+
+/* Monitor of admm_hip_step: 0 off (default), 1 residuals, 2 residuals + objective.  In effect from the next step.  Off, a step is what it
+ * was: no launch more, no kernel changed.  On, the local step also stores z and one reduction over the terms follows every global solve, on
+ * the context's stream, without any host synchronisation.  Single-GPU contexts only. */
+int admm_hip_set_monitor(admm_hip_ctx *ctx, int32_t mode);
+/* Records of the LAST step, one per ADMM iteration s, taken after that iteration's global solve with x = x^{s+1}, z = z^{s+1},
+ * z_prev = z^{s} (z^0 = D m_x at step entry, src/Solver.cpp:70).  records [cap][8]: the four norms above, elastic energy,
+ * inertia term 1/(2 dt^2) |x - x_bar|^2_M, their sum (the objective; the last three 0 in mode 1), 0.
+ * *n = iterations recorded (may exceed cap; 0 when the last step ran with the monitor off).  Synchronises the stream. */
+int admm_hip_get_monitor(admm_hip_ctx *ctx, int32_t cap, int32_t *n, double *records);
+
 /* The LinearSolver objects' public tuning members, changed AFTER Solver::initialize.  The reference reads them on every solve --
  * NodalMultiColorGS::max_iters / m_tol / m_omega (src/NodalMultiColorGS.hpp:40-46, used at :100 and :136-140), UzawaCG::max_iters /
  * m_tol (src/UzawaCG.hpp:44-45, used at :92 and :109) -- so a caller may cast Solver::m_linsolver and change them between steps.
