@@ -78,7 +78,13 @@ struct DevBuf {
         if (e != hipSuccess || h.empty()) return e;
         return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
     }
-    hipError_t zero() { return n ? hipMemset(p, 0, n * sizeof(T)) : hipSuccess; }
+    // hipMemset runs on the NULL stream and may return before it has run; the contexts' streams are non-blocking and do not wait for
+    // it, so the memset is waited for here (set-up paths only: nothing in a step calls this)
+    hipError_t zero() {
+        if (!n) return hipSuccess;
+        const hipError_t e = hipMemset(p, 0, n * sizeof(T));
+        return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+    }
     void release() {
         if (p) { (void)hipFree(p); g_dev_buffers -= 1; g_dev_bytes -= (int64_t)(n * sizeof(T)); }
         p = nullptr; n = 0;
@@ -486,10 +492,18 @@ hipError_t mon_ensure(admm_hip_ctx *c, bool zprev, bool term) {
     if (c->mon_part.n < np && (e = c->mon_part.alloc(np)) != hipSuccess) return e;
     if (!c->mon_out.p && (e = c->mon_out.alloc(kMonQ)) != hipSuccess) return e;
     if (zprev) {
-        if (c->nt && !c->mon_tzp.p) { if ((e = c->mon_tzp.alloc((size_t)9 * c->ldt)) != hipSuccess || (e = c->mon_tzp.zero()) != hipSuccess) return e; }
-        if (c->ntri && !c->mon_rzp.p) { if ((e = c->mon_rzp.alloc((size_t)6 * c->ldr)) != hipSuccess || (e = c->mon_rzp.zero()) != hipSuccess) return e; }
-        if (c->nbend && !c->mon_hzp.p) { if ((e = c->mon_hzp.alloc((size_t)3 * c->ldb)) != hipSuccess || (e = c->mon_hzp.zero()) != hipSuccess) return e; }
-        if (c->npin_terms && !c->mon_pzp.p) { if ((e = c->mon_pzp.alloc((size_t)6 * c->npin_terms)) != hipSuccess || (e = c->mon_pzp.zero()) != hipSuccess) return e; }
+        // zeroed ON THE CONTEXT'S STREAM: DevBuf::zero() is a hipMemset on the NULL stream, which this non-blocking stream does not wait
+        // for -- it could land AFTER the z_prev <- D x of the step that follows (dz of iteration 0 then came out as |W z|, off by 3e5
+        // in test_monitor_matches_oracle_trace[cloth6], once in a few runs)
+        auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
+            if (b.p) return hipSuccess;
+            const hipError_t e2 = b.alloc(n);
+            return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
+        };
+        if (c->nt && (e = fresh(c->mon_tzp, (size_t)9 * c->ldt)) != hipSuccess) return e;
+        if (c->ntri && (e = fresh(c->mon_rzp, (size_t)6 * c->ldr)) != hipSuccess) return e;
+        if (c->nbend && (e = fresh(c->mon_hzp, (size_t)3 * c->ldb)) != hipSuccess) return e;
+        if (c->npin_terms && (e = fresh(c->mon_pzp, (size_t)6 * c->npin_terms)) != hipSuccess) return e;
     }
     const size_t nterm = (size_t)c->nt + c->ntri + c->nbend;
     if (term && nterm && !c->mon_term.p && (e = c->mon_term.alloc(nterm)) != hipSuccess) return e;

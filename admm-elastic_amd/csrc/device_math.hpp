@@ -113,7 +113,29 @@ __device__ __forceinline__ void hestenes_rotate(double *bp, double *bq, double *
 //      becomes round-off; further sweeps only while some pair of columns of some lane is not orthogonal to 3e-14 (cosine).
 //  (4) U by Gram-Schmidt on B: U in SO(3) by construction, the last stretch u2 . b2 carries the sign of det F; if it is negative
 //      and not the smallest, the sign is moved by flipping two columns of U (no sorting, no special case for flat elements).
-__device__ __forceinline__ void signed_svd3(const double *F, double *U, double *S, double *V) {
+// tol2 = the cos^2 at which the FP64 sweeps of (3) stop.  kSvdTol2: F = U diag(S) V^T to 5e-14 |F| (measured <= 3e-14), what every
+// hyperelastic prox needs.  The LINEAR tet passes kSvdTolLinear2: its z = U diag((1 + S) / 2) V^T implies the rotation P = 2 z - F
+// = U V^T + (U diag(S) V^T - F), so the factorisation error is P's distance from SO(3); with 1e-30 (cos <= 1e-15, a decade above
+// the round-off of the dot products) P^T P = I to 1e-14 for |F| of a few units (tests/test_local_step_edges.py, check D).
+constexpr double kSvdTol2 = 1e-27, kSvdTolLinear2 = 1e-30;
+__device__ __forceinline__ void signed_svd3(const double *Fin, double *U, double *S, double *V, const double tol2 = kSvdTol2) {
+    // (0) F is scaled by an EVEN power of two that brings its largest entry into [1, 4): exact, and every quantity below scales
+    // by an exact power of two with it (the v_rsq seeds see the same mantissa), so the factors of an element of ordinary size do
+    // not change by a bit -- but the squares of the Gram entries (nd2, the rotations' a^2 + b^2) no longer leave the double range
+    // for |F| beyond 1e+-75: unscaled, 1e100 came back as NaN and 1e-100 as a wrong factorisation (tests/test_local_step_edges.py).
+    double F[9];
+    int ev;
+    {
+        double fmx = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) fmx = fmax(fmx, fabs(Fin[i]));
+        int he = (__double2hiint(fmx) >> 20) & 0x7ff;
+        he = he < 3 ? 3 : (he > 2043 ? 2043 : he);      // zero / denormal / next to overflow: the scale stays a normal number
+        ev = (he - 1023) & ~1;
+        const double sc = __hiloint2double((1023 - ev) << 20, 0);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) F[i] = Fin[i] * sc;
+    }
     double v0[3], v1[3], v2[3];
     const double c00 = dot3(F + 0, F + 0), c01 = dot3(F + 0, F + 3), c02 = dot3(F + 0, F + 6);
     const double c11 = dot3(F + 3, F + 3), c12 = dot3(F + 3, F + 6), c22 = dot3(F + 6, F + 6);
@@ -157,9 +179,8 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
         b1[r] = fma(F[r], v1[0], fma(F[3 + r], v1[1], F[6 + r] * v1[2]));
         b2[r] = fma(F[r], v2[0], fma(F[3 + r], v2[1], F[6 + r] * v2[2]));
     }
-    // (3) FP64 one-sided sweeps until every pair of columns is orthogonal: cos^2 <= kSvdTol2.  Then F = U diag(S) V^T to
+    // (3) FP64 one-sided sweeps until every pair of columns is orthogonal: cos^2 <= tol2 (kSvdTol2).  Then F = U diag(S) V^T to
     // ~3e-14 |F| whatever the order of the columns in the Gram-Schmidt below.
-    constexpr double kSvdTol2 = 1e-27;
     double n0, n1, n2;
 #pragma unroll 1
     for (int sweep = 0; sweep < 12; ++sweep) {
@@ -170,7 +191,7 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
         n0 = dot3(b0, b0); n1 = dot3(b1, b1); n2 = dot3(b2, b2);
         const double g01 = dot3(b0, b1), g02 = dot3(b0, b2), g12 = dot3(b1, b2);
         ADMM_RECORD(8 + sweep, fmax(g01 * g01 / fmax(n0 * n1, 1e-300), fmax(g02 * g02 / fmax(n0 * n2, 1e-300), g12 * g12 / fmax(n1 * n2, 1e-300))));
-        const bool open = g01 * g01 > kSvdTol2 * n0 * n1 || g02 * g02 > kSvdTol2 * n0 * n2 || g12 * g12 > kSvdTol2 * n1 * n2;
+        const bool open = g01 * g01 > tol2 * n0 * n1 || g02 * g02 > tol2 * n0 * n2 || g12 * g12 > tol2 * n1 * n2;
         if (!__any(open)) break;
     }
     // (4) U by Gram-Schmidt on b0, b1; u2 = u0 x u1.  A column that is round-off (flat or collapsed element) must not be one
@@ -212,7 +233,8 @@ __device__ __forceinline__ void signed_svd3(const double *F, double *U, double *
     // the sign of det F sits on s2; the convention wants it on the smallest stretch: flip u2 and that column of U
     const bool f0 = s2 < 0.0 && s0 < -s2 && s0 <= s1, f1 = s2 < 0.0 && s1 < -s2 && !f0;
     const double g0 = f0 ? -1.0 : 1.0, g1 = f1 ? -1.0 : 1.0, g2 = (f0 || f1) ? -1.0 : 1.0;
-    S[0] = s0 * g0; S[1] = s1 * g1; S[2] = s2 * g2;
+    const double isc = __hiloint2double((1023 + ev) << 20, 0);      // back to the scale of F
+    S[0] = s0 * g0 * isc; S[1] = s1 * g1 * isc; S[2] = s2 * g2 * isc;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         U[i] = u0[i] * g0; U[3 + i] = u1[i] * g1; U[6 + i] = u2[i] * g2;
@@ -662,13 +684,24 @@ __device__ __forceinline__ int newton_stretch_dense(const MODEL &m, double *s, i
 #pragma unroll 1
         for (int ls = 0; ls < 50; ++ls) {
             double gs = 0.0;
+            bool clipped = false;      // an INTERIOR component would land on the bound
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 sn[i] = fma(t, d[i], s[i]);
-                if (m.type != 0) sn[i] = fmax(sn[i], m.lower());
+                if (m.type != 0) { clipped = clipped || (sn[i] < m.lower() && s[i] > m.lower()); sn[i] = fmax(sn[i], m.lower()); }
                 gs = fma(g[i], sn[i] - s[i], gs);
             }
-            if (m.feasible(sn)) {
+            // A component parked on the bound with an outward gradient is frozen for good, so an overshooting step must not put it
+            // there while a shorter one keeps it inside: from (1.78, 0.98, 0.10) with x0_3 = -0.10 (StVK, k = 0.1 mu) the full step
+            // clipped s_3 to 0 and the iteration ended on the boundary point (1.16, 1.13, 0), objective 1.33e5, where the closed-form
+            // kernel and the reference reach the interior minimiser (1.04, 1.00, 0.95), 3.31e4.  The first kInteriorTries halvings
+            // therefore only accept interior points; a minimiser that IS on the bound is approached geometrically and taken once the
+            // remaining distance is below 2^-kInteriorTries of the step.
+#ifndef ADMM_INTERIOR_TRIES
+#define ADMM_INTERIOR_TRIES 30      // (0 = the rule before this one; tests/test_local_step_edges.py builds both to count iterations)
+#endif
+            constexpr int kInteriorTries = ADMM_INTERIOR_TRIES;
+            if (m.feasible(sn) && !(clipped && ls < kInteriorTries)) {
                 fn = m.eval(sn, gn, Hn);
                 if (fn <= f + 1e-4 * gs + 4e-16 * (fabs(f) + fscale)) { ok = true; break; }
             }
@@ -784,7 +817,7 @@ __device__ __forceinline__ void prox_stretches_table(const double *tab, double k
     newton_stretch_dense(m, S, 200);
 }
 // HyperElasticTet::prox on the stretches (src/TetEnergyTerm.cpp:124-135) for a spline with kappa != 0
-__device__ __forceinline__ void prox_stretches_kappa(int type, double mu, double la, double k, double kappa, double *S) {
+__device__ __forceinline__ int prox_stretches_kappa(int type, double mu, double la, double k, double kappa, double *S) {      // returns the Newton iterations
     SplineKappaModel m;
     const double ik = fast_rcp(k);
     m.type = type; m.mu = mu * ik; m.la = la * ik; m.k = 1.0; m.kappa = kappa * ik;
@@ -793,7 +826,7 @@ __device__ __forceinline__ void prox_stretches_kappa(int type, double mu, double
     if (fabs(S[0]) < eps && fabs(S[1]) < eps && fabs(S[2]) < eps) { S[0] = eps; S[1] = eps; S[2] = eps; } // :128-131
     S[0] = fabs(S[0]); S[1] = fabs(S[1]); S[2] = fabs(S[2]);   // :133
     if (type == 0) { S[0] = fmax(S[0], 1e-12); S[1] = fmax(S[1], 1e-12); S[2] = fmax(S[2], 1e-12); }
-    newton_stretch_dense(m, S, 200);
+    return newton_stretch_dense(m, S, 200);
 }
 
 // ---- STABLE NEO-HOOKEAN (the reference's README lists it as a TODO, README.md:23-28; no reference code: "parity unpinned") -------------

@@ -400,7 +400,7 @@ __device__ __forceinline__ void tet_compute_store(const TetArgs &a, int t, bool 
 #pragma unroll
             for (int c = 0; c < 9; ++c) sBi[c * kChunkLdK] = in.Bi[c];
         }
-        signed_svd3(q, U, S0, V);   // q = U diag(S0) V^T to round-off: q itself is not needed any more
+        signed_svd3(q, U, S0, V, KIND == 0 ? kSvdTolLinear2 : kSvdTol2);   // q = U diag(S0) V^T to round-off: q itself is not needed any more
     }
     ADMM_PHASE_MARK(1);
     // the reduction list of this thread's record (first pass): in flight across the prox instead of after the block barrier

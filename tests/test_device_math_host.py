@@ -16,12 +16,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 dp = C.POINTER(C.c_double)
 
 
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("hostmath") / "libhostmath.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(HERE, "hostmath"), "-o", out,
+def build_hostmath(out_dir, flags=()):
+    """tests/hostmath compiled with g++ (+ flags, e.g. -DHM_VOTE_ALWAYS) into out_dir -> the loaded library"""
+    out = os.path.join(str(out_dir), "libhostmath.so")
+    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", *flags, "-I", os.path.join(HERE, "hostmath"), "-o", out,
                            os.path.join(HERE, "hostmath", "hostmath.cpp")])
     return C.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def hm(tmp_path_factory):
+    return build_hostmath(tmp_path_factory.mktemp("hostmath"))
 
 
 def _svd(L, F):

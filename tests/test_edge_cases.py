@@ -94,7 +94,9 @@ def test_degenerate_deformations_through_the_kernel():
     z, u = s.local_step(x.ravel(), np.zeros(R))
     zo = np.zeros(R); uo = np.zeros(R)
     o.local_step(x.ravel(), zo, uo)
-    assert np.abs(z - zo).max() < 1e-7
+    # (1e-10: the bar of every other NH comparison with the oracle; tests/test_local_step_edges.py measures 3.8e-14 on inverted elements)
+    print("all inverted: |z - z_oracle| = %.3g" % np.abs(z - zo).max())
+    assert np.abs(z - zo).max() < 1e-10
 
 
 @pytest.mark.gpu
