@@ -239,6 +239,10 @@ struct admm_hip_ctx {
     DevBuf<int> oc_nbr; DevBuf<unsigned long long> oc_flags;   // neighbour hand-off of the pipelined iteration
     DevBuf<unsigned long long> oc_prof;   // diagnosis (ADMM_HIP_OC_PROF=1)
     bool oc_debug = false, oc_always_verify = false; int oc_prof_block = 0;
+    // k_pcg2 has a generic and a hot instance (pcg_onchip2.hpp); launch_pcg2 chooses per launch (pcg2_hot_ok)
+    bool oc_force_generic = false;      // diagnosis (ADMM_HIP_OC_GENERIC=1): every launch takes the generic instance
+    int oc_last_instance = 0;           // of the last main-stream launch: 0 none yet, 1 generic, 2 hot
+    int64_t oc_instance_launches[4] = {0, 0, 0, 0};   // hot, generic, of these on column lanes: hot (never), generic
     // general-mesh plan of the on-chip PCG (oc_plan.cpp): internal row order, its SELL, slab shares, two-level data
     double oc_sm_ab = 0.0, oc_sm_b = 0.0, oc_lam_bb = 0.0;   // block-local smoother of k_pcg2 (pcg_onchip2.hpp: smooth)
     bool oc_plan = false, oc_coarse = false; int oc_rows = 0, oc_bcols = 0, oc_nc = 0, oc_ncp = 0, oc_veclen = 0;
@@ -636,7 +640,25 @@ int oc_diagnostics(admm_hip_ctx *c, int seq) {
     return 0;
 }
 
-struct OcRc { bool on = false; RcBasis B{}; double *Eslot = nullptr, *Rslot = nullptr; const int *skip = nullptr; };
+struct OcRc { bool on = false; RcBasis B{}; double *Eslot = nullptr, *Rslot = nullptr; const int *skip = nullptr;
+              bool loop = false; };      // loop: a solve of the ADMM loop (launch_global's `loop`), not a stand-alone admm_hip_global_solve
+
+// The instances of k_pcg2 (pcg_onchip2.hpp) by block size and configuration
+static const void *pcg2_instance(int T, bool hot) {
+    if (T <= 768) return hot ? (const void *)k_pcg2<768, true> : (const void *)k_pcg2<768, false>;
+    return hot ? (const void *)k_pcg2<1024, true> : (const void *)k_pcg2<1024, false>;
+}
+// May this launch take the hot instance?  Only when everything that instance fixed at compile time holds: a solve of the ADMM loop on the
+// main stream with the recycled warm start and no skip word, the two-level preconditioner, the neighbour hand-off lists, no profiling or
+// debugging, at most two record units per thread.  Everything else is the generic instance's.  (The halo may be of any length: fixing it
+// at two entries per thread was tried and changed nothing in the instance's registers or its iteration.)
+static bool pcg2_hot_ok(const admm_hip_ctx *c, const OcRc &rc, const admm_hip_ctx::OcLane *ln) {
+    if (c->oc_force_generic || !rc.loop || ln || !rc.on || rc.skip) return false;
+    if (!c->oc_coarse || !c->oc_ainv.p || c->oc_nc > 2 * c->oc_T) return false;
+    if (!c->oc_nbr.p || !c->oc_flags.p) return false;
+    if (c->oc_prof.p || c->oc_debug) return false;
+    return 4 * c->oc_G <= 2 * c->oc_T;
+}
 
 // General-mesh plan: k_pcg2 (pcg_onchip2.hpp)
 int launch_pcg2(admm_hip_ctx *c, const double *b, double *x, int max_iters, const OcRc &rc, admm_hip_ctx::OcLane *ln = nullptr) {
@@ -671,9 +693,17 @@ int launch_pcg2(admm_hip_ctx *c, const double *b, double *x, int max_iters, cons
         if (c->oc_coarse) a.cbuf = ln->cbuf;
         a.trust_short = 0;
     }
-    if (c->oc_T <= 768) hipLaunchKernelGGL((k_pcg2<768>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
-    else hipLaunchKernelGGL((k_pcg2<1024>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
-    if (ln) return 0;
+    const bool hot = pcg2_hot_ok(c, rc, ln);
+    if (c->oc_T <= 768) {
+        if (hot) hipLaunchKernelGGL((k_pcg2<768, true>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
+        else hipLaunchKernelGGL((k_pcg2<768, false>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
+    } else {
+        if (hot) hipLaunchKernelGGL((k_pcg2<1024, true>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
+        else hipLaunchKernelGGL((k_pcg2<1024, false>), dim3(c->oc_G), dim3(c->oc_T), c->oc_lds, st, a);
+    }
+    c->oc_instance_launches[hot ? 0 : 1] += 1;
+    if (ln) { c->oc_instance_launches[hot ? 2 : 3] += 1; return 0; }
+    c->oc_last_instance = hot ? 2 : 1;
     c->last_launched_iters = 0;
     if (c->oc_debug || c->oc_prof.p) return oc_diagnostics(c, a.seq);
     return 0;
@@ -773,13 +803,16 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
         }
     }
     if (!c->oc_plan) return hipSuccess;      // no plan (halo too large for 16-bit columns, per-dof masses, ...): the launch path serves the system
-    if (T <= 768 && (e = hipFuncSetAttribute((const void *)k_pcg2<768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    if (T > 768 && (e = hipFuncSetAttribute((const void *)k_pcg2<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+    for (int hot = 0; hot < 2; ++hot)      // (both instances of this block size: launch_pcg2 chooses per launch)
+        if ((e = hipFuncSetAttribute(pcg2_instance(T, hot != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
     if (T <= 768 && (e = hipFuncSetAttribute((const void *)k_sync_probe<768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
     if (T > 768 && (e = hipFuncSetAttribute((const void *)k_sync_probe<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    int per_cu = 0;     // (the kernel that will actually be launched with this LDS size)
-    e = T <= 768 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pcg2<768>, T, lds) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pcg2<1024>, T, lds);
-    if (e != hipSuccess) return e;
+    int per_cu = 0;     // (the kernels that will actually be launched with this LDS size: the tighter of the two instances)
+    for (int hot = 0; hot < 2; ++hot) {
+        int n = 0;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pcg2_instance(T, hot != 0), T, lds)) != hipSuccess) return e;
+        per_cu = hot ? std::min(per_cu, n) : n;
+    }
     if (per_cu < 1 || G > cus) return hipSuccess; // one block per CU keeps every block resident whatever the LDS split
     c->oc_G = G; c->oc_spb = spb; c->oc_T = T; c->oc_lds = lds;
     if ((e = c->oc_ubuf.alloc((size_t)2 * G * spb * 64 * 4)) != hipSuccess) return e;
@@ -792,6 +825,7 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
     c->oc_debug = env_flag("ADMM_HIP_OC_DEBUG", false);
     c->oc_always_verify = env_flag("ADMM_HIP_OC_VERIFY", false);      // A/B, tests: verify every pass (pcg_onchip2.hpp: kOc2TrustIters)
     c->oc_prof_block = env_int("ADMM_HIP_OC_PROF_BLOCK", 0);
+    c->oc_force_generic = env_flag("ADMM_HIP_OC_GENERIC", false);     // A/B, tests: the generic instance of k_pcg2 for every launch
     if (env_flag("ADMM_HIP_OC_PROF", false)) { if ((e = c->oc_prof.alloc(64 * 8)) != hipSuccess) return e; if ((e = c->oc_prof.zero()) != hipSuccess) return e; }
     if (plan.nbr_ok) {      // which blocks does every block gather from?
         if ((e = c->oc_nbr.upload(plan.nbr)) != hipSuccess) return e;
@@ -1071,9 +1105,9 @@ void launch_deflation(admm_hip_ctx *c, const double *b, double *x, bool have_res
     hipLaunchKernelGGL(k_defl_apply, dim3(blocks_for(c->nv)), dim3(256), 0, st, c->nv, k, c->defl_Z.p, c->defl_y.p, x);
 }
 
-int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x);
+int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x, bool loop);
 // The ADMM global solve with the recycled (Galerkin) warm start around the PCG (+ the end projection on the soft modes, when set).
-int launch_pcg_recycled(admm_hip_ctx *c, const double *b, double *x) {
+int launch_pcg_recycled(admm_hip_ctx *c, const double *b, double *x, bool loop = true) {      // loop: see OcRc
     // The Galerkin step on the soft modes ALSO IN FRONT of the solves of a frame whose bit is set in defl_start (ADMM_HIP_DEFL_START=mask at
     // create; default 2 = the SECOND solve of a frame).  That solve is ADMM's transient -- the first dual update of the frame moves the
     // right-hand side along the soft modes, by an amount the corrections of earlier frames do not predict -- and it alone took 65-69 of a
@@ -1083,13 +1117,13 @@ int launch_pcg_recycled(admm_hip_ctx *c, const double *b, double *x) {
     if (c->defl_start && !c->defl_start_hold && c->defl_k > 0 && c->rc_iter < 31 && ((c->defl_start >> c->rc_iter) & 1)) launch_deflation(c, b, x);
     c->defl_armed = false;
     c->big_rfin_valid = false;
-    const int rc = launch_pcg_recycled_impl(c, b, x);
+    const int rc = launch_pcg_recycled_impl(c, b, x, loop);
     // (fused into k_pcg2's epilogue when the on-chip kernel ran WITH it -- launch_pcg2 says so: a solve that went there without the recycled
     // basis, ADMM_HIP_NO_RECYCLE=1, or down the launch path gets the separate kernels)
     if (rc == 0 && c->defl_k > 0 && !c->defl_armed) launch_deflation(c, b, x, c->big_rfin_valid);
     return rc;
 }
-int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
+int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x, bool loop) {
     const int s = c->rc_iter;
     if (!c->rc_enabled) return launch_pcg(c, b, x, c->pcg_max_iters);
     hipStream_t st = c->stream;
@@ -1111,7 +1145,7 @@ int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
         add(s - 3, fr, s - 3 >= 0);
         add(s + 1, fr - 2, s + 1 < H && s + 1 < c->rc_prev2_valid);
         add(s - 4, fr, s - 4 >= 0);
-        OcRc rc; rc.on = true; rc.B = B; rc.Eslot = c->rc_Ef(s, fr); rc.Rslot = c->rc_Rf(s, fr);
+        OcRc rc; rc.on = true; rc.loop = loop; rc.B = B; rc.Eslot = c->rc_Ef(s, fr); rc.Rslot = c->rc_Rf(s, fr);
         const int r = launch_pcg_onchip(c, b, x, c->pcg_max_iters, rc);
         c->rc_iter = s + 1;
         return r;
@@ -1125,7 +1159,7 @@ int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x) {
     // prototype (experiments/first_solve_proto.py) gives 53 -> 19..26 iterations for the first solve, 30 -> 11..17 for the second.
     for (int q = s; q < kRc && q < c->rc_prev_valid && B.cnt < rc_pairs; ++q) { B.E[B.cnt] = c->rc_E(q); B.R[B.cnt] = c->rc_R(q); ++B.cnt; }
     if (c->oc_enabled) {   // (the plan's pairs live in its internal row order: k_rc_* cannot read them)   // projection, solve and the new pair in ONE persistent launch
-        OcRc rc; rc.on = true; rc.B = B; rc.Eslot = c->rc_E(s); rc.Rslot = c->rc_R(s);
+        OcRc rc; rc.on = true; rc.loop = loop; rc.B = B; rc.Eslot = c->rc_E(s); rc.Rslot = c->rc_R(s);
         const int r = launch_pcg_onchip(c, b, x, c->pcg_max_iters, rc);
         c->rc_iter = s + 1;
         return r;
@@ -1179,10 +1213,13 @@ int enqueue_dyn_detect(admm_hip_ctx *c, const double *x) {
 // profiles/r05_uzawa_column_lanes.txt).  Final assignment of the priorities: uz_make_lanes.
 int uz_lane_fit(admm_hip_ctx *c) {      // instances of k_pcg2 the chip holds at once
     if (c->uz_fit >= 0) return c->uz_fit;
-    int per_cu = 0;
-    const hipError_t e = c->oc_T <= 768 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pcg2<768>, c->oc_T, c->oc_lds)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pcg2<1024>, c->oc_T, c->oc_lds);
-    if (e != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 1; }
+    int per_cu = 0;      // (the lanes run the generic instance, the loop's own solves the hot one: the tighter of the two)
+    for (int hot = 0; hot < 2; ++hot) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pcg2_instance(c->oc_T, hot != 0), c->oc_T, c->oc_lds) != hipSuccess) { (void)hipGetLastError(); n = 0; }
+        per_cu = hot ? std::min(per_cu, n) : n;
+    }
+    if (per_cu <= 0) per_cu = 1;
     c->uz_fit = (int)std::min<long long>(64, (long long)per_cu * c->n_cus / std::max(1, c->oc_G));
     return c->uz_fit;
 }
@@ -1452,7 +1489,7 @@ int uz_ensure_columns(admm_hip_ctx *c, int n_missing) {
 // UzawaCG::solve (src/UzawaCG.hpp:57-125).  The Schur-CG loop is enqueued in chunks, its stop decision is taken on the device; A^-1 of
 // every iteration through cached columns of K^-1 (kernels.hpp: k_uz_cols_apply, k_uzc_*) or, without them, an on-chip PCG solve.
 // Returns the reference's iteration count via *iters.
-int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
+int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters, bool loop = true) {
     hipStream_t st = c->stream;
     const int nv = c->nv, gv = blocks_for(nv);
     *iters = 1;
@@ -1541,13 +1578,13 @@ int launch_uzawa(admm_hip_ctx *c, const double *b, double *x, int *iters) {
         if (hipMemsetAsync(c->uz_y.p, 0, nv * sizeof(double), st) != hipSuccess) return -1;
         c->uz_prev_hits = nh;
     }
-    if (nh == 0) return launch_pcg_recycled(c, b, x); // no constraints: one prefactored solve (:78-81)
+    if (nh == 0) return launch_pcg_recycled(c, b, x, loop); // no constraints: one prefactored solve (:78-81)
     hipLaunchKernelGGL(k_uz_ct, dim3(gv), dim3(256), 0, st, nv, 0, b, c->uz_cn.p, c->uz_y.p, c->uz_q1.p);       // q1 = b - C^T y
     if (dyn) launch_ct_dyn(c, nq, qlist, 0, c->uz_y.p, dface, dbary, c->uz_q1.p);
     // x = A^-1 q1, warm-started from the current x and -- like the contact-free solves -- projected on the recycled pairs first
     c->defl_start_hold = true;      // (with constraint rows the first solve's right-hand side b - C^T y is the multipliers' kick, not the soft-mode
                                     // transient of the free solve: the step in front buys nothing there -- cube100k_uzawa_floor 1 357 against 1 396)
-    const int rc_first = launch_pcg_recycled(c, c->uz_q1.p, x);
+    const int rc_first = launch_pcg_recycled(c, c->uz_q1.p, x, loop);
     c->defl_start_hold = false;
     if (rc_first) return -1;
     hipLaunchKernelGGL(k_uz_resid, dim3(gv), dim3(256), 0, st, nv, x, c->uz_cn.p, c->uz_cc.p, c->uz_r.p, c->uz_d.p, dface, dbary, c->uz_scal.p);
@@ -2998,18 +3035,18 @@ int admm_hip_detect_dynamic(admm_hip_ctx *c, const double *x, int32_t cap, int32
     return ADMM_HIP_OK;
 }
 
-static int launch_global(admm_hip_ctx *c, const double *b, double *x) {
+static int launch_global(admm_hip_ctx *c, const double *b, double *x, bool loop = true) {      // loop = false: admm_hip_global_solve (k_pcg2: the generic instance)
     if (c->linsolver == 1) {
         if (!c->dyn.empty()) return launch_gs_dynamic(c, b, x);
         launch_gs(c, b, x); return 0;
     }
     if (c->linsolver == 2) {
         int it = 1;
-        const int rc = launch_uzawa(c, b, x, &it);
+        const int rc = launch_uzawa(c, b, x, &it, loop);
         c->uz_iters_step += it;
         return rc;
     }
-    return launch_pcg_recycled(c, b, x);
+    return launch_pcg_recycled(c, b, x, loop);
 }
 
 // true: launch_global(c, c->b.p, c->curr.p) will reach launch_pcg2 with the recycled basis as the FIRST thing that reads b
@@ -3328,7 +3365,7 @@ int admm_hip_global_solve(admm_hip_ctx *c, const double *b, double *x_inout, int
     c->rc_prev_valid = 0; c->rc_prev2_valid = 0; c->rc_frame += 1; c->rc_iter = 0;   // stand-alone solve: nothing to recycle
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, kCntStepWords * sizeof(int), st));
     if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + kCntSchurIters, 0, sizeof(int), st));
-    if (launch_global(c, c->b.p, c->curr.p)) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
+    if (launch_global(c, c->b.p, c->curr.p, false)) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(x_inout, c->curr.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
     int h[kCntRing];
@@ -3336,6 +3373,23 @@ int admm_hip_global_solve(admm_hip_ctx *c, const double *b, double *x_inout, int
     HIP_TRY(hipStreamSynchronize(st));
     if (c->h_sig && c->h_sig[kSigAbort]) { c->h_sig[kSigAbort] = 0; return fail(ADMM_HIP_ERR_DEVICE, "PCG: a grid barrier of the on-chip solve timed out (is another persistent kernel sharing the GPU?)"); }
     if (iters) *iters = (c->linsolver == 1) ? h[kCntGsSweeps] : (c->linsolver == 2 ? c->uz_iters_step + h[kCntSchurIters] : h[kCntIters]);
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_pcg_instances(admm_hip_ctx *c, int32_t *last, int64_t *launches, int32_t *last_verifications) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "pcg_instances: NULL context");
+    if (last) *last = c->oc_last_instance;
+    if (launches) for (int i = 0; i < 4; ++i) launches[i] = c->oc_instance_launches[i];
+    if (last_verifications) {
+        *last_verifications = -1;
+        if (c->oc_last_instance) {      // (k_pcg2's report of the solve: alpha[0] = verifications of the true residual it ran)
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            CgScal h;
+            HIP_TRY(hipMemcpy(&h, c->cg_scal.p, sizeof(h), hipMemcpyDeviceToHost));
+            *last_verifications = (int32_t)h.alpha[0];
+        }
+    }
     return ADMM_HIP_OK;
 }
 

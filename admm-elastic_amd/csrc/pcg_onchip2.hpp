@@ -99,7 +99,12 @@ __device__ __forceinline__ void oc2_barrier_arrive(unsigned *bar) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(bar + 16 * ((int)blockIdx.x & 7), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int MAXT>
+// TWO INSTANCES per block size.  The generic one (HOT = false) carries every configuration.  The hot one fixes at compile time what the
+// ADMM loop of an on-chip context launches -- two-level preconditioner, neighbour hand-off, recycled warm start, no profiling stamps, no skip
+// word, records of at most two units per thread -- so that the arms it never takes hold no registers
+// across the pipelined loop; the block smoother's give-up word and the soft-mode end projection stay run-time.  launch_pcg2 (admm_hip.hip)
+// picks the instance per launch (pcg2_hot_ok); both run the same arithmetic in the same order.
+template <int MAXT, bool HOT>
 __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *red = (double *)smem;                   // [16][24] wave totals of up to 24 quantities
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     // cannot hoist): a handful of integer instructions per use, live for a few lines.
     auto otid = [&]() -> int { int t; asm volatile("v_mov_b32_e32 %0, %1" : "=v"(t) : "v"(tid)); return t; };
     auto opq = [](int x) -> int { int t; asm volatile("v_mov_b32_e32 %0, %1" : "=v"(t) : "v"(x)); return t; };
-    const bool prof = a.prof && (int)blockIdx.x == a.prof_block && tid == 0;
+    const bool prof = !HOT && a.prof && (int)blockIdx.x == a.prof_block && tid == 0;
     if (prof) a.prof[63 * 8 + 0] = wall_clock64();
     const int NV = a.vec_len;
     LdsD *vec = (LdsD *)(smem + kOc2Scratch);                    // [3][NV]: own entries [0, T), halo entries [T, T + nh)
@@ -176,7 +181,8 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     const int ub = a.n_rows * 32;           // bytes of one published-vector buffer
     __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc((void *)a.ubuf, 0, 2 * ub, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc((void *)a.part, 0, 2 * 8 * a.G * 8, 0x00020000);
-    const bool two_level = a.ainv != nullptr && a.nc <= 2 * T;
+    const bool two_level = HOT || (a.ainv != nullptr && a.nc <= 2 * T);
+    const bool handoff = HOT || a.nbr != nullptr, rc_on = HOT || a.rc_on != 0;
     __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc((void *)a.cbuf, 0, a.cbuf ? 2 * 3 * a.ncp * 8 : 0, 0x00020000);
 
     double rx[3], ru[3], rw[3], rp[3], rsv[3], rz[3], rq[3], rr[3];
@@ -196,7 +202,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     }
     unsigned *const bar = a.bar + 32 * 16 * (a.seq & 1);
     if (blockIdx.x == 0 && tid < 9) a.bar[32 * 16 * ((a.seq & 1) ^ 1) + 16 * (tid < 8 ? tid : 17)] = 0u;
-    if (a.skip && *a.skip) return;    // (after the clearing above: the next launch counts on the set this one cleared)
+    if (!HOT && a.skip && *a.skip) return;    // (after the clearing above: the next launch counts on the set this one cleared)
     if (tid < 3 * kOcSubK) { yw[tid] = 0.0; yw[3 * kOcSubK + tid] = 0.0; yz[tid] = 0.0; ycur[tid] = 0.0; }
     if (tid == 0) ictl[3] = a.counters[kCntTrustRevoked];      // (a SAMPLED verification of a short first pass failed: below)
     int ywp = 0;         // offset of the current y_w buffer (0 or 3 kOcSubK)
@@ -375,7 +381,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     auto rec_reduce = [&](int par, int nsum, const RecUnit &g0, const RecUnit &g1) {      // -> bc[0..nsum), valid after the NEXT block barrier
         double sa = g0.d[0] + g1.d[0], sb = g0.d[1] + g1.d[1];
         const int tid = otid(), n16 = 4 * a.G;
-        for (int o = tid + 2 * T; o < n16; o += T) {      // (blocks of few waves)
+        for (int o = tid + 2 * T; !HOT && o < n16; o += T) {      // (blocks of few waves; hot instance: 4 G <= 2 T)
             RecUnit g; g.v = __builtin_amdgcn_raw_buffer_load_b128(rs_p, par * a.G * 64 + o * 16, 0, 16);
             sa += g.d[0]; sb += g.d[1];
         }
@@ -473,10 +479,10 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     auto action = [&]() -> int { __syncthreads(); return __builtin_amdgcn_readfirstlane(ictl[2]); };
     // u = D^-1 (b - A x) from the x held in registers (x goes through the published copy: the columns are local indices);
     // leaves r . D^-1 r (and optionally b . D^-1 b) in q[0..5]
-    auto true_residual = [&](bool with_bnorm, double *q, double *ri_out) -> bool {
+    auto true_residual = [&](bool with_bnorm, double *q, double *ri_out, double *b_out = nullptr) -> bool {
         double ax[3];
         ++ph; publish(rx);
-        if (a.nbr) { if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) return false; }
+        if (handoff) { if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) return false; }
         else { ++be; if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) return false; }
         halo_and_rows(rx, ax);
 #pragma unroll
@@ -484,6 +490,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
             const double bj = live ? a.b[3 * (size_t)vi + j] : 0.0;
             const double ri = bj - ax[j];
             if (ri_out) ri_out[j] = ri;
+            if (b_out) b_out[j] = bj;
             ru[j] = rd[j] * ri;
             q[j] = ru[j] * ri;
             q[3 + j] = with_bnorm ? bj * rd[j] * bj : 0.0;
@@ -495,7 +502,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         // ---- start: TRUE residual of the warm start (after the recycled projection), stop test, w = A u ---------------
         {
             double q[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            if (!a.rc_on) { if (!true_residual(true, q, nullptr)) { aborted = true; break; } }
+            if (!rc_on) { if (!true_residual(true, q, nullptr)) { aborted = true; break; } }
             else {
                 // recycled warm start (see k_rc_* in kernels.hpp): A-orthogonal projection of the initial
                 // error on the stored exact pairs (E_j, R_j = A E_j): per axis G c = g, x += E c, r0 -= R c
@@ -510,11 +517,10 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         e[jj][ax] = on ? a.rc.E[jj][3 * (size_t)row + ax] : 0.0;
                         r[jj][ax] = on ? a.rc.R[jj][3 * (size_t)row + ax] : 0.0;
                     }
-                if (!true_residual(true, q, ri)) { aborted = true; break; }
+                if (!true_residual(true, q, ri, bj)) { aborted = true; break; }      // (also hands back this row's b)
                 if (prof) a.prof[62 * 8 + 0] = wall_clock64();
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    bj[j] = live ? a.b[3 * (size_t)vi + j] : 0.0;
                     if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }
                 }
                 if (cnt > 0) {
@@ -628,7 +634,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
             // u to the neighbours (hand-off, no barrier), w = A u, then ONE record: the stop-test sums and P^T w
             if (prof) a.prof[62 * 8 + 4] = wall_clock64();
             ++ph; publish(ru);
-            if (a.nbr) { if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) { aborted = true; break; } }
+            if (handoff) { if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) { aborted = true; break; } }
             else { ++be; if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; } }
             halo_and_rows(ru, rw);                   // w = A u
             if (prof) a.prof[62 * 8 + 5] = wall_clock64();
@@ -764,7 +770,11 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                 const int pass_it0 = iters;
                 double rho_best = 1e300;
                 int since = 0;
-                bool next_pass = false;
+                // THE ITERATION LOOP has one way out besides its cap: `why`, the decision every block took (or -1: a synchronisation was aborted).
+                // What the decision asks for -- verification, restart, hand-over to the classic form -- happens BEHIND the loop: inlined into it,
+                // those rare paths (each with its own copy of the residual and record helpers) and the flags their exits set took part in the
+                // loop's register allocation, which then kept p in scratch memory and copied the other vectors around once per iteration.
+                int why = 0;
                 while (iters < a.max_iters) {
                     OC2_STAMP(0);
                     double rn[3], sn[3];
@@ -776,11 +786,11 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         ++ph; publish(mm);
                     }
                     OC2_STAMP(1);
-                    if (a.nbr) {
-                        if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) { aborted = true; break; }
+                    if (handoff) {
+                        if (__builtin_expect(!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig), 0)) { why = -1; break; }
                     } else {   // more than 64 neighbour blocks somewhere: a grid barrier orders the exchange
                         ++be;
-                        if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; }
+                        if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) { why = -1; break; }
                     }
                     OC2_STAMP(2);
                     halo_and_rows_self_from_vec(rn);                                             // n = A m (m's own entry is in the local vector)
@@ -803,7 +813,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                     // S w is then carried by the recurrences below like w itself, no smoothing on the critical path
                     oc2_barrier_arrive(bar);
                     smooth(rn, sn);
-                    if (!oc_barrier_wait(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; }
+                    if (__builtin_expect(!oc_barrier_wait(bar, be, a.G, ok_lds, a.sig), 0)) { why = -1; break; }
                     OC2_STAMP(5);
                     if (two_level) reduce_and_coarse(par, 7, ar);                                // the sums, and ycur = Ac^-1 P^T n
                     else reduce_records(par, 7);
@@ -834,27 +844,8 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         rho_best = fmin(rho_best, rs);
                         if (lane == 0) ictl[2] = act;
                     }
-                    const int act = action();
-                    if (act == 2) {
-                        if (blockIdx.x == 0 && otid() == 0 && smoothing) a.counters[kCntSmootherOff] = 1;
-                        entry_restart = true; go_classic = true; break;
-                    }
-                    if (act == 4) {                  // converged by the recursive residual of a short first pass: no verification
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) ru[j] = rd[j] * rr[j];
-                        conv = true; break;
-                    }
-                    if (act == 1) {
-                        const int v = verify();      // leaves u = D^-1 (true residual)
-                        if (v < 0) { aborted = true; break; }
-                        if (v == 1) { conv = true; break; }
-                        if (passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[kCntTrustRevoked] = 1; atomicAdd(a.counters + kCntFailedChecks, 1); }
-                        fresh = true;                // the true residual replaces the recursive one: beta = 0
-                        if (++passes >= 4) { go_classic = true; break; }
-                        pass_start = 3.0 * ctl[1];   // (the largest axis ratio of the verification, as a bound of the sum)
-                        next_pass = true;
-                        break;
-                    }
+                    why = action();
+                    if (__builtin_expect(why != 0, 0)) break;
                     const int oa_ = opq(oa);
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
@@ -888,7 +879,25 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                     if (prof) ++prof_n;
                     OC2_MARK(8);
                 }
-                if (!next_pass) break;
+                if (why == 0) break;             // iteration cap
+                if (why < 0) { aborted = true; break; }
+                if (why == 2) {
+                    if (blockIdx.x == 0 && otid() == 0 && smoothing) a.counters[kCntSmootherOff] = 1;
+                    entry_restart = true; go_classic = true; break;
+                }
+                if (why == 4) {                  // converged by the recursive residual of a short first pass: no verification
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) ru[j] = rd[j] * rr[j];
+                    conv = true; break;
+                }
+                // why == 1: the recursive residual reports the target, or stagnates
+                const int v = verify();          // leaves u = D^-1 (true residual)
+                if (v < 0) { aborted = true; break; }
+                if (v == 1) { conv = true; break; }
+                if (passes == 0 && a.tol2 >= kOc2TrustTol2 && iters - pass_it0 <= kOc2TrustIters && blockIdx.x == 0 && otid() == 0) { a.counters[kCntTrustRevoked] = 1; atomicAdd(a.counters + kCntFailedChecks, 1); }
+                fresh = true;                    // the true residual replaces the recursive one: beta = 0
+                if (++passes >= 4) { go_classic = true; break; }
+                pass_start = 3.0 * ctl[1];       // (the largest axis ratio of the verification, as a bound of the sum)
             }
             if (!conv && !go_classic && !aborted) {   // iteration cap: leave u = D^-1 r behind (epilogue, recycled pair)
 #pragma unroll
@@ -985,7 +994,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     const bool proj = a.defl_k > 0 && conv && !aborted;
     const int K = a.defl_k;
     double xs_in[3] = {0.0, 0.0, 0.0}, r0_in[3] = {0.0, 0.0, 0.0};
-    if (live && a.rc_on) {
+    if (live && rc_on) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)row + j; xs_in[j] = a.rc_xs[i]; r0_in[j] = a.rc_r0[i]; }
     }
@@ -1006,7 +1015,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         if (tid + T < K * K) gv[1] = a.defl_Ginv[tid + T];
     }
     double pe[3] = {0.0, 0.0, 0.0}, pr[3] = {0.0, 0.0, 0.0};
-    if (live && a.rc_on) {
+    if (live && rc_on) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             pe[j] = rx[j] - xs_in[j];
@@ -1109,8 +1118,12 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     }
     if (live) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { a.x[3 * (size_t)vi + j] = rx[j]; a.u_out[3 * (size_t)vi + j] = ru[j]; }
-        if (a.rc_on) {
+        for (int j = 0; j < 3; ++j) {
+            a.x[3 * (size_t)vi + j] = rx[j];
+            if (!HOT) a.u_out[3 * (size_t)vi + j] = ru[j];      // (D^-1 r_final: what k_rc_record and launch_deflation(have_resid) read after a launch-path solve.  Nothing reads it
+                                                                // after a solve that ran with the recycled start: it wrote its own pair and ends with its own projection)
+        }
+        if (rc_on) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)row + j; a.rc_Eslot[i] = pe[j]; a.rc_Rslot[i] = pr[j]; }
         }

@@ -700,6 +700,15 @@ class Solver:
         check(lib().admm_hip_pcg_findings(self._ctx, C.byref(a), C.byref(b), C.byref(n)))
         return dict(smoother_given_up=bool(a.value), trust_revoked=bool(b.value), failed_checks=n.value)
 
+    def pcg_instances(self):
+        """admm_hip_pcg_instances: dict(last, hot, generic, lane_hot, lane_generic, last_verifications) -- which instance of the on-chip PCG
+        kernel served the last solve on the context's own stream ('none', 'generic', 'hot'), the launches of each since initialize, and how
+        often that last solve verified its true residual (-1: no solve yet)."""
+        self._need_ctx()
+        last = C.c_int32(0); n = (C.c_int64 * 4)(); v = C.c_int32(0)
+        check(lib().admm_hip_pcg_instances(self._ctx, C.byref(last), n, C.byref(v)))
+        return dict(last=("none", "generic", "hot")[last.value], hot=n[0], generic=n[1], lane_hot=n[2], lane_generic=n[3], last_verifications=v.value)
+
     def probe_sync(self, n=200):
         """admm_hip_probe_sync: (us per all-to-all, us per vector exchange, plan statistics dict) of the on-chip PCG."""
         self._need_ctx()

@@ -349,6 +349,15 @@ int admm_hip_persistent_launches(const admm_hip_ctx *ctx, int64_t *pcg, int64_t 
  * they switched the smoother off for every context that computed its modes).  Synchronises the stream. */
 int admm_hip_pcg_findings(admm_hip_ctx *ctx, int32_t *smoother_given_up, int32_t *trust_revoked, int64_t *failed_checks);
 
+/* Which instance of the on-chip PCG kernel served this context's solves (no reference counterpart; diagnostics, tests).  k_pcg2 exists twice per
+ * block size: a generic instance, and a hot one with the configuration of the ADMM loop's solves fixed at compile time (same arithmetic, same
+ * results; ADMM_HIP_OC_GENERIC=1 forces the generic one).  *last: the instance of the last solve launched on the context's own stream -- 0 none
+ * yet, 1 generic, 2 hot; launches[4]: launches since admm_hip_create of the hot and of the generic instance, and how many of each ran on
+ * UzawaCG's column lanes (the hot one never does); *last_verifications: how often that last solve left its pipelined iteration to verify the
+ * true residual -- the rare path both instances keep behind the iteration loop (-1: no on-chip solve yet; asking for it synchronises the
+ * stream).  Any pointer may be NULL. */
+int admm_hip_pcg_instances(admm_hip_ctx *ctx, int32_t *last, int64_t *launches, int32_t *last_verifications);
+
 /* Device memory the library holds in this process (no reference counterpart; diagnostics, tests): the number of live device buffers of all
  * contexts and their total size in bytes.  A destroyed context leaves none of its own behind.  Any pointer may be NULL. */
 int admm_hip_device_buffers(int64_t *buffers, int64_t *bytes);
