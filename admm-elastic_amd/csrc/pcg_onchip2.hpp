@@ -107,8 +107,8 @@ __device__ __forceinline__ void oc2_barrier_arrive(unsigned *bar) {
 template <int MAXT, bool HOT>
 __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double *red = (double *)smem;                   // [16][24] wave totals of up to 24 quantities
-    double *res24 = (double *)(smem + 3072);        // [24] their block totals
+    double *red = (double *)smem;                   // [16][24] wave totals of up to 24 quantities (their block totals stay in registers: cross_wave_total);
+                                                    // the rows of waves that do not run stay +0.0 from the start of the kernel to the epilogue
     double *bc = (double *)(smem + 3328);           // [8] reduced scalars of the current phase
     double *sc = (double *)(smem + 3392);           // [8] gamma_prev[3], alpha_prev[3]
     double *gbl = (double *)(smem + 3456);          // [4] b . D^-1 b per axis
@@ -204,6 +204,8 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     if (blockIdx.x == 0 && tid < 9) a.bar[32 * 16 * ((a.seq & 1) ^ 1) + 16 * (tid < 8 ? tid : 17)] = 0u;
     if (!HOT && a.skip && *a.skip) return;    // (after the clearing above: the next launch counts on the set this one cleared)
     if (tid < 3 * kOcSubK) { yw[tid] = 0.0; yw[3 * kOcSubK + tid] = 0.0; yz[tid] = 0.0; ycur[tid] = 0.0; }
+    for (int i = tid; i < 16 * 24; i += T) red[i] = 0.0;      // (cross_wave_total reads the rows of all MAXT / 64 waves; the first partials are written behind
+                                                              // the block barriers of the entry residual)
     if (tid == 0) ictl[3] = a.counters[kCntTrustRevoked];      // (a SAMPLED verification of a short first pass failed: below)
     int ywp = 0;         // offset of the current y_w buffer (0 or 3 kOcSubK)
     unsigned ph = 0;     // publish phase of the vector: buffer parity = ph & 1, tag of the neighbour flags
@@ -306,11 +308,28 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         for (int j = 0; j < 3; ++j) out[j] = rd[j] * fma(-a.sm_b, acc[j], a.sm_ab * v[j]);
         __syncthreads();   // the local vector is rewritten by the next publish
     };
-    // block totals of 8 NG quantities -> res24 (valid after the call for all threads); fixed order -> deterministic.
+    // One quantity's total over the block's waves, from their partials in LDS (p[24 k] = wave k's): sm = 0.0; sm += p[0]; sm += p[1]; ...
+    // in exactly that order, for every block the same -> deterministic.  Unrolled to the instance's MAXT / 64 waves, so that the reads are
+    // independent of the adds and go out TOGETHER (one LDS latency, then the chain of adds) -- as a loop over the run-time nw it was one
+    // LDS round trip per wave, twelve in a row on the bench body, with the rest of the block waiting at the next barrier.  A slot k >= nw
+    // contributes +0.0: a sum that starts from +0.0 can never be -0.0 (x + y is -0.0 only when both are), so x + 0.0 == x bit for bit and
+    // the total is what the loop over nw gave.  The +0.0 is READ, not selected: the rows of `red` that no wave of this block writes are
+    // zeroed once, below.  (Selected -- sm += k < nw ? t[k] : 0.0 -- the twelve wave-uniform masks are loop-invariant, were hoisted out of the
+    // iteration loop and paid for in SGPR spills: 57 -> 130 on the hot <768> instance, 20 -> 51 lane reads per iteration.)
+    auto cross_wave_total = [&](const double *p) -> double {      // p = red + quantity: the partials are 24 doubles apart
+        double sm = 0.0;
+#pragma unroll
+        for (int k = 0; k < MAXT / 64; ++k) sm += p[k * 24];
+        return sm;
+    };
+    // block totals of 8 NG quantities: thread tid < 8 NG RETURNS the total of quantity tid (every caller hands total tid on from thread tid
+    // -- to global memory or to LDS -- so it never goes through LDS itself); fixed order -> deterministic.
+    // ONE block barrier inside (wave partials -> the totalling threads).  None behind the totals: the caller sees to a block barrier between
+    // this call's reads of `red` (threads 0 .. 8 NG - 1) and the next call's writes -- the one its own synchronisation brings anyway.
     // The quantities are asked for EIGHT AT A TIME (gen(h, q8) fills group h) with a scheduling barrier between the groups: handed
     // over as one array, all 24 were formed before the first reduction started -- 48 registers on top of the ten recurrence
     // vectors of the iteration, which the allocator paid for by keeping part of THEM in scratch memory.
-    auto block_sums_gen = [&](auto gen, auto ng_tag) {
+    auto block_sums_gen = [&](auto gen, auto ng_tag) -> double {
         constexpr int NG = decltype(ng_tag)::value;
 #pragma unroll
         for (int h = 0; h < NG; ++h) {
@@ -326,28 +345,24 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();
+        __syncthreads();      // red: lanes 0..3 of every wave -> threads 0 .. 8 NG - 1
         const int tid = otid();
-        if (tid < 8 * NG) {
-            double sm = 0.0;
-            for (int k = 0; k < nw; ++k) sm += red[k * 24 + tid];
-            res24[tid] = sm;
-        }
-        __syncthreads();
+        return tid < 8 * NG ? cross_wave_total(red + tid) : 0.0;
     };
-    auto block_sums = [&](const double *q24, auto ng_tag) {
-        block_sums_gen([&](int h, double *q8) {
+    auto block_sums = [&](const double *q24, auto ng_tag) -> double {
+        return block_sums_gen([&](int h, double *q8) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) q8[i] = q24[8 * h + i];
         }, ng_tag);
     };
-    auto block_sums24 = [&](const double *q24) { block_sums(q24, std::integral_constant<int, 3>()); };
+    auto block_sums24 = [&](const double *q24) -> double { return block_sums(q24, std::integral_constant<int, 3>()); };
     // this block's record: q7[0..6] -> part (parity par) and, two-level, P^T v -> cbuf (parity par)
+    // Every caller follows with a grid-barrier arrival (oc_barrier / oc2_barrier_arrive), whose block barrier is the one block_sums_gen asks for.
     // (with_v is a flag, not "v or nullptr": an array whose address is selected against nullptr stays in scratch memory -- the
     // n of every iteration did, and came back through twelve conditional scratch loads)
     const double zero3[3] = {0.0, 0.0, 0.0};
     auto publish_record = [&](const double *q7, const double *v, bool with_v, int par) {
-        block_sums_gen([&](int h, double *q8) {     // groups: [q7, 0] [aggregates 0, 1 and x, y of 2] [z of 2, aggregate 3, 0 ...]
+        const double tot = block_sums_gen([&](int h, double *q8) {     // groups: [q7, 0] [aggregates 0, 1 and x, y of 2] [z of 2, aggregate 3, 0 ...]
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int f = 8 * h + i;                       // compile-time after unrolling
@@ -359,18 +374,18 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
             }
         }, std::integral_constant<int, 3>());
         const int tid = otid();
-        if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, res24[tid]);      // (res24[7] = 0: the chunk is written whole)
+        if (tid < 8) oc_store_sc1(rs_p, ((par * a.G + (int)blockIdx.x) * 8 + tid) * 8, tot);      // (total 7 = 0: the chunk is written whole)
         else if (with_v && tid >= 8 && tid < 8 + 3 * kOcSubK) {
             const int ag = (tid - 8) / 3, j = (tid - 8) - 3 * ag;
-            oc_store_sc1(rs_c, ((par * 3 + j) * a.ncp + (int)blockIdx.x * kOcSubK + ag) * 8, res24[tid]);
+            oc_store_sc1(rs_c, ((par * 3 + j) * a.ncp + (int)blockIdx.x * kOcSubK + ag) * 8, tot);
         }
     };
     // after the grid barrier: bc[0..nsum) = the global sums of the records of parity par
     // The records of all blocks, chunk-wise: the buffer of one parity is 4 G units of 16 bytes (unit o = sums 2 (o & 3), 2 (o & 3) + 1 of block
     // o >> 2); thread tid takes the units tid, tid + T, ... -- T is a multiple of four, so all of them carry the SAME pair of sums -- one or two
-    // 16-byte loads per thread instead of four 8-byte loads per lane of seven waves, every sector asked for once per block.  rec_reduce then adds
+    // 16-byte loads per thread instead of four 8-byte loads per lane of seven waves, every sector asked for once per block.  rec_partials then adds
     // up the pairs: over the lanes of equal lane & 3 inside each row of sixteen (two DPP shifts), over the four rows (two lane exchanges), over the
-    // waves (LDS, the idle local vector).  The same order in every block: the same bits, the same decisions.
+    // waves (LDS).  The same order in every block: the same bits, the same decisions.
     union RecUnit { double d[2]; v4u v; };
     auto rec_issue = [&](int par, RecUnit &g0, RecUnit &g1) {
         const int tid = otid(), n16 = 4 * a.G;
@@ -378,7 +393,11 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         if (tid < n16) g0.v = __builtin_amdgcn_raw_buffer_load_b128(rs_p, par * a.G * 64 + tid * 16, 0, 16);
         if (tid + T < n16) g1.v = __builtin_amdgcn_raw_buffer_load_b128(rs_p, par * a.G * 64 + (tid + T) * 16, 0, 16);
     };
-    auto rec_reduce = [&](int par, int nsum, const RecUnit &g0, const RecUnit &g1) {      // -> bc[0..nsum), valid after the NEXT block barrier
+    // rec_partials: this wave's sums -> columns 16..23 of its row of `red` (free here: the coarse rows that are summed next to them take
+    // columns 0..15, and a record's 24 totals were read before the block barrier of its grid-barrier arrival); after a block barrier
+    // rec_total: bc[0..nsum), formed by the first threads of the block's LAST wave (the first threads of wave 0 total the coarse rows at the
+    // same time, reduce_and_coarse) and valid after the NEXT block barrier
+    auto rec_partials = [&](int par, const RecUnit &g0, const RecUnit &g1) {
         double sa = g0.d[0] + g1.d[0], sb = g0.d[1] + g1.d[1];
         const int tid = otid(), n16 = 4 * a.G;
         for (int o = tid + 2 * T; !HOT && o < n16; o += T) {      // (blocks of few waves; hot instance: 4 G <= 2 T)
@@ -389,21 +408,20 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         sa += dpp_f64<0x118>(sa); sb += dpp_f64<0x118>(sb);      // row_shr:8 -> lanes 12..15 of a row: the row's total of their pair
         sa += __shfl_xor(sa, 16, 64); sb += __shfl_xor(sb, 16, 64);
         sa += __shfl_xor(sa, 32, 64); sb += __shfl_xor(sb, 32, 64);
-        double *red2 = (double *)(smem + kOc2Scratch);      // [waves][8], in the idle local vector
         const int lane = tid & 63;
-        if (lane >= 12 && lane < 16) { red2[(tid >> 6) * 8 + 2 * (lane & 3)] = sa; red2[(tid >> 6) * 8 + 2 * (lane & 3) + 1] = sb; }
-        __syncthreads();
-        if (tid < nsum) {
-            double sm = 0.0;
-            for (int k = 0; k < nw; ++k) sm += red2[k * 8 + tid];
-            bc[tid] = sm;
-        }
+        if (lane >= 12 && lane < 16) { double *dst = red + (tid >> 6) * 24 + 16 + 2 * (lane & 3); dst[0] = sa; dst[1] = sb; }
+    };
+    auto rec_total = [&](int nsum) {
+        const int t = otid() - 64 * (nw - 1);
+        if (t >= 0 && t < nsum) bc[t] = cross_wave_total(red + 16 + t);
     };
     auto reduce_records = [&](int par, int nsum) {
         RecUnit g0, g1;
         rec_issue(par, g0, g1);
-        rec_reduce(par, nsum, g0, g1);
-        __syncthreads();
+        rec_partials(par, g0, g1);
+        __syncthreads();      // red (columns 16..23): every wave -> the last wave's first threads
+        rec_total(nsum);
+        __syncthreads();      // bc -> every thread
     };
     // The rows of Ac^-1 of this block's aggregates, columns tid and tid + T: constant over the solve, fetched (L2) ahead
     // of the grid barrier so that their latency hides behind it
@@ -419,6 +437,11 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     };
     // after the grid barrier: bc[0..nsum) = global sums of the records, ycur = (rows of Ac^-1 of this block's aggregates) x
     // (published coarse vector), all of parity par.  Every global load is issued before the first use.
+    // The record sums and the coarse rows do not depend on each other: the wave partials of both go to LDS in one round (columns 16..23 and 0..15
+    // of `red`) and are totalled behind ONE block barrier by different waves; a second one hands bc and ycur to every thread.
+    //   barrier 1 orders  red: its writers (lanes 12..15 / 0..3 of every wave) -> the totalling threads (last wave / wave 0);
+    //   barrier 2 orders  bc, ycur: the totalling threads -> every thread (decision, prolongation, coarse recurrences); it is also the barrier
+    //             block_sums_gen asks for between its reads of red and the next writes (the next record).
     auto reduce_and_coarse = [&](int par, int nsum, const AinvRows &ar) {
         double cn[2][3];
         const int tid = otid();
@@ -430,9 +453,9 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) cn[it][j] = c < a.nc ? oc_load_sc1_f64(rs_c, ((par * 3 + j) * a.ncp + c) * 8) : 0.0;
         }
-        if (nsum > 0) rec_reduce(par, nsum, g0, g1);      // (bc is read behind the block barriers of the coarse rows below)
+        if (nsum > 0) rec_partials(par, g0, g1);
         __builtin_amdgcn_sched_barrier(0);     // (the record sums are done and their registers free before the coarse rows start)
-        block_sums_gen([&](int h, double *q8) {
+        const double tot = block_sums_gen([&](int h, double *q8) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int f = 8 * h + i, ag = f / 3, j = f % 3;          // compile-time after unrolling
@@ -440,7 +463,8 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                 else q8[i] = 0.0;
             }
         }, std::integral_constant<int, 2>());
-        if (otid() < 3 * kOcSubK) { const int t = otid(); ycur[t] = res24[t]; }
+        if (otid() < 3 * kOcSubK) { const int t = otid(); ycur[t] = tot; }
+        if (nsum > 0) rec_total(nsum);
         __syncthreads();
     };
     // y = (P Ac^-1 P^T v) on this thread's row: one all-to-all (its own grid barrier)
@@ -521,7 +545,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                 if (prof) a.prof[62 * 8 + 0] = wall_clock64();
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }
+                    if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }      // (the entry x needs no copy: it stays in a.x until the epilogue has read it)
                 }
                 if (cnt > 0) {
                     __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void *)a.rc_part, 0, 72 * a.G * 8, 0x00020000);
@@ -544,8 +568,10 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                                    : (qi == NG_ + kRc) ? ri[ax] * rd[ax] * ri[ax]
                                    : bj[ax] * rd[ax] * bj[ax];
                         }
-                        block_sums24(q24);
-                        if (tid < 24) oc_store_sc1(rs_r, ((24 * g24 + tid) * a.G + (int)blockIdx.x) * 8, res24[tid]);
+                        const double tot = block_sums24(q24);
+                        if (tid < 24) oc_store_sc1(rs_r, ((24 * g24 + tid) * a.G + (int)blockIdx.x) * 8, tot);
+                        if (g24 == 0) __syncthreads();      // red: the first round's totals are read before the second round's partials are written
+                                                            // (the second round's reads are followed by the block barrier of oc_barrier below)
                     }
                     if (prof) a.prof[62 * 8 + 1] = wall_clock64();
                     ++be;
@@ -996,7 +1022,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     double xs_in[3] = {0.0, 0.0, 0.0}, r0_in[3] = {0.0, 0.0, 0.0};
     if (live && rc_on) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)row + j; xs_in[j] = a.rc_xs[i]; r0_in[j] = a.rc_r0[i]; }
+        for (int j = 0; j < 3; ++j) { xs_in[j] = a.rc_xs[3 * (size_t)row + j]; r0_in[j] = a.rc_r0[3 * (size_t)row + j]; }      // (x is written once, below, behind this load: the entry x)
     }
     float zw[MPW][SPBMAX], zmine[kOc2DeflMax];
     double gv[2] = {0.0, 0.0};
