@@ -383,6 +383,13 @@ struct admm_hip_ctx {
     // energy / ADMM monitor (monitor.hpp; admm_hip_energy, admm_hip_residuals, admm_hip_set_monitor).  h_kst, pin_vert_d: rest data only the
     // monitor reads (the hinges' stiffness, pin term -> vertex), uploaded at create; everything else is allocated by the first call that needs it
     int mon_mode = 0, mon_n = 0;      // mode in effect from the next step; records the last step wrote
+    // early exit of the ADMM loop (admm_hip_set_admm_stop; monitor.hpp: admm_stop_test, k_mon_decide; kernels.hpp: kCntAdmmStop)
+    double stop_tol = 0.0; int stop_min = 1;      // in effect from the next step; tol = 0: off
+    int stop_last = 0, stop_on_dev = 0;           // the last step: iterations executed; 1 = the remaining ones were skipped on the device
+    bool stop_host = false;                       // ADMM_HIP_STOP_HOST=1 (read at create): every path decides on the host
+    const int *stop_dev = nullptr;                // while step_impl enqueues a step that skips on the device: the stop word -- the launch helpers
+                                                  // then take the STOP instantiations (k_pcg2: the generic instance with Oc2Args::skip)
+    hipEvent_t ev_stop = nullptr;                 // behind k_mon_decide, on the paths that decide on the host
     DevBuf<double> h_kst; DevBuf<int> pin_vert_d;
     DevBuf<double> mon_tzp, mon_rzp, mon_hzp, mon_pzp, mon_pz6;   // z_prev per family (pins: room for the reference's 6 rows), pin z in the reference's row layout
     DevBuf<double> mon_part, mon_rec, mon_out, mon_term;          // block partials, records [admm_iters][8], one result [8], per-term energies
@@ -401,6 +408,7 @@ struct admm_hip_ctx {
         if (ar_host) (void)hipHostFree(ar_host);
         if (ev_coll0) (void)hipEventDestroy(ev_coll0);
         if (ev_coll1) (void)hipEventDestroy(ev_coll1);
+        if (ev_stop) (void)hipEventDestroy(ev_stop);
         if (ev_step0) (void)hipEventDestroy(ev_step0);
         if (ev_step1) (void)hipEventDestroy(ev_step1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -418,13 +426,13 @@ inline int blocks_for(int n) { return (n + 255) / 256; }
 SellA sell_arg(const SellDev &S) { return SellA{S.n_rows, S.n_slices, S.ptr.p, S.w.p, S.idx.p, S.val.p}; }
 
 // ---- launch helpers (all on ctx->stream) -------------------------------------------------------------
-template <bool WRITE_Z, bool REST>
+template <bool WRITE_Z, bool REST, bool STOP = false>
 void launch_local_impl(admm_hip_ctx *c) {
     hipStream_t st = c->stream;
     if (c->nt > 0) {
         const int b0 = c->kind_begin[0], b1 = c->kind_begin[1], b2 = c->kind_begin[2], b3 = c->kind_begin[3];
         TetArgs a{c->ldt, c->t_idx.p, c->t_Binv.p, c->t_u.p, c->t_z.p, c->t_sc.p, c->t_mat.p, c->mats.p, c->curr.p, c->t_x0.p,
-                  c->ch_ent.p, c->ch_group.p, c->ch_rec.p, c->t_rec.p, 0, c->spl_tab.p, nullptr, 0};
+                  c->ch_ent.p, c->ch_group.p, c->ch_rec.p, c->t_rec.p, 0, c->spl_tab.p, nullptr, 0, c->stop_dev};
         auto stamp = [&]() {   // the next launch gets its own pair of stamp arrays
             if (c->timing && c->lk_launch < c->lk_cap) { a.ts = c->lk_ts.p + (size_t)c->lk_launch * 2 * c->lk_tsn; a.ts_n = c->lk_tsn; c->lk_launch += 1; }
             else a.ts = nullptr;
@@ -436,13 +444,13 @@ void launch_local_impl(admm_hip_ctx *c) {
         const int dom = b3 > b0 ? 0 : b4 > b3 ? 3 : 4;
         if (b5 > b4) {    // SplineTet splines with a compression term, tabulated splines, stable Neo-Hookean: their own launch
             stamp(); a.chunk0 = c->chunk_base[4];
-            if (dom == 4 && c->lt_k0) { hipExtLaunchKernelGGL((k_local_tets<4, WRITE_Z, REST>), dim3(blocks_for(b5 - b4)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, b4, b5, a); c->lt_taken = true; }
-            else hipLaunchKernelGGL((k_local_tets<4, WRITE_Z, REST>), dim3(blocks_for(b5 - b4)), dim3(256), 0, st, b4, b5, a);
+            if (dom == 4 && c->lt_k0) { hipExtLaunchKernelGGL((k_local_tets<4, WRITE_Z, REST, STOP>), dim3(blocks_for(b5 - b4)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, b4, b5, a); c->lt_taken = true; }
+            else hipLaunchKernelGGL((k_local_tets<4, WRITE_Z, REST, STOP>), dim3(blocks_for(b5 - b4)), dim3(256), 0, st, b4, b5, a);
         }
         if (b4 > b3) {    // co-rotated spline tets: their own launch (no BASELINE config mixes them in)
             stamp(); a.chunk0 = c->chunk_base[3];
-            if (dom == 3 && c->lt_k0) { hipExtLaunchKernelGGL((k_local_tets<3, WRITE_Z, REST>), dim3(blocks_for(b4 - b3)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, b3, b4, a); c->lt_taken = true; }
-            else hipLaunchKernelGGL((k_local_tets<3, WRITE_Z, REST>), dim3(blocks_for(b4 - b3)), dim3(256), 0, st, b3, b4, a);
+            if (dom == 3 && c->lt_k0) { hipExtLaunchKernelGGL((k_local_tets<3, WRITE_Z, REST, STOP>), dim3(blocks_for(b4 - b3)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, b3, b4, a); c->lt_taken = true; }
+            else hipLaunchKernelGGL((k_local_tets<3, WRITE_Z, REST, STOP>), dim3(blocks_for(b4 - b3)), dim3(256), 0, st, b3, b4, a);
         }
         if (b3 > b0) stamp();
         a.chunk0 = b1 > b0 ? 0 : b2 > b1 ? c->chunk_base[1] : c->chunk_base[2];   // (fused: chunks 0 .. of the models it covers)
@@ -451,33 +459,36 @@ void launch_local_impl(admm_hip_ctx *c) {
         if (k0 && b3 > b0) c->lt_taken = true;
         if (kinds >= 2) { // mixed scene: one launch over all models
             const int n0 = blocks_for(b1 - b0), n1 = blocks_for(b2 - b1), n2 = blocks_for(b3 - b2);
-            if (k0) hipExtLaunchKernelGGL((k_local_tets_fused<WRITE_Z, REST>), dim3(n0 + n1 + n2), dim3(256), 0, st, k0, k1, 0, b0, b1, b2, b3, n0, n0 + n1, a);
-            else hipLaunchKernelGGL((k_local_tets_fused<WRITE_Z, REST>), dim3(n0 + n1 + n2), dim3(256), 0, st, b0, b1, b2, b3, n0, n0 + n1, a);
+            if (k0) hipExtLaunchKernelGGL((k_local_tets_fused<WRITE_Z, REST, STOP>), dim3(n0 + n1 + n2), dim3(256), 0, st, k0, k1, 0, b0, b1, b2, b3, n0, n0 + n1, a);
+            else hipLaunchKernelGGL((k_local_tets_fused<WRITE_Z, REST, STOP>), dim3(n0 + n1 + n2), dim3(256), 0, st, b0, b1, b2, b3, n0, n0 + n1, a);
         } else if (b1 > b0) {
-            if (k0) hipExtLaunchKernelGGL((k_local_tets<0, WRITE_Z, REST>), dim3(blocks_for(b1 - b0)), dim3(256), 0, st, k0, k1, 0, b0, b1, a);
-            else hipLaunchKernelGGL((k_local_tets<0, WRITE_Z, REST>), dim3(blocks_for(b1 - b0)), dim3(256), 0, st, b0, b1, a);
+            if (k0) hipExtLaunchKernelGGL((k_local_tets<0, WRITE_Z, REST, STOP>), dim3(blocks_for(b1 - b0)), dim3(256), 0, st, k0, k1, 0, b0, b1, a);
+            else hipLaunchKernelGGL((k_local_tets<0, WRITE_Z, REST, STOP>), dim3(blocks_for(b1 - b0)), dim3(256), 0, st, b0, b1, a);
         } else if (b2 > b1) {
-            if (k0) hipExtLaunchKernelGGL((k_local_tets<1, WRITE_Z, REST>), dim3(blocks_for(b2 - b1)), dim3(256), 0, st, k0, k1, 0, b1, b2, a);
-            else hipLaunchKernelGGL((k_local_tets<1, WRITE_Z, REST>), dim3(blocks_for(b2 - b1)), dim3(256), 0, st, b1, b2, a);
+            if (k0) hipExtLaunchKernelGGL((k_local_tets<1, WRITE_Z, REST, STOP>), dim3(blocks_for(b2 - b1)), dim3(256), 0, st, k0, k1, 0, b1, b2, a);
+            else hipLaunchKernelGGL((k_local_tets<1, WRITE_Z, REST, STOP>), dim3(blocks_for(b2 - b1)), dim3(256), 0, st, b1, b2, a);
         } else if (b3 > b2) {
-            if (k0) hipExtLaunchKernelGGL((k_local_tets<2, WRITE_Z, REST>), dim3(blocks_for(b3 - b2)), dim3(256), 0, st, k0, k1, 0, b2, b3, a);
-            else hipLaunchKernelGGL((k_local_tets<2, WRITE_Z, REST>), dim3(blocks_for(b3 - b2)), dim3(256), 0, st, b2, b3, a);
+            if (k0) hipExtLaunchKernelGGL((k_local_tets<2, WRITE_Z, REST, STOP>), dim3(blocks_for(b3 - b2)), dim3(256), 0, st, k0, k1, 0, b2, b3, a);
+            else hipLaunchKernelGGL((k_local_tets<2, WRITE_Z, REST, STOP>), dim3(blocks_for(b3 - b2)), dim3(256), 0, st, b2, b3, a);
         }
     }
     if (c->ntri > 0) {
         if (c->nt == 0 && c->lt_k0 && (c->lt_taken = true))      // (a scene of triangles only: their kernel is the dominant one)
-            hipExtLaunchKernelGGL((k_local_tris<WRITE_Z>), dim3(blocks_for(c->ntri)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, c->ntri, c->ldr, c->r_idx.p,
-                                  c->r_rest.p, c->r_u.p, c->r_z.p, c->r_sc.p, c->r_lmin.p, c->r_lmax.p, c->curr.p, c->r_cf.p);
+            hipExtLaunchKernelGGL((k_local_tris<WRITE_Z, STOP>), dim3(blocks_for(c->ntri)), dim3(256), 0, st, c->lt_k0, c->lt_k1, 0, c->ntri, c->ldr, c->r_idx.p,
+                                  c->r_rest.p, c->r_u.p, c->r_z.p, c->r_sc.p, c->r_lmin.p, c->r_lmax.p, c->curr.p, c->r_cf.p, c->stop_dev);
         else
-            hipLaunchKernelGGL((k_local_tris<WRITE_Z>), dim3(blocks_for(c->ntri)), dim3(256), 0, st, c->ntri, c->ldr, c->r_idx.p,
-                               c->r_rest.p, c->r_u.p, c->r_z.p, c->r_sc.p, c->r_lmin.p, c->r_lmax.p, c->curr.p, c->r_cf.p);
+            hipLaunchKernelGGL((k_local_tris<WRITE_Z, STOP>), dim3(blocks_for(c->ntri)), dim3(256), 0, st, c->ntri, c->ldr, c->r_idx.p,
+                               c->r_rest.p, c->r_u.p, c->r_z.p, c->r_sc.p, c->r_lmin.p, c->r_lmax.p, c->curr.p, c->r_cf.p, c->stop_dev);
     }
     if (c->nbend > 0)
-        hipLaunchKernelGGL((k_local_bends<WRITE_Z>), dim3(blocks_for(c->nbend)), dim3(256), 0, st, c->nbend, c->ldb, c->h_idx.p, c->h_coef.p, c->h_u.p, c->h_z.p,
-                           c->h_sc.p, c->h_gam.p, c->curr.p, c->h_cf.p);
+        hipLaunchKernelGGL((k_local_bends<WRITE_Z, STOP>), dim3(blocks_for(c->nbend)), dim3(256), 0, st, c->nbend, c->ldb, c->h_idx.p, c->h_coef.p, c->h_u.p, c->h_z.p,
+                           c->h_sc.p, c->h_gam.p, c->curr.p, c->h_cf.p, c->stop_dev);
 }
 template <bool WRITE_Z>
 void launch_local(admm_hip_ctx *c) {      // Binv recomputed from the rest positions / streamed: decided once, in admm_hip_create
+    if constexpr (WRITE_Z) {      // (a step with early exit runs with the monitor: the WRITE_Z instantiations)
+        if (c->stop_dev) { if (c->tet_rest_mode) launch_local_impl<true, true, true>(c); else launch_local_impl<true, false, true>(c); return; }
+    }
     if (c->tet_rest_mode) launch_local_impl<WRITE_Z, true>(c);
     else launch_local_impl<WRITE_Z, false>(c);
 }
@@ -485,6 +496,17 @@ void launch_local(admm_hip_ctx *c) {      // Binv recomputed from the rest posit
 // ---- energy / ADMM monitor (monitor.hpp) ----
 // single-GPU contexts only: a rank of a multi-GPU job holds a part of the terms (element blocks) or of the bodies (components)
 bool monitor_allowed(const admm_hip_ctx *c) { return c->world == 1 && !c->comm && !c->ar_fn && !c->cm.on; }
+// Early exit of the ADMM loop: may this step SKIP ON THE DEVICE?  Only where every launch of an iteration is one the stop word reaches and
+// the host takes no decision of its own inside the loop: the on-chip PCG (k_pcg2) and the persistent GS sweep (k_gs_persist) without
+// colliders that need the host.  Everything else -- bodies beyond the chip on the launch path, UzawaCG with obstacle or dynamic rows (its
+// host logic reads a row count per iteration, its column lanes run on other streams), the GS colour-kernel fall-backs, dynamic
+// colliders, contexts that have given up their persistent kernels, ADMM_HIP_STOP_HOST=1 -- takes the same decision on the host.
+bool stop_device_ok(const admm_hip_ctx *c) {
+    if (c->stop_host || !c->dyn.empty() || c->dist_solve) return false;
+    if (c->linsolver == 1) return c->gsp_enabled && (int64_t)c->gs_max_iters * c->gsp_C < 2000;      // (launch_gs: the persistent kernel)
+    if (c->linsolver == 2 && c->obst.n > 0) return false;
+    return c->oc_enabled && c->oc_plan;
+}
 int mon_blocks(const admm_hip_ctx *c, bool nodes) {
     return blocks_for(c->nt) + blocks_for(c->ntri) + blocks_for(c->nbend) + blocks_for(c->npin_terms) + (nodes ? blocks_for(c->n3) : 0);
 }
@@ -526,7 +548,7 @@ MonArgs mon_args(const admm_hip_ctx *c, const double *x, bool nodes) {
     a.npin = c->npin_terms; a.pin_dim = 3; a.pin_vert = c->pin_vert_d.p; a.pin_z = c->pin_z.p; a.pin_zp = c->mon_pzp.p; a.pin_w2 = c->pin_weight * c->pin_weight;
     a.n3 = c->n3; a.m = nodes ? c->m.p : nullptr; a.Mxbar = c->Mxbar.p;
     a.nb_t = blocks_for(c->nt); a.nb_r = a.nb_t + blocks_for(c->ntri); a.nb_h = a.nb_r + blocks_for(c->nbend); a.nb_p = a.nb_h + blocks_for(c->npin_terms);
-    a.part = c->mon_part.p; a.term = nullptr;
+    a.part = c->mon_part.p; a.term = nullptr; a.stop = c->stop_dev;
     return a;
 }
 // one pass over the terms + the sum of its partials into out [kMonQ] (device)
@@ -542,10 +564,25 @@ void launch_monitor_init(admm_hip_ctx *c, const double *x) {
     if (a.nb_p > 0) hipLaunchKernelGGL((k_monitor<false, false, true>), dim3(a.nb_p), dim3(256), 0, c->stream, a);
 }
 // record s of the running step: after the global solve of ADMM iteration s, x = curr
-void launch_monitor_step(admm_hip_ctx *c, int s) {
+// decide = true (a step with early exit): k_mon_decide in the place of k_mon_final -- the same record, then the decision on it; with
+// c->stop_dev the pass itself is the STOP instantiation
+void launch_monitor_step(admm_hip_ctx *c, int s, bool decide = false) {
     const MonArgs a = mon_args(c, c->curr.p, c->mon_mode >= 2);
-    if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, c->mon_rec.p + (size_t)kMonQ * s);
-    else launch_monitor<true, false>(c, a, c->mon_rec.p + (size_t)kMonQ * s);
+    double *out = c->mon_rec.p + (size_t)kMonQ * s;
+    if (!decide) {
+        if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, out);
+        else launch_monitor<true, false>(c, a, out);
+        return;
+    }
+    const int nb = std::max(1, a.nb_p + (a.m ? blocks_for(a.n3) : 0));
+    if (c->stop_dev) {
+        if (c->mon_mode >= 2) hipLaunchKernelGGL((k_monitor<true, true, false, true>), dim3(nb), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_monitor<true, false, false, true>), dim3(nb), dim3(256), 0, c->stream, a);
+    } else {
+        if (c->mon_mode >= 2) hipLaunchKernelGGL((k_monitor<true, true, false>), dim3(nb), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_monitor<true, false, false>), dim3(nb), dim3(256), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig);
 }
 
 void launch_gather(admm_hip_ctx *c) {
@@ -560,9 +597,10 @@ void launch_gather(admm_hip_ctx *c) {
         a.pin_u = c->pin_u.p; a.pin_z = c->pin_z.p; a.pin_sc = c->dt * c->dt * c->pin_weight * c->pin_weight;
     }
     a.x = c->curr.p; a.Mxbar = c->Mxbar.p; a.b = c->b.p; a.add_mxbar = (c->rank == 0) ? 1 : 0;
-    a.order = c->g_order.p;
+    a.order = c->g_order.p; a.stop = c->stop_dev;
     const int grid = std::max(1, (a.n_slices + 3) / 4);
-    hipLaunchKernelGGL(k_gather_rhs, dim3(grid), dim3(256), 0, c->stream, a);
+    if (c->stop_dev) hipLaunchKernelGGL(k_gather_rhs<true>, dim3(grid), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_gather_rhs<false>, dim3(grid), dim3(256), 0, c->stream, a);
 }
 
 // in-place sum all-reduce of n doubles on the context's stream: RCCL, or the caller's transport staged through pinned host memory
@@ -653,7 +691,7 @@ static const void *pcg2_instance(int T, bool hot) {
 // debugging, at most two record units per thread.  Everything else is the generic instance's.  (The halo may be of any length: fixing it
 // at two entries per thread was tried and changed nothing in the instance's registers or its iteration.)
 static bool pcg2_hot_ok(const admm_hip_ctx *c, const OcRc &rc, const admm_hip_ctx::OcLane *ln) {
-    if (c->oc_force_generic || !rc.loop || ln || !rc.on || rc.skip) return false;
+    if (c->oc_force_generic || !rc.loop || ln || !rc.on || rc.skip || c->stop_dev) return false;      // (a step with early exit: the generic instance reads the skip word)
     if (!c->oc_coarse || !c->oc_ainv.p || c->oc_nc > 2 * c->oc_T) return false;
     if (!c->oc_nbr.p || !c->oc_flags.p) return false;
     if (c->oc_prof.p || c->oc_debug) return false;
@@ -681,7 +719,7 @@ int launch_pcg2(admm_hip_ctx *c, const double *b, double *x, int max_iters, cons
     a.rc_part = c->oc_rc_part.p;
     if (c->oc_coarse) { a.ainv = c->oc_ainv.p; a.cbuf = c->oc_cbuf.p; a.nc = c->oc_nc; a.ncp = c->oc_ncp; }
     a.cwt = c->oc_cwt.p;
-    a.skip = rc.skip;
+    a.skip = rc.skip ? rc.skip : (ln ? nullptr : c->stop_dev);      // (a step with early exit: the solves behind the stop are no-ops)
     // (every 16th solve and a context's first 40 verify whatever the rule says: the sample that can revoke the trust, pcg_onchip2.hpp)
     a.trust_short = (c->oc_always_verify || c->oc_launches < 40 || (c->oc_launches & 15) == 0) ? 0 : 1;
     if (rc.on && c->defl_fused && c->defl_k > 0) { c->defl_armed = true; a.defl_k = c->defl_k; a.defl_Z = c->defl_Zint.p; a.defl_Ginv = c->defl_Ginv.p; a.defl_rec = c->defl_rec.p; }      // (the ADMM loop's solves only: not the K^-1 columns of UzawaCG)
@@ -1090,19 +1128,25 @@ int launch_pcg(admm_hip_ctx *c, const double *b, double *x, int max_iters, const
 // End projection of a finished solve on the soft modes (kernels.hpp: k_defl_*)
 // have_resid: x is the iterate a launch-path solve has just returned and c->cg_u still holds D^-1 times ITS final residual (k_big_scatter): the
 // projection takes the residual from there instead of forming b - A x again (ADMM_HIP_DEFL_RESID=0: always the product -- A/B, tests).
-void launch_deflation(admm_hip_ctx *c, const double *b, double *x, bool have_resid = false) {
+template <bool STOP> void launch_deflation_impl(admm_hip_ctx *c, const double *b, double *x, bool have_resid);
+void launch_deflation(admm_hip_ctx *c, const double *b, double *x, bool have_resid = false) {      // (c->stop_dev: the STOP instantiations)
+    if (c->stop_dev) launch_deflation_impl<true>(c, b, x, have_resid);
+    else launch_deflation_impl<false>(c, b, x, have_resid);
+}
+template <bool STOP>
+void launch_deflation_impl(admm_hip_ctx *c, const double *b, double *x, bool have_resid) {
     hipStream_t st = c->stream;
     const int NB = c->NB, k = c->defl_k;
     if (have_resid && c->defl_use_resid) {
         const int NBd = (c->nv + 256 * kDeflRV - 1) / (256 * kDeflRV);
-        hipLaunchKernelGGL(k_defl_dots_r, dim3(NBd), dim3(256), 0, st, c->nv, c->cg_u.p, c->dinv.p, k, c->defl_Z.p, c->defl_part.p, NBd);
-        hipLaunchKernelGGL(k_defl_solve, dim3(1), dim3(1024), 0, st, k, c->defl_part.p, NBd, c->defl_Ginv.p, c->defl_y.p);
-        hipLaunchKernelGGL(k_defl_apply, dim3(blocks_for(c->nv)), dim3(256), 0, st, c->nv, k, c->defl_Z.p, c->defl_y.p, x);
+        hipLaunchKernelGGL(k_defl_dots_r<STOP>, dim3(NBd), dim3(256), 0, st, c->nv, c->cg_u.p, c->dinv.p, k, c->defl_Z.p, c->defl_part.p, NBd, c->stop_dev);
+        hipLaunchKernelGGL(k_defl_solve<STOP>, dim3(1), dim3(1024), 0, st, k, c->defl_part.p, NBd, c->defl_Ginv.p, c->defl_y.p, c->stop_dev);
+        hipLaunchKernelGGL(k_defl_apply<STOP>, dim3(blocks_for(c->nv)), dim3(256), 0, st, c->nv, k, c->defl_Z.p, c->defl_y.p, x, c->stop_dev);
         return;
     }
-    hipLaunchKernelGGL(k_defl_dots, dim3(NB), dim3(256), 0, st, sell_arg(c->A), c->m.p, b, x, k, c->defl_Z.p, c->nv, c->defl_part.p, NB);
-    hipLaunchKernelGGL(k_defl_solve, dim3(1), dim3(1024), 0, st, k, c->defl_part.p, NB, c->defl_Ginv.p, c->defl_y.p);
-    hipLaunchKernelGGL(k_defl_apply, dim3(blocks_for(c->nv)), dim3(256), 0, st, c->nv, k, c->defl_Z.p, c->defl_y.p, x);
+    hipLaunchKernelGGL(k_defl_dots<STOP>, dim3(NB), dim3(256), 0, st, sell_arg(c->A), c->m.p, b, x, k, c->defl_Z.p, c->nv, c->defl_part.p, NB, c->stop_dev);
+    hipLaunchKernelGGL(k_defl_solve<STOP>, dim3(1), dim3(1024), 0, st, k, c->defl_part.p, NB, c->defl_Ginv.p, c->defl_y.p, c->stop_dev);
+    hipLaunchKernelGGL(k_defl_apply<STOP>, dim3(blocks_for(c->nv)), dim3(256), 0, st, c->nv, k, c->defl_Z.p, c->defl_y.p, x, c->stop_dev);
 }
 
 int launch_pcg_recycled_impl(admm_hip_ctx *c, const double *b, double *x, bool loop);
@@ -1805,10 +1849,11 @@ void launch_gs_persist(admm_hip_ctx *c, const double *b, double *x) {
     a.box = (v4u *)c->gsp_box.p; a.n_box = (int)std::max<int64_t>(c->gsp_stat[4], 1); a.part = (v4u *)c->gsp_part.p; a.meet = (v4u *)c->gsp_meet.p; a.abort_word = c->gsp_abort.p;
     a.done = c->counters.p + kCntGsDone; a.sweeps = c->counters.p + kCntGsSweeps; a.total = c->counters.p + kCntIters; a.sig = c->d_sig;
     a.prof = c->gsp_prof.p; a.prof_block = c->gsp_prof_block;
-    a.ob = c->obst_dev.p; a.proj = c->gs_proj.p;
+    a.ob = c->obst_dev.p; a.proj = c->gs_proj.p; a.stop = c->stop_dev;
     if (c->test_abort_seq > 0 && (int)a.seq == c->test_abort_seq)   // test hook: this solve finds its hand-off given up
         (void)hipMemsetAsync(c->gsp_abort.p, 1, sizeof(unsigned), st);
-    hipLaunchKernelGGL(k_gs_persist, dim3(c->gsp_G), dim3(kGspT), c->gsp_lds, st, a);
+    if (c->stop_dev) hipLaunchKernelGGL(k_gs_persist<true>, dim3(c->gsp_G), dim3(kGspT), c->gsp_lds, st, a);
+    else hipLaunchKernelGGL(k_gs_persist<false>, dim3(c->gsp_G), dim3(kGspT), c->gsp_lds, st, a);
     c->gsp_launches += 1;
     if (c->gsp_prof.p && (c->solve_seq % 200) == 0) {     // diagnosis: one block's wall-clock split of the phases since the last print
         unsigned long long h[16];
@@ -1848,9 +1893,12 @@ hipError_t plan_gs_persist(admm_hip_ctx *c) {
     const admm_host::GsPlan P = admm_host::build_gs_plan(c->Ahat, c->n_colors, col32.data(), cus, rows_target, lds_max);
     if (!P.ok) return hipSuccess;
     int per_cu = 0;
-    if ((e = hipFuncSetAttribute((const void *)k_gs_persist, hipFuncAttributeMaxDynamicSharedMemorySize, P.lds_bytes)) != hipSuccess) return e;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gs_persist, kGspT, P.lds_bytes)) != hipSuccess) return e;
-    if (per_cu < 1 || P.G > cus) return hipSuccess;      // every block must be resident at once
+    int per_cu_stop = 0;      // (k_gs_persist<true>: the solves of a step with early exit, admm_hip_set_admm_stop)
+    if ((e = hipFuncSetAttribute((const void *)k_gs_persist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, P.lds_bytes)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_gs_persist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, P.lds_bytes)) != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gs_persist<false>, kGspT, P.lds_bytes)) != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_stop, k_gs_persist<true>, kGspT, P.lds_bytes)) != hipSuccess) return e;
+    if (per_cu < 1 || per_cu_stop < 1 || P.G > cus) return hipSuccess;      // every block must be resident at once
     if ((e = c->gsp_hdr.upload(std::vector<int>(P.hdr.begin(), P.hdr.end()))) != hipSuccess) return e;
     if ((e = c->gsp_orig.upload(std::vector<int>(P.orig.begin(), P.orig.end()))) != hipSuccess) return e;
     if ((e = c->gsp_out.upload(std::vector<int>(P.out_idx.begin(), P.out_idx.end()))) != hipSuccess) return e;
@@ -2230,6 +2278,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     HIP_TRY(hipEventCreate(&c->ev_step1));
     HIP_TRY(hipHostMalloc((void **)&c->h_sig, kSigWords * sizeof(int), hipHostMallocMapped));
     std::memset(c->h_sig, 0, kSigWords * sizeof(int));
+    c->stop_host = env_flag("ADMM_HIP_STOP_HOST", false);      // A/B, tests: the early exit of the ADMM loop decided on the host on every path
     HIP_TRY(hipHostGetDevicePointer((void **)&c->d_sig, c->h_sig, 0));
 
     const double dt2 = c->dt * c->dt;
@@ -3080,7 +3129,21 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     struct InStep { admm_hip_ctx *c; ~InStep() { c->in_step = false; } } in_step_guard{c};
     c->in_step = true;
     // monitor (admm_hip_set_monitor): one record per ADMM iteration, written on the stream -- nothing here waits for the device
-    const bool mon = c->mon_mode != 0 && monitor_allowed(c);
+    // early exit (admm_hip_set_admm_stop): the step runs with the monitor (mode max(mode, 1)), k_mon_decide takes the place of k_mon_final,
+    // and the iterations behind the stop are either never launched (the host decides: one event synchronisation per iteration) or launched
+    // as no-ops (c->stop_dev: every kernel of the loop reads the stop word first)
+    const bool stopping = c->stop_tol > 0.0 && admm_iters > 0 && monitor_allowed(c);
+    const bool stop_on_dev = stopping && stop_device_ok(c);
+    struct StopDev { admm_hip_ctx *c; ~StopDev() { c->stop_dev = nullptr; } } stop_dev_guard{c};
+    c->stop_dev = stop_on_dev ? c->counters.p + kCntAdmmStop : nullptr;
+    c->stop_last = admm_iters; c->stop_on_dev = 0;
+    const int seq0 = c->solve_seq;
+    const long long oc_launches0 = c->oc_launches, gsp_launches0 = c->gsp_launches;
+    if (stopping) {
+        if (!c->ev_stop) HIP_TRY(hipEventCreateWithFlags(&c->ev_stop, hipEventDisableTiming));
+        c->h_sig[kSigAdmmStop] = 0; c->h_sig[kSigAdmmIters] = 0;      // (no kernel of an earlier step is still running: see the synchronisation below)
+    }
+    const bool mon = (c->mon_mode != 0 || stopping) && monitor_allowed(c);
     c->mon_n = 0;
     if (mon) {
         HIP_TRY(mon_ensure(c, true, false));
@@ -3110,6 +3173,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     }
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, kCntStepWords * sizeof(int), st));
     if (c->linsolver == 2) HIP_TRY(hipMemsetAsync(c->counters.p + kCntSchurIters, 0, sizeof(int), st));
+    if (stopping) HIP_TRY(hipMemsetAsync(c->counters.p + kCntAdmmStop, 0, 2 * sizeof(int), st));      // (kCntAdmmStop, kCntAdmmIters)
     if (c->wind_n > 0) {   // ExplicitForce::project of the wind, Solver.cpp:54 (before gravity and the prediction)
         hipLaunchKernelGGL(k_wind_tris, dim3(blocks_for(c->wind_n)), dim3(256), 0, st, c->wind_n, c->wind_tris.p, c->x.p, c->v.p,
                            c->wind_dir[0], c->wind_dir[1], c->wind_dir[2], c->dt, c->wind_force.p);
@@ -3123,8 +3187,10 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     if (c->ntri) HIP_TRY(hipMemsetAsync(c->r_u.p, 0, c->r_u.n * sizeof(double), st));
     if (c->nbend) HIP_TRY(hipMemsetAsync(c->h_u.p, 0, c->h_u.n * sizeof(double), st));
     if (c->npin_terms) HIP_TRY(hipMemsetAsync(c->pin_u.p, 0, c->pin_u.n * sizeof(double), st));
+    int n_launched = 0;      // iterations enqueued (all of them, unless the host has seen the stop)
     for (int s = 0; s < admm_iters; ++s) {
         if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * s], st));
+        n_launched = s + 1;
         const bool lt = !timed && c->lt_on;
         if (lt) {
             while (c->lt_ev.size() < c->lt_used + 2) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->lt_ev.push_back(e); }
@@ -3146,15 +3212,41 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         const int grc = launch_global(c, c->b.p, c->curr.p);   // Solver.cpp:99
         if (grc == -2) return kStepAborted;       // a grid barrier timed out in a column solve of UzawaCG: same recovery as any aborted on-chip solve
         if (grc) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
-        if (mon) launch_monitor_step(c, s);     // x = x^{s+1}, z = z^{s+1}, z_prev = z^s
+        if (mon) launch_monitor_step(c, s, stopping);     // x = x^{s+1}, z = z^{s+1}, z_prev = z^s
+        if (stopping && !stop_on_dev) {      // the host decides: wait for the decision, read its pinned copy
+            HIP_TRY(hipEventRecord(c->ev_stop, st));
+            HIP_TRY(hipEventSynchronize(c->ev_stop));
+            if (c->h_sig[kSigAbort]) break;      // (a persistent launch gave up: seen again below)
+            if (((volatile int *)c->h_sig)[kSigAdmmStop]) break;
+        }
     }
     c->timing = false;
-    if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * admm_iters], st));
+    if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * n_launched], st));
     if (timed && c->lk_launch > 0)
         hipLaunchKernelGGL(k_ts_reduce, dim3(c->lk_launch), dim3(256), 0, st, c->lk_ts.p, c->lk_tsn, c->lk_launch, c->lk_out.p);
     hipLaunchKernelGGL(k_finish, dim3(blocks_for(c->n3)), dim3(256), 0, st, c->n3, 1.0 / c->dt, c->x.p, c->v.p, c->curr.p);
     HIP_TRY(hipEventRecord(c->ev_step1, st));
     HIP_TRY(hipGetLastError());
+    int n_exec = admm_iters;      // iterations executed
+    if (stopping) {
+        // ONE synchronisation ends a step with early exit: the host learns the executed count, and everything that counts the solves of a
+        // frame on the host is set from it -- not from the number of launches
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->h_sig[kSigAbort]) return kStepAborted;      // (the replay decides again for itself)
+        n_exec = std::min(n_launched, std::max(1, (int)((volatile int *)c->h_sig)[kSigAdmmIters]));
+        c->stop_last = n_exec; c->stop_on_dev = stop_on_dev ? 1 : 0;
+        c->mon_n = n_exec;
+        if (c->rc_iter > n_exec) c->rc_iter = n_exec;      // the pairs this frame really wrote: next frame's rc_prev_valid, then rc_prev2_valid
+        if (stop_on_dev) {      // every skipped iteration took one solve number (and, k_pcg2, one place in the verification sample): give them back
+            const int skipped = n_launched - n_exec;
+            c->solve_seq = seq0 + n_exec;
+            if (c->linsolver != 1) {      // (admm_hip_persistent_launches, admm_hip_pcg_instances: solves, not no-op launches)
+                c->oc_launches = oc_launches0 + n_exec;
+                c->oc_instance_launches[c->oc_last_instance == 2 ? 0 : 1] -= skipped;
+            } else c->gsp_launches = gsp_launches0 + n_exec;
+            if (c->linsolver == 2) c->uz_iters_step -= skipped;      // (one per launched iteration on this path: stats->inner_iters counts executed ones)
+        }
+    }
     if (timed) {
         HIP_TRY(hipEventSynchronize(c->ev_step1));
         if (c->h_sig && c->h_sig[kSigAbort]) return kStepAborted;
@@ -3162,7 +3254,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev_step0, c->ev_step1));
         stats->step_ms = ms;
-        for (int s = 0; s < admm_iters; ++s) {
+        for (int s = 0; s < n_exec; ++s) {      // (executed iterations only; a skipped one costs its empty launches, inside step_ms)
             // local_ms = the prox kernels (the reference's local loop); global_ms = RHS + solve, as in Solver.cpp:97-100
             HIP_TRY(hipEventElapsedTime(&ms, c->ev_phase[3 * s], c->ev_phase[3 * s + 1])); stats->local_ms += ms;
             HIP_TRY(hipEventElapsedTime(&ms, c->ev_phase[3 * s + 1], c->ev_phase[3 * s + 2])); stats->rhs_ms += ms;
@@ -3181,7 +3273,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         HIP_TRY(hipMemcpy(h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
         CgScal sc[2];
         HIP_TRY(hipMemcpy(sc, c->cg_scal.p, sizeof(sc), hipMemcpyDeviceToHost));
-        stats->admm_iters = admm_iters;
+        stats->admm_iters = n_exec;
         if (c->linsolver == 1) { stats->inner_iters = h[kCntIters]; stats->last_solve_converged = h[kCntGsDone] != 0; }   // (the done word carries the stamp of the launch that raised it)
         else if (c->linsolver == 2) {
             stats->inner_iters = c->uz_iters_step + h[kCntSchurIters]; // the reference counts Schur-CG iterations (UzawaCG.hpp:124)
@@ -3192,11 +3284,11 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         else {
             stats->inner_iters = h[kCntIters];
             stats->last_solve_converged = sc[c->last_launched_iters & 1].converged;
-            stats->unconverged_solves = admm_iters - h[kCntConverged];
+            stats->unconverged_solves = n_exec - h[kCntConverged];
             {   // iterations of the last (up to 64) solves of this step, oldest first
                 int ring[kCntRingLen];
                 HIP_TRY(hipMemcpy(ring, c->counters.p + kCntRing, sizeof(ring), hipMemcpyDeviceToHost));
-                const int n = std::min(admm_iters, kCntRingLen);
+                const int n = std::min(n_exec, kCntRingLen);
                 for (int i = 0; i < n; ++i) stats->pcg_iters_per_solve[i] = ring[(c->solve_seq - n + 1 + i) & kCntRingMask];
             }
             stats->pcg_launched_iters = c->last_launched_iters;
@@ -3506,6 +3598,32 @@ int admm_hip_get_monitor(admm_hip_ctx *c, int32_t cap, int32_t *n, double *recor
     }
     return ADMM_HIP_OK;
 }
+
+// ---- early exit of the ADMM loop on the monitor's residuals (monitor.hpp: admm_stop_test, k_mon_decide; step_impl) ----
+int admm_hip_set_admm_stop(admm_hip_ctx *c, double tol, int32_t min_iters) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "set_admm_stop: NULL context");
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(ADMM_HIP_ERR_ARG, "set_admm_stop: tol must be finite and >= 0 (0 = off)");
+    if (min_iters < 1) return fail(ADMM_HIP_ERR_ARG, "set_admm_stop: min_iters must be >= 1");
+    if (tol > 0.0) { if (int rc = mon_refuse(c, "set_admm_stop")) return rc; }
+    c->stop_tol = tol; c->stop_min = min_iters;
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_get_admm_stop(admm_hip_ctx *c, double *tol, int32_t *min_iters, int32_t *last_iters, int32_t *on_device) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "get_admm_stop: NULL context");
+    if (tol) *tol = c->stop_tol;
+    if (min_iters) *min_iters = c->stop_min;
+    if (last_iters || on_device) {      // (a step without early exit may still be running, and may yet be replayed)
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int rc = settle(c)) return rc;
+    }
+    if (last_iters) *last_iters = c->stop_last;
+    if (on_device) *on_device = c->stop_on_dev;
+    return ADMM_HIP_OK;
+}
+
+int admm_host_admm_stop_test(const double *rec8, double tol) { return (rec8 && admm_k::admm_stop_test(rec8, tol)) ? 1 : 0; }
 
 // LinearSolver tuning members changed after Solver::initialize (the reference reads them on every solve: src/NodalMultiColorGS.hpp:40-46,100,
 // src/UzawaCG.hpp:44-45,92).  Takes effect from the next solve; nothing is re-planned.

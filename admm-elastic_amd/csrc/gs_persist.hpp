@@ -66,6 +66,7 @@ struct GspArgs {
     const Obstacles *ob;                                      // passive obstacles (device copy: 80 SGPRs as a by-value argument)
     unsigned long long *prof; int prof_block;                 // diagnosis (ADMM_HIP_GSP_PROF=1): wall-clock ticks per part of a phase
     unsigned long long *proj;                                 // rows projected onto a passive obstacle since create (admm_hip_contact_totals)
+    const int *stop;                                          // k_gs_persist<true> only: the stop word of the ADMM loop (kernels.hpp: kCntAdmmStop)
 };
 
 __device__ __forceinline__ v4u gsp_pack(double v, unsigned s) {
@@ -120,9 +121,13 @@ struct GspObstOne {      // Obstacles with exactly one entry (k_gs_persist: in S
     int kind[1]; double par[1][4]; const double *gmeta, *gdata;
 };
 
+// STOP: a solve of a step with early exit (admm_hip_set_admm_stop).  The word was written by a kernel that completed before this launch
+// (the rule beside kCntAdmmStop), so every block reads the same value: all of them leave, or none.
+template <bool STOP = false>
 __global__ __launch_bounds__(kGspT) void k_gs_persist(GspArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    if (STOP && *a.stop) return;
 #ifdef ADMM_GSP_PROF_FINE
     const unsigned long long tk0 = wall_clock64();
 #endif

@@ -47,14 +47,23 @@ constexpr int kCntTrustRevoked = kCntFindings + 1;   //   the trust in a short f
 constexpr int kCntFailedChecks = kCntFindings + 2;   //   sampled verifications of a short first pass that failed
 constexpr int kCntFindingsLen = 3;
 constexpr int kCntSchurProducts = kCntFindings + kCntFindingsLen;   // Schur products S d of the persistent launches since create (k_uz_persist)
-constexpr int kCntWords = 80;          // (the last word is spare)
-static_assert(kCntSchurProducts < kCntWords, "counters layout");
+// EARLY EXIT of the ADMM loop (admm_hip_set_admm_stop; monitor.hpp: k_mon_decide): cleared by step_impl beside the per-step words.
+// THE RULE the persistent kernels depend on: only a kernel that has COMPLETED, in stream order, before its reader was launched may
+// write kCntAdmmStop -- k_mon_decide, a launch of its own on the context's stream, is the only writer.  Written by a kernel that runs
+// concurrently with a reader, the blocks of a persistent launch (k_pcg2, k_gs_persist) could see different values: one part of the grid
+// would return while the rest waits at the grid barrier.  Every kernel of the iteration loop reads it first and returns when it is set.
+constexpr int kCntAdmmStop = 79;       // nonzero: the ADMM loop of this step has ended; every later kernel of the loop is a no-op
+constexpr int kCntAdmmIters = 80;      // ADMM iterations of this step executed so far
+constexpr int kCntWords = 88;
+static_assert(kCntSchurProducts < kCntAdmmStop, "counters layout");
 // signal words: kSigWords ints of pinned, device-mapped host memory per context (h_sig; d_sig is the device alias)
 constexpr int kSigConverged = 0;       // sequence number of the last solve that converged
 constexpr int kSigChunks = 1;          // chunks closed so far (the host waits on it before it looks at kSigConverged)
 constexpr int kSigAbort = 2;           // a persistent launch gave up a grid barrier or hand-off: the host takes the recovery path
 constexpr int kSigConvIter = 3;        // iteration at which the last converged solve of the two-level PCG converged (stored before kSigConverged)
-constexpr int kSigWords = 4;
+constexpr int kSigAdmmStop = 4;        // copy of kCntAdmmStop for the host (the paths that decide there read it behind an event)
+constexpr int kSigAdmmIters = 5;       // copy of kCntAdmmIters
+constexpr int kSigWords = 8;
 
 struct Mat { double mu, la, k, kappa; int type, table; };   // KIND 4: type 0..2 = xu:: spline with a compression term kappa; type 3 = tabulated (user-defined) spline `table`; type 4 = stable Neo-Hookean
 
@@ -233,6 +242,7 @@ struct TetArgs {
     // ts[ts_n + wave slot]; nullptr = off.  max(exit) - min(entry) is the launch's
     // duration as rocprofv3 reports it, without the dispatch gaps an event pair around the launch also counts.
     unsigned long long *ts; int ts_n;
+    const int *stop;          // STOP instantiations only: the stop word of the ADMM loop (kCntAdmmStop) -- set, the launch is a no-op
 };
 __device__ __forceinline__ void ts_enter(const TetArgs &a) {
     if (a.ts && (threadIdx.x & 63) == 0) a.ts[blockIdx.x * 4 + (threadIdx.x >> 6)] = wall_clock64();
@@ -530,10 +540,12 @@ __device__ __forceinline__ void local_tet_body(const TetArgs &a, int t, int t_en
 
 // one constitutive model per launch (used when a scene has a single model, and by the parity entry point)
 constexpr int kNhWaves = 4;      // waves per SIMD of the Neo-Hookean launches
-template <int KIND, bool WRITE_Z, bool REST>
+// (STOP, here and below: the instantiations of a step with early exit that skips on the device -- admm_hip_set_admm_stop)
+template <int KIND, bool WRITE_Z, bool REST, bool STOP = false>
 __global__ __launch_bounds__(256, (KIND == 1 ? kNhWaves : KIND == 4 ? 2 : 4)) void k_local_tets(int t0, int t1, TetArgs a) {
     __shared__ double sLm[((KIND == 1 || KIND == 2 || KIND == 3) ? 18 : 12) * kChunkLdK];     // rows 0..8: Binv; 9..: V (parked); 0..11: corner forces
     LdsDk *sL = (LdsDk *)sLm;
+    if (STOP && *a.stop) return;
     const int blk = xcd_block();
     ts_enter(a);
     local_tet_body<KIND, WRITE_Z, REST>(a, t0 + blk * 256 + (int)threadIdx.x, t1, a.chunk0 + blk, sL);
@@ -543,10 +555,11 @@ __global__ __launch_bounds__(256, (KIND == 1 ? kNhWaves : KIND == 4 ? 2 : 4)) vo
 // all models in ONE launch: block ranges [0,nb0) linear, [nb0,nb1) NH, [nb1,nb2) StVK (wave-uniform branch).
 // Avoids the ramp-down / ramp-up between per-model launches of a mixed scene.  (Chunks are numbered model by model in this
 // order, so the block index is the chunk index.)
-template <bool WRITE_Z, bool REST>
+template <bool WRITE_Z, bool REST, bool STOP = false>
 __global__ __launch_bounds__(256, kNhWaves) void k_local_tets_fused(int b0, int b1, int b2, int b3, int nb0, int nb1, TetArgs a) {
     __shared__ double sLm[18 * kChunkLdK];
     LdsDk *sL = (LdsDk *)sLm;
+    if (STOP && *a.stop) return;
     const int blk = xcd_block();
     ts_enter(a);
     if (blk < nb0) {
@@ -560,12 +573,13 @@ __global__ __launch_bounds__(256, kNhWaves) void k_local_tets_fused(int b0, int 
 }
 
 // LOCAL STEP, triangles (src/TriEnergyTerm.cpp:54-101): F (3x2) = [x1-x0, x2-x0] rest
-template <bool WRITE_Z>
+template <bool WRITE_Z, bool STOP = false>
 __global__ __launch_bounds__(256) void k_local_tris(int n, int ld, const int4 *__restrict__ idx,
                                                     const double *__restrict__ rest, double *__restrict__ u,
                                                     double *__restrict__ z, const double *__restrict__ sc,
                                                     const double *__restrict__ lmin, const double *__restrict__ lmax,
-                                                    const double *__restrict__ x, double *__restrict__ cf) {
+                                                    const double *__restrict__ x, double *__restrict__ cf, const int *stop) {
+    if (STOP && *stop) return;
     const int t = xcd_block() * 256 + threadIdx.x;
     if (t >= n) return;
     const int4 id = idx[t];
@@ -609,10 +623,12 @@ __global__ __launch_bounds__(256) void k_local_tris(int n, int ld, const int4 *_
 // per hinge in the mould of EnergyTerm::update (src/EnergyTerm.hpp:130-140): D_i x = sum_k c_k x_{v_k} (3 rows), quadratic energy
 // E(z) = kappa / 2 |z|^2  =>  prox(q) = gam q with gam = w^2 / (kappa + w^2), u += D_i x - z; the four corner forces
 // dt^2 w^2 c_k (z - u) go to cf [12][ld] and are summed per vertex by k_gather_rhs.  lane = hinge, SoA like the triangles.
-template <bool WRITE_Z>
+template <bool WRITE_Z, bool STOP = false>
 __global__ __launch_bounds__(256) void k_local_bends(int n, int ld, const int4 *__restrict__ idx, const double *__restrict__ coef,
                                                      double *__restrict__ u, double *__restrict__ z, const double *__restrict__ sc,
-                                                     const double *__restrict__ gam, const double *__restrict__ x, double *__restrict__ cf) {
+                                                     const double *__restrict__ gam, const double *__restrict__ x, double *__restrict__ cf,
+                                                     const int *stop) {
+    if (STOP && *stop) return;
     const int t = xcd_block() * 256 + threadIdx.x;
     if (t >= n) return;
     const int4 id = idx[t];
@@ -658,6 +674,7 @@ struct GatherArgs {
     double *b;
     int add_mxbar;             // 1 on a single GPU / on rank 0
     const int *order;          // [nv] vertex gathered by every row (rows sorted by list length inside 512-vertex windows)
+    const int *stop;           // k_gather_rhs<true> only: the stop word of the ADMM loop (kCntAdmmStop)
 };
 
 // sum of the corner forces incident to this lane's vertex (incidence widths are multiples of 8; padding
@@ -751,7 +768,9 @@ __device__ __forceinline__ void pin_term_update(const int *__restrict__ vert_pin
     }
 }
 
+template <bool STOP = false>
 __global__ __launch_bounds__(256) void k_gather_rhs(GatherArgs a) {
+    if (STOP && *a.stop) return;
     const int lane = threadIdx.x & 63;
     const int s = wave_slice();
     if (s >= a.n_slices) return;
@@ -1180,8 +1199,10 @@ __global__ __launch_bounds__(256) void k_rc_apply(int n3, RcBasis B, const doubl
 // k_defl_dots: r = b - A x and the partial sums of Z^T r per block; k_defl_solve: one block reduces them and applies (Z^T K Z)^-1;
 // k_defl_apply: x += Z y.
 constexpr int kDeflMax = 64;
+template <bool STOP = false>
 __global__ __launch_bounds__(256) void k_defl_dots(SellA A, const double *__restrict__ m, const double *__restrict__ b, const double *__restrict__ x,
-                                                   int k, const double *__restrict__ Z, int nv, double *__restrict__ part, int NB) {
+                                                   int k, const double *__restrict__ Z, int nv, double *__restrict__ part, int NB, const int *stop) {
+    if (STOP && *stop) return;      // a step with early exit (kCntAdmmStop): the launches behind the stop are no-ops
     __shared__ double lds[4][3 * kDeflMax];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int s = wave_slice();
@@ -1218,8 +1239,10 @@ __global__ __launch_bounds__(256) void k_defl_dots(SellA A, const double *__rest
 // at 2 M tets k_defl_dots is 79 us, 45 of them the product (profiles/r06_launch_path_fixed_costs.txt).  Four vertices per thread, the loads
 // of eight modes x four vertices in flight, one wave sum per mode and axis; a quarter of the partials for k_defl_solve to add up.
 constexpr int kDeflRV = 4;
+template <bool STOP = false>
 __global__ __launch_bounds__(256) void k_defl_dots_r(int nv, const double *__restrict__ u, const double *__restrict__ dinv, int k, const double *__restrict__ Z,
-                                                     double *__restrict__ part, int NBd) {
+                                                     double *__restrict__ part, int NBd, const int *stop) {
+    if (STOP && *stop) return;      // a step with early exit (kCntAdmmStop): the launches behind the stop are no-ops
     __shared__ double lds[4][3 * kDeflMax];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int v0 = blockIdx.x * (256 * kDeflRV) + threadIdx.x;
@@ -1255,7 +1278,9 @@ __global__ __launch_bounds__(256) void k_defl_dots_r(int nv, const double *__res
 // one block of 1024 threads: wave w adds up the quantities w, w + 16, ... over the blocks (lanes stride the blocks: fixed order), then y = G^-1 d
 // (round 6: eight partials of a lane in flight at a time -- as a plain loop every load waited for the one before it: 22 round trips per
 // quantity at 2 M tets, 35 us for a 24 x 24 solve; the order of the additions is unchanged)
-__global__ __launch_bounds__(1024) void k_defl_solve(int k, const double *__restrict__ part, int NB, const double *__restrict__ Ginv, double *__restrict__ y) {
+template <bool STOP = false>
+__global__ __launch_bounds__(1024) void k_defl_solve(int k, const double *__restrict__ part, int NB, const double *__restrict__ Ginv, double *__restrict__ y, const int *stop) {
+    if (STOP && *stop) return;      // a step with early exit (kCntAdmmStop): the launches behind the stop are no-ops
     __shared__ double d[3 * kDeflMax];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
     for (int q = wv; q < 3 * k; q += nw) {
@@ -1278,7 +1303,9 @@ __global__ __launch_bounds__(1024) void k_defl_solve(int k, const double *__rest
         y[o] = acc;
     }
 }
-__global__ __launch_bounds__(256) void k_defl_apply(int nv, int k, const double *__restrict__ Z, const double *__restrict__ y, double *__restrict__ x) {
+template <bool STOP = false>
+__global__ __launch_bounds__(256) void k_defl_apply(int nv, int k, const double *__restrict__ Z, const double *__restrict__ y, double *__restrict__ x, const int *stop) {
+    if (STOP && *stop) return;      // a step with early exit (kCntAdmmStop): the launches behind the stop are no-ops
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= nv) return;
     double acc[3] = {0.0, 0.0, 0.0};

@@ -24,6 +24,19 @@ namespace admm_k {
 
 constexpr int kMonQ = 8;
 
+// EARLY EXIT of the ADMM loop (admm_hip_set_admm_stop): does the record of an iteration meet tol?  rec = the record as admm_hip_get_monitor
+// returns it: primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x| (the square roots of the sums 0..3 above).  The loop
+// stops after an iteration when  primal <= tol max(wz, wdx)  and  dz <= tol wz.  In this product form with <=: no division, 0 <= 0 stops
+// (a body at rest), a NaN anywhere never stops (every comparison with it is false), tol = 0 is "off" and never stops.  The ONE statement
+// of the test: the decide kernel below and the host export admm_host_admm_stop_test both call it.
+__host__ __device__ inline bool admm_stop_test(const double *rec, double tol) {
+    if (!(tol > 0.0)) return false;
+    const double primal = rec[0], dz = rec[1], wz = rec[2], wdx = rec[3];
+    if (!(wz == wz && wdx == wdx)) return false;      // (max() below would drop a NaN on one side)
+    const double big = wz > wdx ? wz : wdx;
+    return primal <= tol * big && dz <= tol * wz;
+}
+
 struct MonArgs {
     const double *x;          // [nv][3] positions D is applied to
     double dt2;               // sc = dt^2 w^2  ->  w^2 = sc / dt2
@@ -42,6 +55,7 @@ struct MonArgs {
     int nb_t, nb_r, nb_h, nb_p;      // block ranges: [0, nb_t) tets, [nb_t, nb_r) triangles, [nb_r, nb_h) hinges, [nb_h, nb_p) pins, then nodes
     double *part;             // [blocks][kMonQ]
     double *term;             // energy per element in device order [nt | ntri | nbend], or nullptr
+    const int *stop;          // k_monitor<.., STOP = true> only: the stop word of the ADMM loop (kernels.hpp: kCntAdmmStop)
 };
 
 // one row of a term: adds to the four residual sums (without the weight, applied once per element)
@@ -124,9 +138,11 @@ __device__ __forceinline__ double mon_tet_energy(const MonArgs &a, int t, const 
 }
 
 // RES: the four residual sums, z_prev <- z.  ENERGY: the energies (+ the inertia sum when a.m is given).  INIT: z_prev <- D x only.
-template <bool RES, bool ENERGY, bool INIT>
+// STOP: an iteration of a step that skips on the device -- a set stop word makes the launch a no-op (nothing written: z_prev stays).
+template <bool RES, bool ENERGY, bool INIT, bool STOP = false>
 __global__ __launch_bounds__(256) void k_monitor(MonArgs a) {
     __shared__ double lds[4 * kMonQ];
+    if (STOP && *a.stop) return;
     const int blk = xcd_block(), tid = (int)threadIdx.x;
     double q[kMonQ] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (blk < a.nb_t) {
@@ -285,6 +301,34 @@ __global__ __launch_bounds__(256) void k_mon_final(const double *__restrict__ pa
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < kMonQ; ++i) out[i] = q[i];
+    }
+}
+
+// k_mon_final of a step with early exit (admm_hip_set_admm_stop): the same sum in the same order -- a record has the same bits with and
+// without the feature -- then the decision on it.  s = the ADMM iteration.  A set stop word makes the launch a no-op like every other
+// kernel of the loop.  Thread 0 writes, with ordinary vector stores: the executed count (cnt[kCntAdmmIters], sig[kSigAdmmIters]) and,
+// when iteration s is the last, the stop word (cnt[kCntAdmmStop], sig[kSigAdmmStop]); sig is pinned host memory, for the host.
+__global__ __launch_bounds__(256) void k_mon_decide(const double *__restrict__ part, int nb, double *__restrict__ out, double tol, int min_iters,
+                                                    int s, int *__restrict__ cnt, int *__restrict__ sig) {
+    __shared__ double lds[4 * kMonQ];
+    if (cnt[kCntAdmmStop]) return;
+    double q[kMonQ] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = (int)threadIdx.x; b < nb; b += 256) {
+#pragma unroll
+        for (int i = 0; i < kMonQ; ++i) q[i] += part[(size_t)b * kMonQ + i];
+    }
+    block_sum<kMonQ>(q, lds);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kMonQ; ++i) out[i] = q[i];
+        const double rec[4] = {sqrt(q[0]), sqrt(q[1]), sqrt(q[2]), sqrt(q[3])};      // (as admm_hip_get_monitor converts the sums)
+        const bool stop = s + 1 >= min_iters && admm_stop_test(rec, tol);
+        cnt[kCntAdmmIters] = s + 1;
+        __hip_atomic_store(sig + kSigAdmmIters, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (stop) {
+            cnt[kCntAdmmStop] = 1;
+            __hip_atomic_store(sig + kSigAdmmStop, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
 }
 

@@ -20,7 +20,7 @@ namespace solver_detail {
 
 // Solver::Settings (src/Solver.hpp:39-50): command-line switches in the comments
 struct SolverSettings {
-    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0), monitor(0) {}
+    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0), monitor(0), admm_tol(0.0), admm_min_iters(1) {}
     double timestep_s;   // -dt
     int verbose;         // -v
     int admm_iters;      // -it
@@ -30,15 +30,19 @@ struct SolverSettings {
     int soft_modes;      // -sm  (GPU build, appended: the reference's fields keep their order) every PCG solve ends with an exact Galerkin step on
                          //      the k softest modes of the system matrix (admm_hip_compute_soft_modes at initialize); 0 = off
     int monitor;         //      (GPU build, appended) ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
+    double admm_tol;     // -tol (GPU build, appended) early exit of a step's ADMM loop (admm_hip_set_admm_stop): the loop stops after the iteration whose
+                         //      residuals meet  |W(Dx - z)| <= tol max(|W z|, |W D x|)  and  |W(z - z_prev)| <= tol |W z|; 0 = off
+    int admm_min_iters;  //      (GPU build, appended) ... but not before this many iterations (>= 1)
     void help();
     bool parse_args(int argc, char **argv);   // true when help() was printed
 };
 
 // Solver::RuntimeData (src/Solver.hpp:54-61): filled from admm_hip_stats after every step
 struct SolverRuntimeData {
-    SolverRuntimeData() : global_ms(0), local_ms(0), collision_ms(0), inner_iters(0) {}
+    SolverRuntimeData() : global_ms(0), local_ms(0), collision_ms(0), inner_iters(0), admm_iters(0) {}
     double global_ms, local_ms, collision_ms;
     int inner_iters;
+    int admm_iters;      // (GPU build, appended) ADMM iterations the step executed: Settings::admm_iters, fewer with Settings::admm_tol > 0
     void print(const SolverSettings &settings);
 };
 
@@ -98,8 +102,10 @@ public:
     std::shared_ptr<LinearSolver> linear_solver() { return m_linsolver; }
     // Sum of EnergyTerm::energy(D, x) over all terms (pins have none), reduced on the device (admm_hip_energy); after initialize()
     double energy(const VecX &x);
-    // the records of the last step(), one per ADMM iteration; empty with Settings::monitor = 0
+    // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
+    // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)
+    void set_admm_stop(double tol, int min_iters = 1);
     void *context() { return m_ctx; }                             // the admm_hip_ctx behind this solver (include/admm_hip.h), for the C ABI's extras
 
 protected:

@@ -582,6 +582,8 @@ bool Solver::initialize(const Settings &settings_) { // src/Solver.cpp:167-261
     la::set_csr(solver_termA, d.n_verts, std::vector<int>(rp.begin(), rp.end()), std::vector<int>(ci.begin(), ci.end()), va);
     m_linsolver->update_system(solver_termA);
     if (m_settings.monitor) check(admm_hip_set_monitor(ctx, (int32_t)m_settings.monitor), "Solver::initialize (monitor)");
+    if (m_settings.admm_tol != 0.0 || m_settings.admm_min_iters != 1)
+        check(admm_hip_set_admm_stop(ctx, m_settings.admm_tol, (int32_t)m_settings.admm_min_iters), "Solver::initialize (admm_tol)");
     m_history.clear();
     if (m_settings.verbose >= 1) printf("%d nodes, %d energy terms\n", (int)m_x.size() / 3, (int)energyterms.size());
     initialized = true;
@@ -601,9 +603,9 @@ void Solver::step() { // src/Solver.cpp:35-110
     check(admm_hip_get_state(ctx, m_x.data(), m_v.data()), "Solver::step");
     m_runtime = RuntimeData();
     m_runtime.global_ms = st.global_ms; m_runtime.local_ms = st.local_ms; m_runtime.collision_ms = st.collision_ms;
-    m_runtime.inner_iters = st.inner_iters;
+    m_runtime.inner_iters = st.inner_iters; m_runtime.admm_iters = st.admm_iters;
     m_history.clear();
-    if (m_settings.monitor) {
+    if (m_settings.monitor || m_settings.admm_tol > 0.0) {      // (get_monitor returns the executed iterations' records)
         int32_t n = 0;
         std::vector<double> rec(8 * (size_t)std::max(1, m_settings.admm_iters));
         check(admm_hip_get_monitor(ctx, (int32_t)(rec.size() / 8), &n, rec.data()), "Solver::step (monitor)");
@@ -613,6 +615,12 @@ void Solver::step() { // src/Solver.cpp:35-110
         }
     }
     if (m_settings.verbose > 0) m_runtime.print(m_settings);
+}
+
+void Solver::set_admm_stop(double tol, int min_iters) {
+    if (!initialized) throw std::runtime_error("Solver::set_admm_stop: initialize() first");
+    check(admm_hip_set_admm_stop((admm_hip_ctx *)m_ctx, tol, (int32_t)min_iters), "Solver::set_admm_stop");
+    m_settings.admm_tol = tol; m_settings.admm_min_iters = min_iters;
 }
 
 double Solver::energy(const VecX &x) {
@@ -644,6 +652,7 @@ const Switch kSwitches[] = {
     {"-ls", nullptr, &Solver::Settings::linsolver, "linear solver (0=LDLT as GPU PCG, 1=NCMCGS, 2=UzawaCG) "},
     {"-ck", &Solver::Settings::constraint_w, nullptr, "constraint weights (-1 = auto) "},
     {"-sm", nullptr, &Solver::Settings::soft_modes, "soft modes of the PCG's end projection (GPU build; 0 = off) "},
+    {"-tol", &Solver::Settings::admm_tol, nullptr, "early exit of the admm loop on its residuals (GPU build; 0 = off) "},
 };
 bool wants_help(const char *a) { const std::string s(a); return s == "-help" || s == "--help" || s == "-h"; }
 } // namespace
@@ -668,10 +677,12 @@ void Solver::Settings::help() {
 }
 
 void Solver::RuntimeData::print(const Solver::Settings &settings) { // src/Solver.cpp:309-319
-    const double n = double(settings.admm_iters);
+    // (with early exit the averages are over the iterations the step executed)
+    const int its = (settings.admm_tol > 0.0 && admm_iters > 0) ? admm_iters : settings.admm_iters;
+    const double n = double(its);
     std::cout << "\nTotal global step: " << global_ms << "ms\nTotal local step: " << local_ms << "ms\nTotal collision update: " << collision_ms
               << "ms\nAvg global step: " << global_ms / n << "ms\nAvg local step: " << local_ms / n << "ms\nAvg collision update: "
-              << collision_ms / n << "ms\nADMM Iters: " << settings.admm_iters << "\nAvg Inner Iters: " << float(inner_iters) / float(settings.admm_iters)
+              << collision_ms / n << "ms\nADMM Iters: " << its << "\nAvg Inner Iters: " << float(inner_iters) / float(its)
               << std::endl;
 }
 

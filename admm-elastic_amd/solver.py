@@ -65,6 +65,8 @@ class Settings:
         self.rank = 0
         self.world_size = 1
         self.monitor = 0             # GPU build: ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
+        self.admm_tol = 0.0          # GPU build: early exit of a step's ADMM loop on its residuals (admm_hip_set_admm_stop); 0 = off
+        self.admm_min_iters = 1      #            ... but not before this many iterations
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown setting " + k)
@@ -86,6 +88,7 @@ class RuntimeData:
         self.unconverged_solves = 0
         self.pcg_launched_iters = 0
         self.pcg_iters_per_solve = []
+        self.admm_iters = 0          # ADMM iterations the step executed (fewer than Settings.admm_iters with Settings.admm_tol > 0)
 
 
 class Floor:
@@ -483,6 +486,8 @@ class Solver:
             check(lib().admm_hip_compute_soft_modes(ctx, int(s.soft_modes), 0))
         if s.monitor:
             check(lib().admm_hip_set_monitor(ctx, int(s.monitor)))
+        if s.admm_tol != 0.0 or s.admm_min_iters != 1:
+            check(lib().admm_hip_set_admm_stop(ctx, float(s.admm_tol), int(s.admm_min_iters)))
         self.initialized = True
         return True
 
@@ -515,7 +520,8 @@ class Solver:
             r.inner_iters, r.step_ms, r.last_solve_converged = st.inner_iters, st.step_ms, st.last_solve_converged
             r.rhs_ms, r.unconverged_solves, r.pcg_launched_iters = st.rhs_ms, st.unconverged_solves, st.pcg_launched_iters
             r.local_kernel_ms = st.local_kernel_ms
-            r.pcg_iters_per_solve = list(st.pcg_iters_per_solve)[:min(it, 64)]
+            r.admm_iters = st.admm_iters
+            r.pcg_iters_per_solve = list(st.pcg_iters_per_solve)[:min(st.admm_iters, 64)]
         else:
             check(lib().admm_hip_step(self._ctx, it, s.gravity, None))
 
@@ -605,6 +611,21 @@ class Solver:
         self._need_ctx()
         check(lib().admm_hip_set_monitor(self._ctx, int(mode)))
         self._settings.monitor = int(mode)
+
+    def set_admm_stop(self, tol, min_iters=1):
+        """admm_hip_set_admm_stop: end a step's ADMM loop after the iteration s (s + 1 >= min_iters) whose record meets
+        primal <= tol max(wz, wdx) and dz <= tol wz; tol = 0 switches it off.  In effect from the next step."""
+        self._need_ctx()
+        check(lib().admm_hip_set_admm_stop(self._ctx, float(tol), int(min_iters)))
+        self._settings.admm_tol, self._settings.admm_min_iters = float(tol), int(min_iters)
+
+    def admm_stop(self):
+        """admm_hip_get_admm_stop: dict(tol, min_iters, last_iters = ADMM iterations the last step executed, on_device = 1 when the
+        remaining ones were skipped on the device, 0 when the host decided or the feature is off)."""
+        self._need_ctx()
+        t = C.c_double(0.0); m = C.c_int32(0); n = C.c_int32(0); d = C.c_int32(0)
+        check(lib().admm_hip_get_admm_stop(self._ctx, C.byref(t), C.byref(m), C.byref(n), C.byref(d)))
+        return dict(tol=t.value, min_iters=m.value, last_iters=n.value, on_device=d.value)
 
     def admm_history(self):
         """Records of the last step (admm_hip_get_monitor), one entry per ADMM iteration, taken after its global solve: dict of arrays

@@ -303,6 +303,36 @@ int admm_hip_set_monitor(admm_hip_ctx *ctx, int32_t mode);
  * *n = iterations recorded (may exceed cap; 0 when the last step ran with the monitor off).  Synchronises the stream. */
 int admm_hip_get_monitor(admm_hip_ctx *ctx, int32_t cap, int32_t *n, double *records);
 
+/* EARLY EXIT of a step's ADMM loop on the monitor's residuals.  With the record of iteration s as admm_hip_get_monitor returns it
+ * (primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x|) the loop stops AFTER iteration s when
+ *     s + 1 >= min_iters   and   primal <= tol * max(wz, wdx)   and   dz <= tol * wz
+ * (compared in this product form: 0 <= 0 stops, a NaN never does).  tol = 0 (default) switches it off: a step is then exactly what it
+ * was -- the same kernels, the same bits.  tol >= 0 and finite, min_iters >= 1, else ADMM_HIP_ERR_ARG; in effect from the next step;
+ * single-GPU contexts only (refused with tol > 0 where admm_hip_set_monitor is).  While tol > 0:
+ *   - a step runs with the monitor in mode max(mode, 1); admm_hip_get_monitor returns exactly the executed iterations' records, with
+ *     the bits a step of that many iterations records;
+ *   - admm_hip_stats::admm_iters is the EXECUTED count; unconverged_solves, inner_iters, pcg_iters_per_solve and the per-phase times
+ *     describe the executed iterations only;
+ *   - the decision is taken ON THE DEVICE, and the iterations behind it are skipped there (launched ahead as before, every kernel
+ *     returns at once), on contexts whose global solve is the on-chip PCG or the persistent Gauss-Seidel sweep, without colliders that
+ *     need the host.  The step then ends with ONE stream synchronisation (the host learns the count) and has none inside the loop;
+ *   - everywhere else -- bodies beyond the chip (launch-path PCG), UzawaCG with passive or dynamic colliders, the Gauss-Seidel
+ *     colour-kernel fall-backs, dynamic colliders, contexts that gave up their persistent kernels, ADMM_HIP_STOP_HOST=1 (read at
+ *     create) -- the host takes the same decision: ONE EVENT SYNCHRONISATION PER ADMM ITERATION, then the one at the end.  Same rule,
+ *     same count;
+ *   - admm_hip_persistent_launches, admm_hip_pcg_instances and admm_hip_solve_totals count executed solves, not the no-op launches
+ *     behind the stop.  The opt-in launch diagnostics do include them where the device skips: the event pairs of
+ *     admm_hip_time_local_launches also time the empty local-step launches, and under ADMM_HIP_KERNEL_CLOCK=1 a skipped launch leaves
+ *     its stamps zero and adds nothing to local_kernel_ms. */
+int admm_hip_set_admm_stop(admm_hip_ctx *ctx, double tol, int32_t min_iters);
+/* The values in effect and, of the LAST step: the ADMM iterations it executed (= its admm_iters with tol = 0) and whether the
+ * remaining ones were skipped on the device (1) or never launched because the host decided (0; also 0 with tol = 0).  Pointers may be
+ * NULL; asking for last_iters or on_device synchronises the stream. */
+int admm_hip_get_admm_stop(admm_hip_ctx *ctx, double *tol, int32_t *min_iters, int32_t *last_iters, int32_t *on_device);
+/* The stop test itself on one record (rec8 as admm_hip_get_monitor returns it; entries 0..3 are read): 1 = stop.  Host code, no GPU:
+ * the same inline function the device decision calls. */
+int admm_host_admm_stop_test(const double *rec8, double tol);
+
 /* The LinearSolver objects' public tuning members, changed AFTER Solver::initialize.  The reference reads them on every solve --
  * NodalMultiColorGS::max_iters / m_tol / m_omega (src/NodalMultiColorGS.hpp:40-46, used at :100 and :136-140), UzawaCG::max_iters /
  * m_tol (src/UzawaCG.hpp:44-45, used at :92 and :109) -- so a caller may cast Solver::m_linsolver and change them between steps.
