@@ -90,6 +90,8 @@ SYMBOLS = [
     ("admm_hip_num_rows", C.c_int, [C.c_void_p]),
     ("admm_hip_solve_totals", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("admm_hip_energy", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("admm_hip_forces", C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    ("admm_hip_stress", C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     ("admm_hip_residuals", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_set_monitor", C.c_int, [C.c_void_p, C.c_int32]),
     ("admm_hip_get_monitor", C.c_int, [C.c_void_p, C.c_int32, c_int_p, c_double_p]),

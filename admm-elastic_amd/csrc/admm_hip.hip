@@ -23,6 +23,7 @@
 #include "host_setup.hpp"
 #include "kernels.hpp"
 #include "monitor.hpp"
+#include "forces.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
 #include "gs_persist.hpp"
@@ -393,6 +394,10 @@ struct admm_hip_ctx {
     DevBuf<double> h_kst; DevBuf<int> pin_vert_d;
     DevBuf<double> mon_tzp, mon_rzp, mon_hzp, mon_pzp, mon_pz6;   // z_prev per family (pins: room for the reference's 6 rows), pin z in the reference's row layout
     DevBuf<double> mon_part, mon_rec, mon_out, mon_term;          // block partials, records [admm_iters][8], one result [8], per-term energies
+    // internal forces / stress / stationarity (forces.hpp; admm_hip_forces, admm_hip_stress, monitor mode 3): buffers of their own, allocated
+    // by the first call that needs them -- the step's t_rec, r_cf, h_cf are not borrowed
+    DevBuf<double> f_rec, f_rcf, f_hcf, f_out, f_stress, f_part, f_stat;   // records, corner forces, f [3 nv], stress [13][ldt], block partials, sums [admm_iters]
+    int mon_stat_n = 0;      // stationarity sums the last step wrote (mode 3), else 0
 
     ~admm_hip_ctx() {      // (every DevBuf member, lane and dynamic collider frees its own memory after this body)
         (void)hipSetDevice(device);
@@ -583,6 +588,61 @@ void launch_monitor_step(admm_hip_ctx *c, int s, bool decide = false) {
         else hipLaunchKernelGGL((k_monitor<true, false, false>), dim3(nb), dim3(256), 0, c->stream, a);
     }
     hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig);
+}
+
+// ---- internal forces, stress, stationarity (forces.hpp) ----
+// buffers, allocated by the first call that needs them; the padding record / element the incidence lists point at must be zero: zeroed
+// on the context's stream (see mon_ensure)
+hipError_t force_ensure(admm_hip_ctx *c, bool stress, int stat_records) {
+    hipError_t e;
+    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
+        if (b.p) return hipSuccess;
+        const hipError_t e2 = b.alloc(n);
+        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
+    };
+    if (c->nt && (e = fresh(c->f_rec, (size_t)4 * (c->n_rec + 1))) != hipSuccess) return e;
+    if (c->ntri && (e = fresh(c->f_rcf, (size_t)12 * c->ldr)) != hipSuccess) return e;
+    if (c->nbend && (e = fresh(c->f_hcf, (size_t)12 * c->ldb)) != hipSuccess) return e;
+    if ((e = fresh(c->f_out, (size_t)std::max(1, c->n3))) != hipSuccess) return e;
+    if (stress && c->nt && (e = fresh(c->f_stress, (size_t)kStressQ * c->ldt)) != hipSuccess) return e;
+    if (stat_records > 0) {
+        if ((e = fresh(c->f_part, (size_t)std::max(1, blocks_for(c->nv)))) != hipSuccess) return e;
+        if (c->f_stat.n < (size_t)stat_records && (e = c->f_stat.alloc((size_t)stat_records)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// f_out = -dE/dx at positions x (device); stress: also the per-tet stress into f_stress; stop: the stop word or nullptr
+void launch_forces(admm_hip_ctx *c, const double *x, bool stress, const int *stop) {
+    ForceArgs a{};
+    a.x = x; a.dt2 = c->dt * c->dt;
+    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
+    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
+    for (int i = 0; i < 6; ++i) { a.kb[i] = c->kind_begin[i]; a.cb[i] = c->chunk_base[i]; }
+    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = c->f_rec.p;
+    a.stress = stress ? c->f_stress.p : nullptr;
+    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_cf = c->f_rcf.p;
+    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_k = c->h_kst.p; a.h_cf = c->f_hcf.p;
+    a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
+    a.stop = stop;
+    const int nb = a.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_forces, dim3(nb), dim3(256), 0, c->stream, a);
+    ForceGatherArgs g{};
+    g.nv = c->nv; g.n_slices = (c->nv + 63) / 64;
+    if (c->nt > 0) { g.t_ptr = c->t_inc.ptr.p; g.t_w = c->t_inc.w.p; g.t_inc = c->t_inc.idx.p; g.t_rec = c->f_rec.p; }
+    if (c->ntri > 0) { g.r_ptr = c->r_inc.ptr.p; g.r_w = c->r_inc.w.p; g.r_inc = c->r_inc.idx.p; g.r_cf = c->f_rcf.p; g.r_ld = c->ldr; }
+    if (c->nbend > 0) { g.h_ptr = c->h_inc.ptr.p; g.h_w = c->h_inc.w.p; g.h_inc = c->h_inc.idx.p; g.h_cf = c->f_hcf.p; g.h_ld = c->ldb; }
+    g.order = c->g_order.p; g.f = c->f_out.p; g.stop = stop;
+    hipLaunchKernelGGL(k_gather_forces, dim3(std::max(1, (g.n_slices + 3) / 4)), dim3(256), 0, c->stream, g);
+}
+// monitor mode 3, record s of the running step: the stationarity sum at x = curr into f_stat[s].  Launched BEFORE the record's decision
+// (k_mon_decide), so the last executed iteration of a step with early exit has its figure.
+void launch_stationarity(admm_hip_ctx *c, int s) {
+    launch_forces(c, c->curr.p, false, c->stop_dev);
+    const int nb = std::max(1, blocks_for(c->nv));
+    const bool gs = c->linsolver == 1;
+    hipLaunchKernelGGL(k_stationarity, dim3(nb), dim3(256), 0, c->stream, c->nv, c->curr.p, c->m.p, c->Mxbar.p, c->f_out.p, 1.0 / (c->dt * c->dt),
+                       (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr, c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->f_part.p, c->stop_dev);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, c->stream, c->f_part.p, nb, c->f_stat.p + s, c->stop_dev);
 }
 
 void launch_gather(admm_hip_ctx *c) {
@@ -3151,6 +3211,13 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         launch_monitor_init(c, c->x.p);
         c->mon_n = admm_iters;
     }
+    const bool stat = mon && c->mon_mode == 3;      // (mode 3: mode 2 plus the stationarity residual, forces.hpp)
+    c->mon_stat_n = 0;
+    if (stat) {
+        HIP_TRY(force_ensure(c, false, std::max(1, admm_iters)));
+        HIP_TRY(hipMemsetAsync(c->f_stat.p, 0, c->f_stat.n * sizeof(double), st));
+        c->mon_stat_n = admm_iters;
+    }
     c->rc_prev2_valid = c->rc_prev_valid; c->rc_prev_valid = c->rc_iter; c->rc_frame += 1; c->rc_iter = 0;   // this frame's pairs become "previous frame"
     // How many pairs a projection uses is decided ONCE per context, from the scene's own behaviour: four pairs cost ~4 us per solve
     // more than three (8.8 MB of reads, 20 block sums) and pay when solves need many iterations (Kuhn cube: 17.4 -> 13.9 per solve),
@@ -3212,6 +3279,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         const int grc = launch_global(c, c->b.p, c->curr.p);   // Solver.cpp:99
         if (grc == -2) return kStepAborted;       // a grid barrier timed out in a column solve of UzawaCG: same recovery as any aborted on-chip solve
         if (grc) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
+        if (stat) launch_stationarity(c, s);
         if (mon) launch_monitor_step(c, s, stopping);     // x = x^{s+1}, z = z^{s+1}, z_prev = z^s
         if (stopping && !stop_on_dev) {      // the host decides: wait for the decision, read its pinned copy
             HIP_TRY(hipEventRecord(c->ev_stop, st));
@@ -3538,6 +3606,32 @@ int admm_hip_energy(admm_hip_ctx *c, const double *x, double *totals4, double *p
     return ADMM_HIP_OK;
 }
 
+// f = -dE/dx and / or the per-tet stress at x (host, or NULL = the device-resident state): one force pass (forces.hpp)
+static int forces_impl(admm_hip_ctx *c, const char *who, const double *x, double *f, double *out13) {
+    if (!c || (!f && !out13)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": NULL argument");
+    if (int rc = mon_refuse(c, who)) return rc;
+    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, std::string(who) + ": no device-resident state yet (admm_hip_set_state), and x is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = settle(c)) return rc;
+    HIP_TRY(force_ensure(c, out13 != nullptr, 0));
+    const double *xd = c->x.p;
+    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    launch_forces(c, xd, out13 != nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> sd(out13 && c->nt ? (size_t)kStressQ * c->ldt : 0);      // (a scene without tets has no stress)
+    if (f && c->n3) HIP_TRY(hipMemcpyAsync(f, c->f_out.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!sd.empty()) HIP_TRY(hipMemcpyAsync(sd.data(), c->f_stress.p, sd.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out13)      // device order (tets sorted by model) -> the caller's tet order
+        for (int n = 0; n < c->nt; ++n)
+            for (int q = 0; q < kStressQ; ++q) out13[(size_t)kStressQ * c->tet_perm[n] + q] = sd[(size_t)q * c->ldt + n];
+    return ADMM_HIP_OK;
+}
+int admm_hip_forces(admm_hip_ctx *c, const double *x, double *f) { return forces_impl(c, "forces", x, f, nullptr); }
+int admm_hip_stress(admm_hip_ctx *c, const double *x, double *out13) { return forces_impl(c, "stress", x, nullptr, out13); }
+
 int admm_hip_residuals(admm_hip_ctx *c, const double *x, const double *z, const double *z_prev, double *out4) {
     if (!c || !x || !z || !z_prev || !out4) return fail(ADMM_HIP_ERR_ARG, "residuals: NULL argument");
     if (int rc = mon_refuse(c, "residuals")) return rc;
@@ -3572,7 +3666,7 @@ int admm_hip_residuals(admm_hip_ctx *c, const double *x, const double *z, const 
 
 int admm_hip_set_monitor(admm_hip_ctx *c, int32_t mode) {
     if (!c) return fail(ADMM_HIP_ERR_ARG, "set_monitor: NULL context");
-    if (mode < 0 || mode > 2) return fail(ADMM_HIP_ERR_ARG, "set_monitor: mode must be 0 (off), 1 (residuals) or 2 (residuals + objective)");
+    if (mode < 0 || mode > 3) return fail(ADMM_HIP_ERR_ARG, "set_monitor: mode must be 0 (off), 1 (residuals), 2 (residuals + objective) or 3 (2 + stationarity)");
     if (mode != 0) { if (int rc = mon_refuse(c, "set_monitor")) return rc; }
     c->mon_mode = mode;
     return ADMM_HIP_OK;
@@ -3589,12 +3683,14 @@ int admm_hip_get_monitor(admm_hip_ctx *c, int32_t cap, int32_t *n, double *recor
     if (m <= 0) return ADMM_HIP_OK;
     std::vector<double> h((size_t)kMonQ * m);
     HIP_TRY(hipMemcpy(h.data(), c->mon_rec.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> hs((size_t)std::min(m, c->mon_stat_n));      // mode 3: the stationarity sums (forces.hpp)
+    if (!hs.empty()) HIP_TRY(hipMemcpy(hs.data(), c->f_stat.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
     const double half_idt2 = 0.5 / (c->dt * c->dt);
     for (int s = 0; s < m; ++s) {
         const double *q = h.data() + (size_t)kMonQ * s;
         double *r = records + 8 * (size_t)s;
         for (int i = 0; i < 4; ++i) r[i] = std::sqrt(q[i]);
-        r[4] = (q[4] + q[5]) + q[6]; r[5] = half_idt2 * q[7]; r[6] = r[4] + r[5]; r[7] = 0.0;
+        r[4] = (q[4] + q[5]) + q[6]; r[5] = half_idt2 * q[7]; r[6] = r[4] + r[5]; r[7] = (size_t)s < hs.size() ? std::sqrt(hs[s]) : 0.0;
     }
     return ADMM_HIP_OK;
 }

@@ -29,7 +29,8 @@ struct SolverSettings {
     double constraint_w; // -ck  (-1 = automatic)
     int soft_modes;      // -sm  (GPU build, appended: the reference's fields keep their order) every PCG solve ends with an exact Galerkin step on
                          //      the k softest modes of the system matrix (admm_hip_compute_soft_modes at initialize); 0 = off
-    int monitor;         //      (GPU build, appended) ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
+    int monitor;         //      (GPU build, appended) ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective,
+                         //      3 = 2 + stationarity; -monitor
     double admm_tol;     // -tol (GPU build, appended) early exit of a step's ADMM loop (admm_hip_set_admm_stop): the loop stops after the iteration whose
                          //      residuals meet  |W(Dx - z)| <= tol max(|W z|, |W D x|)  and  |W(z - z_prev)| <= tol |W z|; 0 = off
     int admm_min_iters;  //      (GPU build, appended) ... but not before this many iterations (>= 1)
@@ -48,8 +49,12 @@ struct SolverRuntimeData {
 
 // One ADMM iteration of the last step as the monitor recorded it (Settings::monitor; include/admm_hip.h: admm_hip_get_monitor), taken after
 // the iteration's global solve: primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x|; elastic energy, inertia term
-// 1/(2 dt^2) |x - x_bar|^2_M and their sum, the objective (the last three 0 with monitor = 1).
-struct AdmmRecord { double primal, dz, wz, wdx, energy, inertia, objective; };
+// 1/(2 dt^2) |x - x_bar|^2_M and their sum, the objective (the last three 0 with monitor = 1); stationarity = |(M (x - x_bar) / dt^2 +
+// grad E(x))_free| over the nodes without an active pin (monitor = 3, else 0).
+struct AdmmRecord { double primal, dz, wz, wdx, energy, inertia, objective, stationarity; };
+// Stress of one tet (include/admm_hip.h: admm_hip_stress): first Piola-Kirchhoff stress P = dpsi/dF column-major, the signed stretches, the von
+// Mises stress of the Cauchy stress P F^T / J (at J -> 0: what the arithmetic gives)
+struct TetStress { double P[9], stretches[3], von_mises; };
 
 } // namespace solver_detail
 
@@ -58,6 +63,7 @@ public:
     typedef solver_detail::SolverSettings Settings;
     typedef solver_detail::SolverRuntimeData RuntimeData;
     typedef solver_detail::AdmmRecord AdmmRecord;
+    typedef solver_detail::TetStress TetStress;
 
     Solver();
     virtual ~Solver();
@@ -102,6 +108,10 @@ public:
     std::shared_ptr<LinearSolver> linear_solver() { return m_linsolver; }
     // Sum of EnergyTerm::energy(D, x) over all terms (pins have none), reduced on the device (admm_hip_energy); after initialize()
     double energy(const VecX &x);
+    // Internal forces f = -dE/dx of that energy, three values per node, and the stress of every tet term in the order of energyterms
+    // (admm_hip_forces, admm_hip_stress); after initialize()
+    VecX forces(const VecX &x);
+    std::vector<TetStress> stress(const VecX &x);
     // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)
@@ -112,6 +122,7 @@ protected:
     void release();
     void *m_ctx;                                                  // admm_hip_ctx
     bool initialized;
+    int m_n_tets;                                                 // tet terms handed to the context at initialize()
     Settings m_settings;
     RuntimeData m_runtime;
     std::vector<AdmmRecord> m_history;

@@ -364,7 +364,7 @@ int LinearSolver::solve(VecX &x, const VecX &b) {
 }
 
 // ---------------------------------------------------------------- Solver ----------------------------
-Solver::Solver() : device(0), obstacle_grid_nodes(64), obstacle_grid_lo(0, 0, 0), obstacle_grid_hi(0, 0, 0), build_global_matrices(true), m_ctx(nullptr), initialized(false), m_constraints(std::make_shared<ConstraintSet>()) {}
+Solver::Solver() : device(0), obstacle_grid_nodes(64), obstacle_grid_lo(0, 0, 0), obstacle_grid_hi(0, 0, 0), build_global_matrices(true), m_ctx(nullptr), initialized(false), m_n_tets(0), m_constraints(std::make_shared<ConstraintSet>()) {}
 Solver::~Solver() { release(); }
 void Solver::release() { if (m_ctx) { admm_hip_destroy((admm_hip_ctx *)m_ctx); m_ctx = nullptr; } }
 
@@ -515,6 +515,7 @@ bool Solver::initialize(const Settings &settings_) { // src/Solver.cpp:167-261
     d.vert_xyz = m_x.data();      // smooth coordinates for the coarse space of the on-chip PCG (the solve does not depend on them)
     flat.tabulate();              // user-defined xu::Spline objects -> device tables
     flat.fill(d);
+    m_n_tets = d.n_tets;
     // pins that are not energy terms (linsolver 1) go through the in-sweep pin list
     std::vector<int32_t> gs_v; std::vector<double> gs_p, gs_n;
     if (m_settings.linsolver == 1) {
@@ -611,7 +612,7 @@ void Solver::step() { // src/Solver.cpp:35-110
         check(admm_hip_get_monitor(ctx, (int32_t)(rec.size() / 8), &n, rec.data()), "Solver::step (monitor)");
         for (int s = 0; s < std::min((int)n, (int)(rec.size() / 8)); ++s) {
             const double *r = rec.data() + 8 * (size_t)s;
-            m_history.push_back(AdmmRecord{r[0], r[1], r[2], r[3], r[4], r[5], r[6]});
+            m_history.push_back(AdmmRecord{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]});
         }
     }
     if (m_settings.verbose > 0) m_runtime.print(m_settings);
@@ -629,6 +630,25 @@ double Solver::energy(const VecX &x) {
     double tot[4] = {0.0, 0.0, 0.0, 0.0};
     check(admm_hip_energy((admm_hip_ctx *)m_ctx, x.data(), tot, nullptr), "Solver::energy");
     return tot[3];
+}
+
+VecX Solver::forces(const VecX &x) {
+    if (!initialized) throw std::runtime_error("Solver::forces: initialize() first");
+    if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::forces: x must hold three values per node");
+    VecX f(m_x.rows());
+    check(admm_hip_forces((admm_hip_ctx *)m_ctx, x.data(), f.data()), "Solver::forces");
+    return f;
+}
+
+std::vector<Solver::TetStress> Solver::stress(const VecX &x) {
+    if (!initialized) throw std::runtime_error("Solver::stress: initialize() first");
+    if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::stress: x must hold three values per node");
+    admm_hip_ctx *ctx = (admm_hip_ctx *)m_ctx;
+    const int n_tets = m_n_tets;      // one entry per tet term, in the order of energyterms
+    std::vector<TetStress> out(n_tets);
+    static_assert(sizeof(TetStress) == 13 * sizeof(double), "TetStress is the 13 doubles of admm_hip_stress");
+    check(admm_hip_stress(ctx, x.data(), n_tets ? &out[0].P[0] : nullptr), "Solver::stress");
+    return out;
 }
 
 void Solver::save_matrix(const std::string &filename) { // src/Solver.cpp:264-269 (Ahat; A = diag(m) + Ahat (x) I3)
@@ -653,6 +673,7 @@ const Switch kSwitches[] = {
     {"-ck", &Solver::Settings::constraint_w, nullptr, "constraint weights (-1 = auto) "},
     {"-sm", nullptr, &Solver::Settings::soft_modes, "soft modes of the PCG's end projection (GPU build; 0 = off) "},
     {"-tol", &Solver::Settings::admm_tol, nullptr, "early exit of the admm loop on its residuals (GPU build; 0 = off) "},
+    {"-monitor", nullptr, &Solver::Settings::monitor, "ADMM monitor (GPU build; 0 = off, 1 residuals, 2 + objective, 3 + stationarity) "},
 };
 bool wants_help(const char *a) { const std::string s(a); return s == "-help" || s == "--help" || s == "-h"; }
 } // namespace

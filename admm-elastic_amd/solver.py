@@ -64,7 +64,7 @@ class Settings:
         self.device = 0
         self.rank = 0
         self.world_size = 1
-        self.monitor = 0             # GPU build: ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective
+        self.monitor = 0             # GPU build: ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective, 3 = 2 + stationarity
         self.admm_tol = 0.0          # GPU build: early exit of a step's ADMM loop on its residuals (admm_hip_set_admm_stop); 0 = off
         self.admm_min_iters = 1      #            ... but not before this many iterations
         for k, v in kw.items():
@@ -595,6 +595,31 @@ class Solver:
             out["terms"] = terms
         return out
 
+    def _state_arg(self, x, who):
+        xc = None if x is None else f64(x).ravel().copy()
+        if xc is not None and xc.size != self.m_x.size:
+            raise ValueError(who + ": x must hold 3 values per node")
+        return xc
+
+    def forces(self, x=None):
+        """admm_hip_forces: the internal forces f = -dE/dx [n_verts, 3] of the energy energy() sums, at x (default: the device-resident
+        state).  Triangles ignore their strain limits, pins add nothing."""
+        self._need_ctx()
+        xc = self._state_arg(x, "forces")
+        f = np.zeros(self.m_x.size)
+        check(lib().admm_hip_forces(self._ctx, dptr(xc), dptr(f)))
+        return f.reshape(-1, 3)
+
+    def stress(self, x=None):
+        """admm_hip_stress: per tet, in the order the tets were added: dict(P [n, 3, 3] = dpsi/dF, stretches [n, 3] (signed),
+        von_mises [n] of the Cauchy stress P F^T / J).  At J -> 0 von_mises is what the arithmetic gives."""
+        self._need_ctx()
+        xc = self._state_arg(x, "stress")
+        f = getattr(self, "_flat", None) or self.flatten()
+        out = np.zeros((f["tet_idx"].shape[0], 13))
+        check(lib().admm_hip_stress(self._ctx, dptr(xc), dptr(out)))
+        return dict(P=out[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1).copy(), stretches=out[:, 9:12].copy(), von_mises=out[:, 12].copy())
+
     def residuals(self, x, z, z_prev):
         """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""
         self._need_ctx()
@@ -607,7 +632,8 @@ class Solver:
         return tuple(out)
 
     def set_monitor(self, mode):
-        """admm_hip_set_monitor: 0 off, 1 residuals, 2 residuals + objective per ADMM iteration; in effect from the next step."""
+        """admm_hip_set_monitor: 0 off, 1 residuals, 2 residuals + objective, 3 = 2 + stationarity per ADMM iteration; in effect from
+        the next step."""
         self._need_ctx()
         check(lib().admm_hip_set_monitor(self._ctx, int(mode)))
         self._settings.monitor = int(mode)
@@ -630,14 +656,15 @@ class Solver:
     def admm_history(self):
         """Records of the last step (admm_hip_get_monitor), one entry per ADMM iteration, taken after its global solve: dict of arrays
         primal = |W(Dx - z)|, dz = |W(z - z_prev)|, wz = |W z|, wdx = |W D x|, energy, inertia = 1/(2 dt^2) |x - x_bar|^2_M,
-        objective = energy + inertia (the last three zero in mode 1).  Empty arrays when the step ran with the monitor off."""
+        objective = energy + inertia (the last three zero in mode 1), stationarity = |(M (x - x_bar) / dt^2 + grad E(x))_free| over the
+        vertices without an active pin (mode 3, zero otherwise).  Empty arrays when the step ran with the monitor off."""
         self._need_ctx()
         n = C.c_int32(0)
         check(lib().admm_hip_get_monitor(self._ctx, 0, C.byref(n), None))
         rec = np.zeros((n.value, 8))
         if n.value:
             check(lib().admm_hip_get_monitor(self._ctx, n.value, C.byref(n), dptr(rec)))
-        keys = ("primal", "dz", "wz", "wdx", "energy", "inertia", "objective")
+        keys = ("primal", "dz", "wz", "wdx", "energy", "inertia", "objective", "stationarity")
         return {k: rec[:, i].copy() for i, k in enumerate(keys)}
 
     def set_solver_params(self, kind, max_iters=0, tol=-1.0, omega=0.0):

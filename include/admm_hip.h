@@ -289,17 +289,29 @@ int admm_hip_solve_totals(admm_hip_ctx *ctx, int64_t *solves, int64_t *converged
  * bit-reproducible from run to run (no floating-point atomics).  Single-GPU contexts only.  Synchronises the stream. */
 int admm_hip_energy(admm_hip_ctx *ctx, const double *x, double *totals4, double *per_term);
 
+/* Internal forces f = -dE/dx of the energy admm_hip_energy sums (the same sign rules, triangles without their strain limits, hinges; pins
+ * add nothing), and the per-tet stress from the same pass.  No reference code exists (TetEnergyTerm::gradient and TriEnergyTerm::gradient
+ * throw): the forces are the gradient of the energies.  out13 [13 n_tets]: per tet the first Piola-Kirchhoff stress P = dpsi/dF column-major
+ * (9), the signed stretches (3), the von Mises stress of the Cauchy stress P F^T / J (1).  Limits: at a stretch of exactly 0 the kinds
+ * evaluated at |sigma| (linear, Neo-Hookean, every SplineTet) have a kink and the force is a one-sided derivative; at J -> 0 the Cauchy
+ * stress, and for a collapsed triangle its force, are what the arithmetic gives (inf / NaN), nothing is clamped.  Bit-reproducible from run
+ * to run.  Single-GPU contexts only.  Both synchronise the stream. */
+int admm_hip_forces(admm_hip_ctx *ctx, const double *x, double *f);      /* x [3 n_verts] host or NULL = device-resident state; f [3 n_verts] = -dE/dx */
+int admm_hip_stress(admm_hip_ctx *ctx, const double *x, double *out13);  /* [13 n_tets], the CALLER's tet order (tet_perm, as energy's per_term) */
+
 /* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
  * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
 int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
 
-/* Monitor of admm_hip_step: 0 off (default), 1 residuals, 2 residuals + objective.  In effect from the next step.  Off, a step is what it
+/* Monitor of admm_hip_step: 0 off (default), 1 residuals, 2 residuals + objective, 3 = 2 + the stationarity residual of implicit Euler,
+ * |(M (x - x_bar) / dt^2 + grad E(x))_free| over the vertices without an active pin (one force pass more per iteration; contact reactions
+ * are not subtracted, so with colliders the figure contains them).  In effect from the next step.  Off, a step is what it
  * was: no launch more, no kernel changed.  On, the local step also stores z and one reduction over the terms follows every global solve, on
  * the context's stream, without any host synchronisation.  Single-GPU contexts only. */
 int admm_hip_set_monitor(admm_hip_ctx *ctx, int32_t mode);
 /* Records of the LAST step, one per ADMM iteration s, taken after that iteration's global solve with x = x^{s+1}, z = z^{s+1},
  * z_prev = z^{s} (z^0 = D m_x at step entry, src/Solver.cpp:70).  records [cap][8]: the four norms above, elastic energy,
- * inertia term 1/(2 dt^2) |x - x_bar|^2_M, their sum (the objective; the last three 0 in mode 1), 0.
+ * inertia term 1/(2 dt^2) |x - x_bar|^2_M, their sum (the objective; the last three 0 in mode 1), the stationarity residual (mode 3; 0 otherwise).
  * *n = iterations recorded (may exceed cap; 0 when the last step ran with the monitor off).  Synchronises the stream. */
 int admm_hip_get_monitor(admm_hip_ctx *ctx, int32_t cap, int32_t *n, double *records);
 
