@@ -24,6 +24,7 @@
 #include "kernels.hpp"
 #include "monitor.hpp"
 #include "forces.hpp"
+#include "tangent.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
 #include "gs_persist.hpp"
@@ -398,6 +399,10 @@ struct admm_hip_ctx {
     // by the first call that needs them -- the step's t_rec, r_cf, h_cf are not borrowed
     DevBuf<double> f_rec, f_rcf, f_hcf, f_out, f_stress, f_part, f_stat;   // records, corner forces, f [3 nv], stress [13][ldt], block partials, sums [admm_iters]
     int mon_stat_n = 0;      // stationarity sums the last step wrote (mode 3), else 0
+    // tangent stiffness (tangent.hpp; admm_hip_stiffness_apply): buffers of their own for k_cap directions, allocated by the first call
+    // and again by a call with more directions
+    DevBuf<double> k_rec, k_rcf, k_hcf, k_d, k_out;      // records, corner contributions, the directions and the result [k_cap][3 nv]
+    int k_cap = 0;
 
     ~admm_hip_ctx() {      // (every DevBuf member, lane and dynamic collider frees its own memory after this body)
         (void)hipSetDevice(device);
@@ -634,6 +639,56 @@ void launch_forces(admm_hip_ctx *c, const double *x, bool stress, const int *sto
     g.order = c->g_order.p; g.f = c->f_out.p; g.stop = stop;
     hipLaunchKernelGGL(k_gather_forces, dim3(std::max(1, (g.n_slices + 3) / 4)), dim3(256), 0, c->stream, g);
 }
+// ---- tangent stiffness (tangent.hpp) ----
+// buffers for n_vec directions; the padding record / element of every direction must be zero: zeroed on the context's stream
+hipError_t tangent_ensure(admm_hip_ctx *c, int n_vec) {
+    if (n_vec <= c->k_cap) return hipSuccess;
+    hipError_t e;
+    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
+        const hipError_t e2 = b.alloc(n);
+        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
+    };
+    c->k_cap = 0;
+    const size_t k = (size_t)n_vec;
+    if (c->nt && (e = fresh(c->k_rec, k * 4 * (c->n_rec + 1))) != hipSuccess) return e;
+    if (c->ntri && (e = fresh(c->k_rcf, k * 12 * c->ldr)) != hipSuccess) return e;
+    if (c->nbend && (e = fresh(c->k_hcf, k * 12 * c->ldb)) != hipSuccess) return e;
+    if ((e = fresh(c->k_d, k * std::max(1, c->n3))) != hipSuccess) return e;
+    if ((e = fresh(c->k_out, k * std::max(1, c->n3))) != hipSuccess) return e;
+    c->k_cap = n_vec;
+    return hipSuccess;
+}
+// k_out[j] = K(x) k_d[j] + shift m o k_d[j], j < n_vec, at positions x (device)
+void launch_tangent(admm_hip_ctx *c, const double *x, int n_vec, double shift) {
+    TangentArgs t{};
+    ForceArgs &a = t.f;
+    a.x = x; a.dt2 = c->dt * c->dt;
+    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
+    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
+    for (int i = 0; i < 6; ++i) { a.kb[i] = c->kind_begin[i]; a.cb[i] = c->chunk_base[i]; }
+    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = c->k_rec.p;
+    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_cf = c->k_rcf.p;
+    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_k = c->h_kst.p; a.h_cf = c->k_hcf.p;
+    a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
+    t.d = c->k_d.p; t.n_vec = n_vec;
+    t.d_stride = (size_t)c->n3; t.rec_stride = (size_t)4 * (c->n_rec + 1); t.rcf_stride = (size_t)12 * c->ldr; t.hcf_stride = (size_t)12 * c->ldb;
+    const int nb = a.nb_r + blocks_for(c->nbend);
+    if (nb > 0) {
+        if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent<true>, dim3(nb), dim3(256), 0, c->stream, t);
+        else hipLaunchKernelGGL(k_tangent<false>, dim3(nb), dim3(256), 0, c->stream, t);
+    }
+    TangentGatherArgs q{};
+    ForceGatherArgs &g = q.g;
+    g.nv = c->nv; g.n_slices = (c->nv + 63) / 64;
+    if (c->nt > 0) { g.t_ptr = c->t_inc.ptr.p; g.t_w = c->t_inc.w.p; g.t_inc = c->t_inc.idx.p; g.t_rec = c->k_rec.p; }
+    if (c->ntri > 0) { g.r_ptr = c->r_inc.ptr.p; g.r_w = c->r_inc.w.p; g.r_inc = c->r_inc.idx.p; g.r_cf = c->k_rcf.p; g.r_ld = c->ldr; }
+    if (c->nbend > 0) { g.h_ptr = c->h_inc.ptr.p; g.h_w = c->h_inc.w.p; g.h_inc = c->h_inc.idx.p; g.h_cf = c->k_hcf.p; g.h_ld = c->ldb; }
+    g.order = c->g_order.p; g.f = c->k_out.p;
+    q.d = c->k_d.p; q.m = c->m.p; q.shift = shift;
+    q.d_stride = t.d_stride; q.rec_stride = t.rec_stride; q.rcf_stride = t.rcf_stride; q.hcf_stride = t.hcf_stride;
+    hipLaunchKernelGGL(k_gather_tangent, dim3(std::max(1, (g.n_slices + 3) / 4), n_vec), dim3(256), 0, c->stream, q);
+}
+
 // monitor mode 3, record s of the running step: the stationarity sum at x = curr into f_stat[s].  Launched BEFORE the record's decision
 // (k_mon_decide), so the last executed iteration of a step with early exit has its figure.
 void launch_stationarity(admm_hip_ctx *c, int s) {
@@ -3631,6 +3686,27 @@ static int forces_impl(admm_hip_ctx *c, const char *who, const double *x, double
 }
 int admm_hip_forces(admm_hip_ctx *c, const double *x, double *f) { return forces_impl(c, "forces", x, f, nullptr); }
 int admm_hip_stress(admm_hip_ctx *c, const double *x, double *out13) { return forces_impl(c, "stress", x, nullptr, out13); }
+
+// out_j = K(x) d_j + shift (m o d_j), K = d2E/dx2 at x (host, or NULL = the device-resident state): one tangent pass (tangent.hpp)
+int admm_hip_stiffness_apply(admm_hip_ctx *c, const double *x, int32_t n_vec, const double *d, double shift, double *out) {
+    if (!c || !d || !out || n_vec < 1 || n_vec > 65535) return fail(ADMM_HIP_ERR_ARG, "stiffness_apply: NULL argument, n_vec < 1 or n_vec > 65535");
+    if (int rc = mon_refuse(c, "stiffness_apply")) return rc;
+    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, "stiffness_apply: no device-resident state yet (admm_hip_set_state), and x is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = settle(c)) return rc;
+    HIP_TRY(tangent_ensure(c, n_vec));
+    const double *xd = c->x.p;
+    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    const size_t n = (size_t)n_vec * c->n3;
+    if (n) HIP_TRY(hipMemcpyAsync(c->k_d.p, d, n * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_tangent(c, xd, n_vec, shift);
+    HIP_TRY(hipGetLastError());
+    if (n) HIP_TRY(hipMemcpyAsync(out, c->k_out.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
 
 int admm_hip_residuals(admm_hip_ctx *c, const double *x, const double *z, const double *z_prev, double *out4) {
     if (!c || !x || !z || !z_prev || !out4) return fail(ADMM_HIP_ERR_ARG, "residuals: NULL argument");

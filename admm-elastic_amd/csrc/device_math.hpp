@@ -967,4 +967,211 @@ __device__ __forceinline__ void prox_tri(const double *q, double lmin, double lm
     }
 }
 
+// ---- TANGENT STIFFNESS of one element: dP = (d2 psi / dF2) : dF  (tangent.hpp: k_tangent; tests/hostmath/tangent_host.cpp) -------------
+// No reference code (the reference's gradient() throws, a Hessian does not exist there).  For a tet with F = U diag(sigma) V^T (the signed
+// SVD) and psi an isotropic density, with A = U^T dF V:  dP = U B V^T,
+//     B_ii = sum_j Hs_ij A_jj,                                   Hs = d2 psi / dsigma2
+//     B_ij = al_ij (A_ij + A_ji) / 2 + be_ij (A_ij - A_ji) / 2,  al_ij = (p_i - p_j) / (sigma_i - sigma_j)   (twist)
+//                                                                be_ij = (p_i + p_j) / (sigma_i + sigma_j)   (flip)
+// p = dpsi/dsigma.  The quotients are never formed as written: every density here has a closed-form divided difference.  With e the
+// stretches as the density takes them (e = |sigma|, or e = sigma for StVK and stable Neo-Hookean), g = dpsi/de, (i, j, l) a permutation:
+//     linear        g_i = k (e_i - 1)                          al' = k                               be' = k ((e_i - 1) + (e_j - 1)) / (e_i + e_j)
+//     Neo-Hookean   g_i = mu (e_i - 1/e_i) + la lnJ / e_i      al' = mu + (mu - la lnJ) / (e_i e_j)  be' = mu - (mu - la lnJ) / (e_i e_j)
+//     StVK          g_i = e_i (mu (e_i^2 - 1) + la trE)        al' = mu (e_i^2 + e_i e_j + e_j^2 - 1) + la trE,  be': with - e_i e_j
+//     co-rotated    g_i = 2 mu (e_i - 1) + la tr               al' = 2 mu                            be' = (g_i + g_j) / (e_i + e_j)
+//     + c(J)        g_i += c' e_j e_l                          al' -= c' e_l                         be' += c' e_l
+//     stable NH     g_i = a1 e_i + la_s (J - alpha) e_j e_l    al' = a1 - la_s (J - alpha) e_l       be' = a1 + la_s (J - alpha) e_l
+//     tabulated     g_i = f'(e_i) + g'(e_i e_j) e_j + g'(e_i e_l) e_l + h'(J) e_j e_l
+//                   al' = [f'](e_i, e_j) - g'(e_i e_j) + e_l^2 [g'](e_i e_l, e_j e_l) - h'(J) e_l,   be' = (g_i + g_j) / (e_i + e_j)
+// [F'](x, y) = (F'(x) - F'(y)) / (x - y) = the mean of F'' between y and x: the quotient where x and y are 5 % apart (it loses 20 ulp
+// there), the 3-point Gauss mean of the table's F'' where they are closer (exact for the interpolant's quintic pieces; across a node
+// the interpolant's F''' jumps by the table's own representation error).  For the kinds taken at e = |sigma| the frame U diag(s) is an
+// SVD of F with the unsigned stretches, in which the formulas hold as they stand with e_i + e_j > 0: carried back to the signed frame
+// that is Hs_ij = s_i s_j H_ij and (al, be)_ij = (al', be')_ij, swapped where s_i s_j < 0 -- the energy is smooth at sigma_i = -sigma_j.
+// StVK and stable Neo-Hookean take the signed stretches: their be' is a polynomial, finite at sigma_i = -sigma_j as well.
+// Limits, as for the forces (forces.hpp): at a stretch sigma_i = 0 the |sigma| kinds have a kink (sign(0) counts as +, be' divides by
+// e_i + e_j) and the Neo-Hookean kinds a log barrier at J -> 0; the outputs there are what the arithmetic gives, nothing is clamped.
+// Nor is the tangent projected to a positive semi-definite one.
+__device__ __forceinline__ double spline_table_dd1(const double *tab, double x, double y, double f1x, double f1y) {
+    const double d = x - y;
+    if (fabs(d) > 0.05 * fmax(fabs(x), fabs(y))) return (f1x - f1y) / d;
+    const double m = 0.5 * (x + y), r = 0.5 * d * 0.7745966692414834;      // sqrt(3 / 5)
+    double f0, f1, c, lo, hi;
+    spline_table_eval(tab, m, f0, f1, c);
+    spline_table_eval(tab, m - r, f0, f1, lo);
+    spline_table_eval(tab, m + r, f0, f1, hi);
+    return fma(4.0 / 9.0, c, (5.0 / 18.0) * (lo + hi));
+}
+// the tabulated spline's Hs, al', be' at the unsigned stretches A (out of line: 25 table evaluations that only this model pays for)
+__device__ __attribute__((noinline)) inline void tet_tangent_table(const double *tab, const double *A, double *Hs, double *al, double *be) {
+    const int pi[3] = {0, 0, 1}, pj[3] = {1, 2, 2}, pl[3] = {2, 1, 0};
+    double g[3];
+    SplineTableModel m; m.type = 1; m.tab = tab; m.mu = 0.0; m.la = 0.0; m.k = 0.0; m.lo = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+    (void)m.eval(A, g, Hs);
+    const double *tf = tab, *tg = tab + kSplineFnDoubles, *th = tab + 2 * kSplineFnDoubles;
+    double f0, f2, f1[3], g1[3], h1;      // f'(e_i); g' at the products e_0 e_1, e_0 e_2, e_1 e_2; h'(J)
+    const double pr[3] = {A[0] * A[1], A[0] * A[2], A[1] * A[2]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { spline_table_eval(tf, A[i], f0, f1[i], f2); spline_table_eval(tg, pr[i], f0, g1[i], f2); }
+    spline_table_eval(th, A[0] * A[1] * A[2], f0, h1, f2);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int i = pi[q], j = pj[q], l = pl[q];
+        // the products e_i e_l and e_j e_l: pairs (0,1) -> pr[1], pr[2]; (0,2) -> pr[0], pr[2]; (1,2) -> pr[0], pr[1]
+        const int qi = q == 0 ? 1 : 0, qj = q == 2 ? 1 : 2;
+        al[q] = spline_table_dd1(tf, A[i], A[j], f1[i], f1[j]) - g1[q]
+              + A[l] * A[l] * spline_table_dd1(tg, pr[qi], pr[qj], g1[qi], g1[qj]) - h1 * A[l];
+        be[q] = (g[i] + g[j]) / (A[i] + A[j]);
+    }
+}
+// Hs = {h00, h01, h02, h11, h12, h22}, al and be for the pairs (0,1), (0,2), (1,2), all in the frame of the signed SVD.
+// grp: the tet's model group (0 linear, 1 Neo-Hookean, 2 StVK, 3 co-rotated, 4 the dense-Hessian models by `type`, kernels.hpp: Mat)
+// TABLE = false: for callers that hold no tabulated spline (type 3 cannot occur) -- the table path and its registers are compiled out
+template <bool TABLE = true>
+__device__ __forceinline__ void tet_tangent_coef(int grp, int type, double mu, double la, double k, double kappa, const double *tab,
+                                                 const double *S, double *Hs, double *al, double *be) {
+    const double A[3] = {fabs(S[0]), fabs(S[1]), fabs(S[2])};
+    const int pi[3] = {0, 0, 1}, pj[3] = {1, 2, 2}, pl[3] = {2, 1, 0}, ph[3] = {1, 2, 4};
+    double g[3], D[3], w[3];
+    bool use_abs = true;
+    if (grp == 0) {
+        Hs[0] = k; Hs[3] = k; Hs[5] = k; Hs[1] = 0.0; Hs[2] = 0.0; Hs[4] = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int i = pi[q], j = pj[q];
+            al[q] = k;
+            be[q] = k * ((A[i] - 1.0) + (A[j] - 1.0)) / (A[i] + A[j]);
+        }
+    } else if (TABLE && grp == 4 && type == 3) {
+        tet_tangent_table(tab, A, Hs, al, be);
+    } else if (grp == 2 || (grp == 4 && type == 4)) {
+        use_abs = false;
+        if (grp == 2) {
+            StretchModel<2, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
+            (void)m.eval(S, g, D, w);
+            Hs[0] = fma(la * w[0], w[0], D[0]); Hs[1] = la * w[0] * w[1]; Hs[2] = la * w[0] * w[2];
+            Hs[3] = fma(la * w[1], w[1], D[1]); Hs[4] = la * w[1] * w[2]; Hs[5] = fma(la * w[2], w[2], D[2]);
+            const double c = fma(la, 0.5 * (fma(S[0], S[0], fma(S[1], S[1], S[2] * S[2])) - 3.0), -mu);      // la trE - mu
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int i = pi[q], j = pj[q];
+                const double ss = fma(S[i], S[i], S[j] * S[j]), sij = S[i] * S[j];
+                al[q] = fma(mu, ss + sij, c);
+                be[q] = fma(mu, ss - sij, c);
+            }
+        } else {
+            StableNHModel m; m.type = 0; m.mu = (4.0 / 3.0) * mu; m.la = la + (5.0 / 6.0) * mu; m.k = 0.0; m.alpha = 1.0 + 0.75 * m.mu / m.la;
+            m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
+            (void)m.eval(S, g, Hs);
+            const double IC = fma(S[0], S[0], fma(S[1], S[1], S[2] * S[2])), a1 = m.mu * (1.0 - 1.0 / (IC + 1.0));
+            const double lj = m.la * (S[0] * S[1] * S[2] - m.alpha);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { al[q] = fma(-lj, S[pl[q]], a1); be[q] = fma(lj, S[pl[q]], a1); }
+        }
+    } else {
+        // Neo-Hookean / StVK at |sigma| / co-rotated, plain (grp 1, 3) or with the compression term c(J) (grp 4, type 0..2)
+        const int base = grp == 1 ? 0 : grp == 3 ? 2 : type;
+        if (base == 0) {
+            StretchModel<1, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+            (void)m.eval(A, g, D, w);
+            const double c = fma(-la, t_log(A[0] * A[1] * A[2]), mu);      // mu - la ln J
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { const double ww = w[pi[q]] * w[pj[q]]; al[q] = fma(c, ww, mu); be[q] = fma(-c, ww, mu); }
+        } else if (base == 1) {
+            StretchModel<2, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+            (void)m.eval(A, g, D, w);
+            const double c = fma(la, 0.5 * (fma(A[0], A[0], fma(A[1], A[1], A[2] * A[2])) - 3.0), -mu);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int i = pi[q], j = pj[q];
+                const double ss = fma(A[i], A[i], A[j] * A[j]), sij = A[i] * A[j];
+                al[q] = fma(mu, ss + sij, c);
+                be[q] = fma(mu, ss - sij, c);
+            }
+        } else {
+            StretchModel<3, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+            (void)m.eval(A, g, D, w);
+            const double tr = (A[0] - 1.0) + (A[1] - 1.0) + (A[2] - 1.0);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int i = pi[q], j = pj[q];
+                al[q] = 2.0 * mu;
+                be[q] = 2.0 * fma(mu, (A[i] - 1.0) + (A[j] - 1.0), la * tr) / (A[i] + A[j]);
+            }
+        }
+        Hs[0] = fma(la * w[0], w[0], D[0]); Hs[1] = la * w[0] * w[1]; Hs[2] = la * w[0] * w[2];
+        Hs[3] = fma(la * w[1], w[1], D[1]); Hs[4] = la * w[1] * w[2]; Hs[5] = fma(la * w[2], w[2], D[2]);
+        if (grp == 4) {      // c(J) = kappa / 12 ((1 - J) / 6)^3, as SplineKappaModel::eval
+            const double J = A[0] * A[1] * A[2], t = (1.0 - J) * (1.0 / 6.0);
+            const double c1 = -kappa * (1.0 / 24.0) * t * t, c2 = kappa * (1.0 / 72.0) * t;
+            const double dJ[3] = {A[1] * A[2], A[2] * A[0], A[0] * A[1]};
+            Hs[0] = fma(c2 * dJ[0], dJ[0], Hs[0]); Hs[3] = fma(c2 * dJ[1], dJ[1], Hs[3]); Hs[5] = fma(c2 * dJ[2], dJ[2], Hs[5]);
+            Hs[1] += fma(c2 * dJ[0], dJ[1], c1 * A[2]); Hs[2] += fma(c2 * dJ[0], dJ[2], c1 * A[1]); Hs[4] += fma(c2 * dJ[1], dJ[2], c1 * A[0]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { al[q] = fma(-c1, A[pl[q]], al[q]); be[q] = fma(c1, A[pl[q]], be[q]); }
+        }
+    }
+    if (use_abs) {      // back to the frame of the signed SVD
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            if ((S[pi[q]] < 0.0) != (S[pj[q]] < 0.0)) { Hs[ph[q]] = -Hs[ph[q]]; const double t = al[q]; al[q] = be[q]; be[q] = t; }
+    }
+}
+// dP = U B V^T, B from A = U^T dF V: B_ii = sum_j Hs_ij A_jj, B_ij = a_ij A_ij + b_ij A_ji with a = (al + be) / 2, b = (al - be) / 2
+// (pairs (0,1), (0,2), (1,2)).  dF, dP column-major.
+__device__ __forceinline__ void tet_tangent_apply(const double *U, const double *V, const double *Hs, const double *a, const double *b,
+                                                  const double *dF, double *dP) {
+    double T[9], A[9], B[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(T, r, c) = fma(ADMM_M3(dF, r, 0), ADMM_M3(V, 0, c), fma(ADMM_M3(dF, r, 1), ADMM_M3(V, 1, c), ADMM_M3(dF, r, 2) * ADMM_M3(V, 2, c)));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(A, r, c) = fma(ADMM_M3(U, 0, r), ADMM_M3(T, 0, c), fma(ADMM_M3(U, 1, r), ADMM_M3(T, 1, c), ADMM_M3(U, 2, r) * ADMM_M3(T, 2, c)));
+    const double a0 = ADMM_M3(A, 0, 0), a1 = ADMM_M3(A, 1, 1), a2 = ADMM_M3(A, 2, 2);
+    ADMM_M3(B, 0, 0) = fma(Hs[0], a0, fma(Hs[1], a1, Hs[2] * a2));
+    ADMM_M3(B, 1, 1) = fma(Hs[1], a0, fma(Hs[3], a1, Hs[4] * a2));
+    ADMM_M3(B, 2, 2) = fma(Hs[2], a0, fma(Hs[4], a1, Hs[5] * a2));
+    ADMM_M3(B, 0, 1) = fma(a[0], ADMM_M3(A, 0, 1), b[0] * ADMM_M3(A, 1, 0)); ADMM_M3(B, 1, 0) = fma(a[0], ADMM_M3(A, 1, 0), b[0] * ADMM_M3(A, 0, 1));
+    ADMM_M3(B, 0, 2) = fma(a[1], ADMM_M3(A, 0, 2), b[1] * ADMM_M3(A, 2, 0)); ADMM_M3(B, 2, 0) = fma(a[1], ADMM_M3(A, 2, 0), b[1] * ADMM_M3(A, 0, 2));
+    ADMM_M3(B, 1, 2) = fma(a[2], ADMM_M3(A, 1, 2), b[2] * ADMM_M3(A, 2, 1)); ADMM_M3(B, 2, 1) = fma(a[2], ADMM_M3(A, 2, 1), b[2] * ADMM_M3(A, 1, 2));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(T, r, c) = fma(ADMM_M3(U, r, 0), ADMM_M3(B, 0, c), fma(ADMM_M3(U, r, 1), ADMM_M3(B, 1, c), ADMM_M3(U, r, 2) * ADMM_M3(B, 2, c)));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(dP, r, c) = fma(ADMM_M3(T, r, 0), ADMM_M3(V, c, 0), fma(ADMM_M3(T, r, 1), ADMM_M3(V, c, 1), ADMM_M3(T, r, 2) * ADMM_M3(V, c, 2)));
+}
+
+// Triangle: E = w^2 / 2 sum (sigma_i - 1)^2 of the 3x2 F, P = w^2 (F - Q), Q = F C^(-1/2) the closest isometry (C = F^T F), so
+// dP = w^2 (dF - dQ).  With F = Q S (S = C^(1/2)):  dQ = om Q J + (dF - Q Q^T dF) S^-1,  J = [[0, -1], [1, 0]],
+// om = (q_1 . dF_0 - q_0 . dF_1) / (sigma_1 + sigma_2): the in-plane rotation, and the out-of-plane part.  The closed-form 2x2 inverse
+// square root of forces.hpp.  tri_tangent_frame: Q (3x2 column-major), Si = {S^-1_00, S^-1_01, S^-1_11}, itr = 1 / (sigma_1 + sigma_2);
+// at a collapsed triangle (sigma_1 sigma_2 -> 0) the outputs are what the arithmetic gives.
+__device__ __forceinline__ void tri_tangent_frame(const double *F, double *Q, double *Si, double &itr) {
+    const double c00 = dot3(F, F), c01 = dot3(F, F + 3), c11 = dot3(F + 3, F + 3);
+    double cr[3];
+    cross3(F, F + 3, cr);
+    const double s = sqrt(dot3(cr, cr)), q = sqrt(c00 + c11 + 2.0 * s), iq = 1.0 / (q * s);
+    Si[0] = (c11 + s) * iq; Si[1] = -c01 * iq; Si[2] = (c00 + s) * iq;
+    itr = 1.0 / q;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { Q[j] = fma(F[j], Si[0], F[3 + j] * Si[1]); Q[3 + j] = fma(F[j], Si[1], F[3 + j] * Si[2]); }
+}
+// out = dF - dQ (3x2 column-major); the caller scales it by w^2
+__device__ __forceinline__ void tri_tangent_apply(const double *Q, const double *Si, double itr, const double *dF, double *out) {
+    const double m00 = dot3(Q, dF), m10 = dot3(Q + 3, dF), m01 = dot3(Q, dF + 3), m11 = dot3(Q + 3, dF + 3);
+    const double om = (m10 - m01) * itr;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double n0 = dF[j] - fma(Q[j], m00, Q[3 + j] * m10), n1 = dF[3 + j] - fma(Q[j], m01, Q[3 + j] * m11);      // (I - Q Q^T) dF
+        out[j] = dF[j] - fma(om, Q[3 + j], fma(n0, Si[0], n1 * Si[1]));
+        out[3 + j] = dF[3 + j] - fma(-om, Q[j], fma(n0, Si[1], n1 * Si[2]));
+    }
+}
+
 } // namespace admm_dev

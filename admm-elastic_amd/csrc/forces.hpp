@@ -20,7 +20,8 @@
 //
 // Limits.  At a stretch sigma_i = 0 the |sigma| kinds have a kink: the force there is a one-sided derivative (sign(0) counts as +).  The
 // stress divides by J = sigma_1 sigma_2 sigma_3 and a triangle's R by sigma_1 sigma_2: at J -> 0 (a flat tet, a collapsed triangle) the
-// outputs are what the arithmetic gives (inf / NaN), nothing is clamped.
+// outputs are what the arithmetic gives (inf / NaN), nothing is clamped.  The tangent of these forces (tangent.hpp) has the same limits:
+// a kink at sigma_i = 0 of the |sigma| kinds, the log barrier of the Neo-Hookean kinds at J -> 0, a collapsed triangle.
 //
 // REPRODUCIBLE to the bit: fixed summation orders everywhere, ordinary vector stores, no floating-point atomics.
 #pragma once

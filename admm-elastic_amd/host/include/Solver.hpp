@@ -112,6 +112,9 @@ public:
     // (admm_hip_forces, admm_hip_stress); after initialize()
     VecX forces(const VecX &x);
     std::vector<TetStress> stress(const VecX &x);
+    // K(x) d + shift (m o d), K = d2E/dx2 = -d forces / dx the exact tangent stiffness of that energy at x, m the nodal masses
+    // (admm_hip_stiffness_apply); shift = 1 / dt^2: the Jacobian of the implicit-Euler residual.  Pins are not masked; after initialize()
+    VecX stiffness_apply(const VecX &d, const VecX &x, double shift = 0.0);
     // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)

@@ -640,6 +640,14 @@ VecX Solver::forces(const VecX &x) {
     return f;
 }
 
+VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift) {
+    if (!initialized) throw std::runtime_error("Solver::stiffness_apply: initialize() first");
+    if (x.rows() != m_x.rows() || d.rows() != m_x.rows()) throw std::runtime_error("Solver::stiffness_apply: x and d must hold three values per node");
+    VecX out(m_x.rows());
+    check(admm_hip_stiffness_apply((admm_hip_ctx *)m_ctx, x.data(), 1, d.data(), shift, out.data()), "Solver::stiffness_apply");
+    return out;
+}
+
 std::vector<Solver::TetStress> Solver::stress(const VecX &x) {
     if (!initialized) throw std::runtime_error("Solver::stress: initialize() first");
     if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::stress: x must hold three values per node");

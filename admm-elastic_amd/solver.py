@@ -620,6 +620,25 @@ class Solver:
         check(lib().admm_hip_stress(self._ctx, dptr(xc), dptr(out)))
         return dict(P=out[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1).copy(), stretches=out[:, 9:12].copy(), von_mises=out[:, 12].copy())
 
+    def stiffness_apply(self, d, x=None, shift=0.0):
+        """admm_hip_stiffness_apply: K(x) d + shift * (m o d) with K = d2E/dx2 = -d forces / dx the tangent stiffness of the energy
+        energy() sums, at x (default: the device-resident state); m the nodal masses.  d is [n_verts, 3] or [k, n_verts, 3], the result
+        has the same shape; every direction of a stack equals the same direction applied alone, bit for bit.  Sign: the result is
+        +K d, so forces(x + e d) = forces(x) - e K d + O(e^2); shift = 1 / dt^2 gives the Jacobian of the implicit-Euler residual that
+        `stationarity` measures.  K is exact (not projected to a positive semi-definite matrix, not ADMM's constant matrix).  Limits:
+        triangles ignore their strain limits, pins add nothing and are not masked, at a stretch of exactly 0 (a kink of the |sigma|
+        kinds), at J -> 0 of the Neo-Hookean kinds and at a collapsed triangle the result is what the arithmetic gives.
+        Single-GPU contexts."""
+        self._need_ctx()
+        xc = self._state_arg(x, "stiffness_apply")
+        dc = f64(d).copy()
+        nv = self.m_x.size // 3
+        if dc.ndim not in (2, 3) or dc.shape[-2:] != (nv, 3) or (dc.ndim == 3 and dc.shape[0] < 1):
+            raise ValueError("stiffness_apply: d must be [n_verts, 3] or [k, n_verts, 3]")
+        out = np.zeros(dc.shape)
+        check(lib().admm_hip_stiffness_apply(self._ctx, dptr(xc), 1 if dc.ndim == 2 else dc.shape[0], dptr(dc), float(shift), dptr(out)))
+        return out
+
     def residuals(self, x, z, z_prev):
         """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""
         self._need_ctx()

@@ -299,6 +299,15 @@ int admm_hip_energy(admm_hip_ctx *ctx, const double *x, double *totals4, double 
 int admm_hip_forces(admm_hip_ctx *ctx, const double *x, double *f);      /* x [3 n_verts] host or NULL = device-resident state; f [3 n_verts] = -dE/dx */
 int admm_hip_stress(admm_hip_ctx *ctx, const double *x, double *out13);  /* [13 n_tets], the CALLER's tet order (tet_perm, as energy's per_term) */
 
+/* Tangent stiffness K(x) = d2E/dx2 = -df/dx of the same energy, applied to n_vec directions: out_j = K(x) d_j + shift (m o d_j), m the
+ * nodal masses.  x [3 n_verts] host or NULL = the device-resident state; d and out [n_vec][3 n_verts] host, 1 <= n_vec <= 65535.  shift = 0: the pure tangent
+ * stiffness; shift = 1 / dt^2: the Jacobian of the implicit-Euler residual whose squares monitor mode 3 sums.  Pins carry no energy and
+ * are not masked: the caller masks them.  K is the exact second derivative (the equal-stretch and equal-and-inverted cases in closed
+ * form), NOT projected to a positive semi-definite matrix and not ADMM's constant surrogate.  Limits as for the forces: kinks at a stretch
+ * of exactly 0, the log barrier of the Neo-Hookean kinds at J -> 0, a collapsed triangle -- what the arithmetic gives.  Every column is
+ * bit-identical to the same direction applied alone, and from run to run.  Single-GPU contexts only.  Synchronises the stream. */
+int admm_hip_stiffness_apply(admm_hip_ctx *ctx, const double *x, int32_t n_vec, const double *d, double shift, double *out);
+
 /* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
  * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
 int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
