@@ -545,28 +545,38 @@ hipError_t mon_ensure(admm_hip_ctx *c, bool zprev, bool term) {
     if (term && nterm && !c->mon_term.p && (e = c->mon_term.alloc(nterm)) != hipSuccess) return e;
     return hipSuccess;
 }
-// the kernel's view of the context at positions x; the pin rows as the step keeps them (3 per pin)
+// the scene at positions x as every pass over the terms reads it (elements.hpp)
+ElemView elem_view(const admm_hip_ctx *c, const double *x) {
+    ElemView v{};
+    v.x = x; v.dt2 = c->dt * c->dt;
+    v.nt = c->nt; v.ldt = c->ldt; v.t_idx = c->t_idx.p; v.t_Binv = c->t_Binv.p; v.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; v.t_sc = c->t_sc.p;
+    v.t_mat = c->t_mat.p; v.mats = c->mats.p; v.spl = c->spl_tab.p;
+    for (int i = 0; i < 6; ++i) v.kb[i] = c->kind_begin[i];
+    v.ntri = c->ntri; v.ldr = c->ldr; v.r_idx = c->r_idx.p; v.r_rest = c->r_rest.p; v.r_sc = c->r_sc.p;
+    v.nbend = c->nbend; v.ldb = c->ldb; v.h_idx = c->h_idx.p; v.h_coef = c->h_coef.p; v.h_k = c->h_kst.p;
+    return v;
+}
+// the monitor's view of the context at positions x; the pin rows as the step keeps them (3 per pin)
 MonArgs mon_args(const admm_hip_ctx *c, const double *x, bool nodes) {
     MonArgs a{};
-    a.x = x; a.dt2 = c->dt * c->dt;
-    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
-    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
-    for (int i = 0; i < 6; ++i) a.kb[i] = c->kind_begin[i];
+    a.v = elem_view(c, x);
     a.t_z = c->t_z.p; a.t_zp = c->mon_tzp.p;
-    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_z = c->r_z.p; a.r_zp = c->mon_rzp.p;
-    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_sc = c->h_sc.p; a.h_k = c->h_kst.p; a.h_z = c->h_z.p; a.h_zp = c->mon_hzp.p;
+    a.r_z = c->r_z.p; a.r_zp = c->mon_rzp.p;
+    a.h_sc = c->h_sc.p; a.h_z = c->h_z.p; a.h_zp = c->mon_hzp.p;
     a.npin = c->npin_terms; a.pin_dim = 3; a.pin_vert = c->pin_vert_d.p; a.pin_z = c->pin_z.p; a.pin_zp = c->mon_pzp.p; a.pin_w2 = c->pin_weight * c->pin_weight;
     a.n3 = c->n3; a.m = nodes ? c->m.p : nullptr; a.Mxbar = c->Mxbar.p;
     a.nb_t = blocks_for(c->nt); a.nb_r = a.nb_t + blocks_for(c->ntri); a.nb_h = a.nb_r + blocks_for(c->nbend); a.nb_p = a.nb_h + blocks_for(c->npin_terms);
     a.part = c->mon_part.p; a.term = nullptr; a.stop = c->stop_dev;
     return a;
 }
-// one pass over the terms + the sum of its partials into out [kMonQ] (device)
-template <bool RES, bool ENERGY>
-void launch_monitor(admm_hip_ctx *c, const MonArgs &a, double *out) {
+// one pass over the terms + the sum of its partials into out [kMonQ] (device).  s >= 0: record s of a step with early exit -- k_mon_decide
+// in the place of k_mon_final, the same record, then the decision on it (STOP: the pass itself reads the stop word)
+template <bool RES, bool ENERGY, bool STOP = false>
+void launch_monitor(admm_hip_ctx *c, const MonArgs &a, double *out, int s = -1) {
     const int nb = std::max(1, a.nb_p + (a.m ? blocks_for(a.n3) : 0));
-    hipLaunchKernelGGL((k_monitor<RES, ENERGY, false>), dim3(nb), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(k_mon_final, dim3(1), dim3(256), 0, c->stream, a.part, nb, out);
+    hipLaunchKernelGGL((k_monitor<RES, ENERGY, false, STOP>), dim3(nb), dim3(256), 0, c->stream, a);
+    if (s < 0) hipLaunchKernelGGL(k_mon_final, dim3(1), dim3(256), 0, c->stream, a.part, nb, out);
+    else hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig);
 }
 // z_prev <- D x: the reference's curr_z = D m_x at step entry (src/Solver.cpp:70)
 void launch_monitor_init(admm_hip_ctx *c, const double *x) {
@@ -574,25 +584,18 @@ void launch_monitor_init(admm_hip_ctx *c, const double *x) {
     if (a.nb_p > 0) hipLaunchKernelGGL((k_monitor<false, false, true>), dim3(a.nb_p), dim3(256), 0, c->stream, a);
 }
 // record s of the running step: after the global solve of ADMM iteration s, x = curr
-// decide = true (a step with early exit): k_mon_decide in the place of k_mon_final -- the same record, then the decision on it; with
-// c->stop_dev the pass itself is the STOP instantiation
+// decide = true: a step with early exit; with c->stop_dev the pass itself is the STOP instantiation
 void launch_monitor_step(admm_hip_ctx *c, int s, bool decide = false) {
     const MonArgs a = mon_args(c, c->curr.p, c->mon_mode >= 2);
     double *out = c->mon_rec.p + (size_t)kMonQ * s;
-    if (!decide) {
-        if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, out);
-        else launch_monitor<true, false>(c, a, out);
-        return;
-    }
-    const int nb = std::max(1, a.nb_p + (a.m ? blocks_for(a.n3) : 0));
-    if (c->stop_dev) {
-        if (c->mon_mode >= 2) hipLaunchKernelGGL((k_monitor<true, true, false, true>), dim3(nb), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((k_monitor<true, false, false, true>), dim3(nb), dim3(256), 0, c->stream, a);
+    const int sd = decide ? s : -1;
+    if (decide && c->stop_dev) {
+        if (c->mon_mode >= 2) launch_monitor<true, true, true>(c, a, out, sd);
+        else launch_monitor<true, false, true>(c, a, out, sd);
     } else {
-        if (c->mon_mode >= 2) hipLaunchKernelGGL((k_monitor<true, true, false>), dim3(nb), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((k_monitor<true, false, false>), dim3(nb), dim3(256), 0, c->stream, a);
+        if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, out, sd);
+        else launch_monitor<true, false>(c, a, out, sd);
     }
-    hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig);
 }
 
 // ---- internal forces, stress, stationarity (forces.hpp) ----
@@ -616,27 +619,34 @@ hipError_t force_ensure(admm_hip_ctx *c, bool stress, int stat_records) {
     }
     return hipSuccess;
 }
+// the scene and the chunk plan at positions x; rec, r_cf, h_cf: where the pass leaves the records and corner forces
+ForceArgs force_args(const admm_hip_ctx *c, const double *x, double *rec, double *r_cf, double *h_cf) {
+    ForceArgs a{};
+    a.v = elem_view(c, x);
+    for (int i = 0; i < 6; ++i) a.cb[i] = c->chunk_base[i];
+    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = rec; a.r_cf = r_cf; a.h_cf = h_cf;
+    a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
+    return a;
+}
+// the incidence lists of the three families (those of k_gather_rhs) over the records and corner forces a force_args pass left; out [nv][3]
+ForceGatherArgs force_gather_args(const admm_hip_ctx *c, const ForceArgs &a, double *out) {
+    ForceGatherArgs g{};
+    g.nv = c->nv; g.n_slices = (c->nv + 63) / 64;
+    if (c->nt > 0) { g.t_ptr = c->t_inc.ptr.p; g.t_w = c->t_inc.w.p; g.t_inc = c->t_inc.idx.p; g.t_rec = a.rec; }
+    if (c->ntri > 0) { g.r_ptr = c->r_inc.ptr.p; g.r_w = c->r_inc.w.p; g.r_inc = c->r_inc.idx.p; g.r_cf = a.r_cf; g.r_ld = c->ldr; }
+    if (c->nbend > 0) { g.h_ptr = c->h_inc.ptr.p; g.h_w = c->h_inc.w.p; g.h_inc = c->h_inc.idx.p; g.h_cf = a.h_cf; g.h_ld = c->ldb; }
+    g.order = c->g_order.p; g.f = out;
+    return g;
+}
 // f_out = -dE/dx at positions x (device); stress: also the per-tet stress into f_stress; stop: the stop word or nullptr
 void launch_forces(admm_hip_ctx *c, const double *x, bool stress, const int *stop) {
-    ForceArgs a{};
-    a.x = x; a.dt2 = c->dt * c->dt;
-    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
-    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
-    for (int i = 0; i < 6; ++i) { a.kb[i] = c->kind_begin[i]; a.cb[i] = c->chunk_base[i]; }
-    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = c->f_rec.p;
+    ForceArgs a = force_args(c, x, c->f_rec.p, c->f_rcf.p, c->f_hcf.p);
     a.stress = stress ? c->f_stress.p : nullptr;
-    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_cf = c->f_rcf.p;
-    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_k = c->h_kst.p; a.h_cf = c->f_hcf.p;
-    a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
     a.stop = stop;
     const int nb = a.nb_r + blocks_for(c->nbend);
     if (nb > 0) hipLaunchKernelGGL(k_forces, dim3(nb), dim3(256), 0, c->stream, a);
-    ForceGatherArgs g{};
-    g.nv = c->nv; g.n_slices = (c->nv + 63) / 64;
-    if (c->nt > 0) { g.t_ptr = c->t_inc.ptr.p; g.t_w = c->t_inc.w.p; g.t_inc = c->t_inc.idx.p; g.t_rec = c->f_rec.p; }
-    if (c->ntri > 0) { g.r_ptr = c->r_inc.ptr.p; g.r_w = c->r_inc.w.p; g.r_inc = c->r_inc.idx.p; g.r_cf = c->f_rcf.p; g.r_ld = c->ldr; }
-    if (c->nbend > 0) { g.h_ptr = c->h_inc.ptr.p; g.h_w = c->h_inc.w.p; g.h_inc = c->h_inc.idx.p; g.h_cf = c->f_hcf.p; g.h_ld = c->ldb; }
-    g.order = c->g_order.p; g.f = c->f_out.p; g.stop = stop;
+    ForceGatherArgs g = force_gather_args(c, a, c->f_out.p);
+    g.stop = stop;
     hipLaunchKernelGGL(k_gather_forces, dim3(std::max(1, (g.n_slices + 3) / 4)), dim3(256), 0, c->stream, g);
 }
 // ---- tangent stiffness (tangent.hpp) ----
@@ -661,32 +671,19 @@ hipError_t tangent_ensure(admm_hip_ctx *c, int n_vec) {
 // k_out[j] = K(x) k_d[j] + shift m o k_d[j], j < n_vec, at positions x (device)
 void launch_tangent(admm_hip_ctx *c, const double *x, int n_vec, double shift) {
     TangentArgs t{};
-    ForceArgs &a = t.f;
-    a.x = x; a.dt2 = c->dt * c->dt;
-    a.nt = c->nt; a.ldt = c->ldt; a.t_idx = c->t_idx.p; a.t_Binv = c->t_Binv.p; a.t_x0 = c->tet_rest_mode ? c->t_x0.p : nullptr; a.t_sc = c->t_sc.p;
-    a.t_mat = c->t_mat.p; a.mats = c->mats.p; a.spl = c->spl_tab.p;
-    for (int i = 0; i < 6; ++i) { a.kb[i] = c->kind_begin[i]; a.cb[i] = c->chunk_base[i]; }
-    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = c->k_rec.p;
-    a.ntri = c->ntri; a.ldr = c->ldr; a.r_idx = c->r_idx.p; a.r_rest = c->r_rest.p; a.r_sc = c->r_sc.p; a.r_cf = c->k_rcf.p;
-    a.nbend = c->nbend; a.ldb = c->ldb; a.h_idx = c->h_idx.p; a.h_coef = c->h_coef.p; a.h_k = c->h_kst.p; a.h_cf = c->k_hcf.p;
-    a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
+    t.f = force_args(c, x, c->k_rec.p, c->k_rcf.p, c->k_hcf.p);
     t.d = c->k_d.p; t.n_vec = n_vec;
     t.d_stride = (size_t)c->n3; t.rec_stride = (size_t)4 * (c->n_rec + 1); t.rcf_stride = (size_t)12 * c->ldr; t.hcf_stride = (size_t)12 * c->ldb;
-    const int nb = a.nb_r + blocks_for(c->nbend);
+    const int nb = t.f.nb_r + blocks_for(c->nbend);
     if (nb > 0) {
         if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent<true>, dim3(nb), dim3(256), 0, c->stream, t);
         else hipLaunchKernelGGL(k_tangent<false>, dim3(nb), dim3(256), 0, c->stream, t);
     }
     TangentGatherArgs q{};
-    ForceGatherArgs &g = q.g;
-    g.nv = c->nv; g.n_slices = (c->nv + 63) / 64;
-    if (c->nt > 0) { g.t_ptr = c->t_inc.ptr.p; g.t_w = c->t_inc.w.p; g.t_inc = c->t_inc.idx.p; g.t_rec = c->k_rec.p; }
-    if (c->ntri > 0) { g.r_ptr = c->r_inc.ptr.p; g.r_w = c->r_inc.w.p; g.r_inc = c->r_inc.idx.p; g.r_cf = c->k_rcf.p; g.r_ld = c->ldr; }
-    if (c->nbend > 0) { g.h_ptr = c->h_inc.ptr.p; g.h_w = c->h_inc.w.p; g.h_inc = c->h_inc.idx.p; g.h_cf = c->k_hcf.p; g.h_ld = c->ldb; }
-    g.order = c->g_order.p; g.f = c->k_out.p;
+    q.g = force_gather_args(c, t.f, c->k_out.p);
     q.d = c->k_d.p; q.m = c->m.p; q.shift = shift;
     q.d_stride = t.d_stride; q.rec_stride = t.rec_stride; q.rcf_stride = t.rcf_stride; q.hcf_stride = t.hcf_stride;
-    hipLaunchKernelGGL(k_gather_tangent, dim3(std::max(1, (g.n_slices + 3) / 4), n_vec), dim3(256), 0, c->stream, q);
+    hipLaunchKernelGGL(k_gather_tangent, dim3(std::max(1, (q.g.n_slices + 3) / 4), n_vec), dim3(256), 0, c->stream, q);
 }
 
 // monitor mode 3, record s of the running step: the stationarity sum at x = curr into f_stat[s].  Launched BEFORE the record's decision
@@ -3629,17 +3626,26 @@ static int mon_refuse(const admm_hip_ctx *c, const char *who) {
     return ADMM_HIP_OK;
 }
 
+// The common entry of energy, forces / stress and stiffness_apply: refuses what mon_refuse refuses and a call without positions, waits for
+// the stream, settles and uploads x.  *xd = the positions on the device: the device-resident state, or curr when x is given (curr is scratch
+// between steps).
+static int eval_begin(admm_hip_ctx *c, const char *who, const double *x, const double **xd) {
+    if (int rc = mon_refuse(c, who)) return rc;
+    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, std::string(who) + ": no device-resident state yet (admm_hip_set_state), and x is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = settle(c)) return rc;
+    *xd = c->x.p;
+    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, c->stream)); *xd = c->curr.p; }
+    return ADMM_HIP_OK;
+}
+
 int admm_hip_energy(admm_hip_ctx *c, const double *x, double *totals4, double *per_term) {
     if (!c || !totals4) return fail(ADMM_HIP_ERR_ARG, "energy: NULL argument");
-    if (int rc = mon_refuse(c, "energy")) return rc;
-    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, "energy: no device-resident state yet (admm_hip_set_state), and x is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = settle(c)) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, "energy", x, &xd)) return rc;
     HIP_TRY(mon_ensure(c, false, per_term != nullptr));
-    const double *xd = c->x.p;
-    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    hipStream_t st = c->stream;
     MonArgs a = mon_args(c, xd, false);
     a.term = per_term ? c->mon_term.p : nullptr;
     launch_monitor<false, true>(c, a, c->mon_out.p);
@@ -3664,15 +3670,10 @@ int admm_hip_energy(admm_hip_ctx *c, const double *x, double *totals4, double *p
 // f = -dE/dx and / or the per-tet stress at x (host, or NULL = the device-resident state): one force pass (forces.hpp)
 static int forces_impl(admm_hip_ctx *c, const char *who, const double *x, double *f, double *out13) {
     if (!c || (!f && !out13)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": NULL argument");
-    if (int rc = mon_refuse(c, who)) return rc;
-    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, std::string(who) + ": no device-resident state yet (admm_hip_set_state), and x is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = settle(c)) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, who, x, &xd)) return rc;
     HIP_TRY(force_ensure(c, out13 != nullptr, 0));
-    const double *xd = c->x.p;
-    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    hipStream_t st = c->stream;
     launch_forces(c, xd, out13 != nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     std::vector<double> sd(out13 && c->nt ? (size_t)kStressQ * c->ldt : 0);      // (a scene without tets has no stress)
@@ -3690,15 +3691,10 @@ int admm_hip_stress(admm_hip_ctx *c, const double *x, double *out13) { return fo
 // out_j = K(x) d_j + shift (m o d_j), K = d2E/dx2 at x (host, or NULL = the device-resident state): one tangent pass (tangent.hpp)
 int admm_hip_stiffness_apply(admm_hip_ctx *c, const double *x, int32_t n_vec, const double *d, double shift, double *out) {
     if (!c || !d || !out || n_vec < 1 || n_vec > 65535) return fail(ADMM_HIP_ERR_ARG, "stiffness_apply: NULL argument, n_vec < 1 or n_vec > 65535");
-    if (int rc = mon_refuse(c, "stiffness_apply")) return rc;
-    if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, "stiffness_apply: no device-resident state yet (admm_hip_set_state), and x is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = settle(c)) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, "stiffness_apply", x, &xd)) return rc;
     HIP_TRY(tangent_ensure(c, n_vec));
-    const double *xd = c->x.p;
-    if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, st)); xd = c->curr.p; }   // (curr is scratch between steps)
+    hipStream_t st = c->stream;
     const size_t n = (size_t)n_vec * c->n3;
     if (n) HIP_TRY(hipMemcpyAsync(c->k_d.p, d, n * sizeof(double), hipMemcpyHostToDevice, st));
     launch_tangent(c, xd, n_vec, shift);

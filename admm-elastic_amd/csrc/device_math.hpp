@@ -866,9 +866,15 @@ struct StableNHModel {
         return f;
     }
 };
+// mu_s, la_s, alpha of the model from the tet's Lame constants (the formulas above)
+__device__ __forceinline__ void stable_nh_params(double mu, double la, double &mus, double &las, double &alpha) {
+    mus = (4.0 / 3.0) * mu; las = la + (5.0 / 6.0) * mu; alpha = 1.0 + 0.75 * mus / las;
+}
 // HyperElasticTet::prox on the stretches (src/TetEnergyTerm.cpp:124-135) for the stable Neo-Hookean model; mu, la = the tet's Lame constants
 __device__ __forceinline__ void prox_stretches_stable_nh(double mu, double la, double k, double *S) {
     StableNHModel m;
+    // (stable_nh_params restated: a call moves alpha in front of the two products below, and the local step's instances, which sit on
+    // spilled registers, came out with another schedule)
     const double ik = fast_rcp(k), mus = (4.0 / 3.0) * mu, las = la + (5.0 / 6.0) * mu;
     m.type = 0; m.mu = mus * ik; m.la = las * ik; m.k = 1.0; m.alpha = 1.0 + 0.75 * mus / las;
     m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];       // :124 set_x0 (before the fix-ups)
@@ -1024,6 +1030,50 @@ __device__ __attribute__((noinline)) inline void tet_tangent_table(const double 
         be[q] = (g[i] + g[j]) / (A[i] + A[j]);
     }
 }
+// EnergyTerm::energy of a tet, as a density: psi at the signed stretches S of its model (the return value; the energy is psi vol) and
+// sg[i] = s_i dpsi/da_i, the diagonal of P = dpsi/dF in the frame of the signed SVD.  THE dispatch from (grp, type) to a model, for value
+// and gradient at once -- both come out of the same eval, a caller that needs one discards the other.  The densities are the stretch
+// models' own eval with the prox's quadratic switched off (k = 0); the signs follow the reference: the linear tet takes a = |sigma|
+// (src/TetEnergyTerm.cpp:94-100), Neo-Hookean and every SplineTet flip a negative smallest stretch (:138-149) -- there s_i = sign(sigma_i),
+// and at sigma_i = 0 the gradient is one-sided (sign(0) counts as +); StVK is even in the stretches and stable Neo-Hookean keeps the sign
+// (its point): a = sigma, s_i = 1.  grp, type, k, kappa: kernels.hpp: Mat; tab: the tabulated spline's table (read by grp 4, type 3 only).
+__device__ __forceinline__ double tet_energy_grad(int grp, int type, double mu, double la, double k, double kappa, const double *tab,
+                                                  const double *S, double *sg) {
+    const double A[3] = {fabs(S[0]), fabs(S[1]), fabs(S[2])};
+    double g[3], D[3], w[3], H[6], psi;
+    bool use_abs = true;
+    if (grp == 0) {
+        psi = 0.5 * k * ((A[0] - 1.0) * (A[0] - 1.0) + (A[1] - 1.0) * (A[1] - 1.0) + (A[2] - 1.0) * (A[2] - 1.0));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) g[i] = k * (A[i] - 1.0);
+    } else if (grp == 1) {
+        StretchModel<1, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+        psi = m.eval(A, g, D, w);
+    } else if (grp == 2) {
+        StretchModel<2, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
+        psi = m.eval(S, g, D, w);
+        use_abs = false;
+    } else if (grp == 3) {
+        StretchModel<3, double> m; m.mu = mu; m.la = la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+        psi = m.eval(A, g, D, w);
+    } else if (type == 3) {
+        SplineTableModel m; m.type = 1; m.tab = tab; m.mu = 0.0; m.la = 0.0; m.k = 0.0; m.lo = 0.0;
+        m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+        psi = m.eval(A, g, H);
+    } else if (type == 4) {
+        StableNHModel m; m.type = 0; m.k = 0.0;
+        stable_nh_params(mu, la, m.mu, m.la, m.alpha);
+        m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
+        psi = m.eval(S, g, H);
+        use_abs = false;
+    } else {
+        SplineKappaModel m; m.type = type; m.mu = mu; m.la = la; m.k = 0.0; m.kappa = kappa; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
+        psi = m.eval(A, g, H);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) sg[i] = (use_abs && S[i] < 0.0) ? -g[i] : g[i];
+    return psi;
+}
 // Hs = {h00, h01, h02, h11, h12, h22}, al and be for the pairs (0,1), (0,2), (1,2), all in the frame of the signed SVD.
 // grp: the tet's model group (0 linear, 1 Neo-Hookean, 2 StVK, 3 co-rotated, 4 the dense-Hessian models by `type`, kernels.hpp: Mat)
 // TABLE = false: for callers that hold no tabulated spline (type 3 cannot occur) -- the table path and its registers are compiled out
@@ -1060,7 +1110,8 @@ __device__ __forceinline__ void tet_tangent_coef(int grp, int type, double mu, d
                 be[q] = fma(mu, ss - sij, c);
             }
         } else {
-            StableNHModel m; m.type = 0; m.mu = (4.0 / 3.0) * mu; m.la = la + (5.0 / 6.0) * mu; m.k = 0.0; m.alpha = 1.0 + 0.75 * m.mu / m.la;
+            StableNHModel m; m.type = 0; m.k = 0.0;
+            stable_nh_params(mu, la, m.mu, m.la, m.alpha);
             m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
             (void)m.eval(S, g, Hs);
             const double IC = fma(S[0], S[0], fma(S[1], S[1], S[2] * S[2])), a1 = m.mu * (1.0 - 1.0 / (IC + 1.0));

@@ -6,15 +6,13 @@
 // HyperElasticTet::gradient exists in stretch space only), so like the energies of the f3 terms this has no reference code: it is pinned on
 // the energies (tests/test_forces.py: the numpy forces are the gradient of the numpy energies, the device forces equal the numpy forces).
 //
-// k_forces walks the families in block ranges like k_monitor:
-//   tets      one block per 256-tet CHUNK of the local step's plan (host_setup.hpp: TetChunks; chunks are numbered model by model and do
-//             not straddle a model boundary), lane = tet.  F = D_i x = U diag(sigma) V^T (signed_svd3), g = dpsi/da from the kind's own
-//             eval with the prox quadratic off (k = 0), a = |sigma| for the kinds whose energy is evaluated there (linear, Neo-Hookean,
-//             every SplineTet) and a = sigma for StVK and stable Neo-Hookean; P = U diag(s_i g_i) V^T with s_i = sign(sigma_i) resp. 1;
-//             corner forces H = -vol P Binv^T (corner m + 1: column m, corner 0: minus their sum), reduced per chunk into 32-byte records
-//             exactly as tet_compute_store does.  No density is restated here.
+// k_forces walks the families in block ranges like k_monitor and reads the elements through elements.hpp:
+//   tets      one block per 256-tet CHUNK of the local step's plan (host_setup.hpp: TetChunks), lane = tet.  F = D_i x = U diag(sigma) V^T
+//             (signed_svd3), P = U diag(s_i g_i) V^T with s_i g_i from the kind's own eval (device_math.hpp: tet_energy_grad -- the
+//             dispatch the energy uses, so the two cannot differ); corner forces H = -vol P Binv^T (corner m + 1: column m, corner 0: minus
+//             their sum), reduced per chunk into 32-byte records the way the local step reduces its own.  No density is restated here.
 //   triangles lane = triangle: E = w^2 / 2 sum (sigma_i - 1)^2 of the 3x2 F, P = w^2 (F - R), R = F (F^T F)^(-1/2) the closest isometry
-//             (closed-form 2x2 inverse square root), corner forces through `rest` as k_local_tris forms them.
+//             (closed-form 2x2 inverse square root), corner forces through `rest`.
 //   hinges    f_{v_k} = -stiffness c_k (D_i x).
 // k_gather_forces (lane = vertex) sums records and corner forces through the incidence lists of k_gather_rhs, in list order.
 //
@@ -32,116 +30,42 @@ namespace admm_k {
 constexpr int kStressQ = 13;      // per tet: P column-major (9), the signed stretches (3), von Mises of the Cauchy stress (1)
 
 struct ForceArgs {
-    const double *x;          // [nv][3]
-    double dt2;               // sc = dt^2 w^2  ->  w^2 = sc / dt2
-    // tets in device order (sorted by model group); kb = the groups' first tets, cb = their first chunks
-    int nt, ldt; const int4 *t_idx; const double *t_Binv, *t_x0, *t_sc; const int *t_mat; const Mat *mats; const double *spl;
-    int kb[6], cb[6];
+    ElemView v;               // the scene at x
+    int cb[6];                // the model groups' first chunks (v.kb: their first tets)
     const unsigned short *ch_ent; const int *ch_group, *ch_rec; double *rec;      // the local step's chunk plan; records [n_rec + 1][4]
     double *stress;           // [kStressQ][ldt] in device order, or nullptr
-    int ntri, ldr; const int4 *r_idx; const double *r_rest, *r_sc; double *r_cf;   // corner forces [9 of 12][ldr]
-    int nbend, ldb; const int4 *h_idx; const double *h_coef, *h_k; double *h_cf;   // [12][ldb]
+    double *r_cf;             // corner forces of the triangles [9 of 12][ldr]
+    double *h_cf;             // of the hinges [12][ldb]
     int nb_t, nb_r;           // block ranges: [0, nb_t) tet chunks, [nb_t, nb_r) triangles, then hinges
     const int *stop;          // the stop word of the ADMM loop (kernels.hpp: kCntAdmmStop) or nullptr: set, the launch is a no-op
 };
 
-// psi's gradient g[i] = dpsi/da_i of tet t's model at the stretches S, a = |S| or S as its energy takes them (mon_tet_energy), and
-// sg[i] = s_i g_i, the diagonal of P in the frame of the SVD
-__device__ __forceinline__ void force_tet_grad(const Mat mt, int grp, const double *spl, const double *S, double *sg) {
-    const double A[3] = {fabs(S[0]), fabs(S[1]), fabs(S[2])};
-    double g[3], D[3], w[3], H[6];
-    bool use_abs = true;
-    if (grp == 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) g[i] = mt.k * (A[i] - 1.0);
-    } else if (grp == 1) {
-        StretchModel<1, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        (void)m.eval(A, g, D, w);
-    } else if (grp == 2) {
-        StretchModel<2, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
-        (void)m.eval(S, g, D, w);
-        use_abs = false;
-    } else if (grp == 3) {
-        StretchModel<3, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        (void)m.eval(A, g, D, w);
-    } else if (mt.type == 3) {
-        SplineTableModel m; m.type = 1; m.tab = spl + (size_t)mt.table * kSplineTableDoubles; m.mu = 0.0; m.la = 0.0; m.k = 0.0; m.lo = 0.0;
-        m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        (void)m.eval(A, g, H);
-    } else if (mt.type == 4) {
-        StableNHModel m; m.type = 0; m.mu = (4.0 / 3.0) * mt.mu; m.la = mt.la + (5.0 / 6.0) * mt.mu; m.k = 0.0; m.alpha = 1.0 + 0.75 * m.mu / m.la;
-        m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
-        (void)m.eval(S, g, H);
-        use_abs = false;
-    } else {
-        SplineKappaModel m; m.type = mt.type; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.kappa = mt.kappa; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        (void)m.eval(A, g, H);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) sg[i] = (use_abs && S[i] < 0.0) ? -g[i] : g[i];
-}
-
-// One chunk of tets.  The whole block takes part (signed_svd3 takes wave votes, the chunk's reduction synchronises the block): lanes
-// past the end of the model's range redo its last tet and park values no list refers to.
+// One chunk of tets; the whole block takes part (elements.hpp: chunk_locate).
 __device__ __forceinline__ void force_tets(const ForceArgs &a, int chunk, LdsDk *sL) {
+    const ElemView &v = a.v;
     const int tid = (int)threadIdx.x;
-    const int grp = (chunk >= a.cb[1]) + (chunk >= a.cb[2]) + (chunk >= a.cb[3]) + (chunk >= a.cb[4]);
-    const int c0 = grp == 0 ? a.cb[0] : grp == 1 ? a.cb[1] : grp == 2 ? a.cb[2] : grp == 3 ? a.cb[3] : a.cb[4];
-    const int tb = grp == 0 ? a.kb[0] : grp == 1 ? a.kb[1] : grp == 2 ? a.kb[2] : grp == 3 ? a.kb[3] : a.kb[4];
-    const int t_end = grp == 0 ? a.kb[1] : grp == 1 ? a.kb[2] : grp == 2 ? a.kb[3] : grp == 3 ? a.kb[4] : a.kb[5];
-    const int t0 = tb + (chunk - c0) * 256 + tid;
-    const bool valid = t0 < t_end;
-    const int t = valid ? t0 : t_end - 1;
+    const ChunkLane ln = chunk_locate(v.kb, a.cb, chunk, tid);
+    const int t = ln.t;
     LdsDk *sBi = sL + tid;                                   // row c of this thread: [c * kChunkLdK]
     if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;            // the padding column of the reduction lists
     // the reduction list of this thread's record (first pass) and the tet's scalars: in flight across the SVD
     const int g0 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk]), g1 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk + 1]);
     const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk + 1]) - r0;
     const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
-    union { bv4u v; unsigned short h[8]; } e;
-    e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
-    const double w2 = a.t_sc[t] / a.dt2;
-    const Mat mt = a.mats[a.t_mat[t]];
+    const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+    const double w2 = v.t_sc[t] / v.dt2;
+    const Mat mt = v.mats[v.t_mat[t]];
     double U[9], S[3], V[9], F[9];
     {
-        const int4 id = a.t_idx[t];
-        const int vid[4] = {id.x, id.y, id.z, id.w};
         double Bi[9];
-        if (a.t_x0) {      // Binv from the rest positions, as the local step recomputes it (kernels.hpp: tet_rest_binv)
-            double p[12];
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) p[3 * v + j] = a.t_x0[3 * (size_t)vid[v] + j];
-            double e0[3], e1[3], e2[3], q0[3], q1[3], q2[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { e0[j] = p[3 + j] - p[j]; e1[j] = p[6 + j] - p[j]; e2[j] = p[9 + j] - p[j]; }
-            cross3(e1, e2, q0); cross3(e2, e0, q1); cross3(e0, e1, q2);
-            const double idet = fast_rcp(fma(e0[0], q0[0], fma(e0[1], q0[1], e0[2] * q0[2])));
-#pragma unroll
-            for (int r = 0; r < 3; ++r) { Bi[r * 3 + 0] = q0[r] * idet; Bi[r * 3 + 1] = q1[r] * idet; Bi[r * 3 + 2] = q2[r] * idet; }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 9; ++c) Bi[c] = a.t_Binv[(size_t)c * a.ldt + t];
-        }
-        double x[12], Ds[9];
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) x[3 * v + j] = a.x[3 * (size_t)vid[v] + j];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) F[r * 3 + j] = fma(Ds[j], Bi[r * 3 + 0], fma(Ds[3 + j], Bi[r * 3 + 1], Ds[6 + j] * Bi[r * 3 + 2]));
-        // Binv is needed again for the corner forces: parked in this thread's LDS column across the SVD, as the local step does
+        tet_F_binv(v, v.t_idx[t], t, F, Bi);
+        // Binv is needed again for the corner forces: parked in this thread's LDS column across the SVD
 #pragma unroll
         for (int c = 0; c < 9; ++c) sBi[c * kChunkLdK] = Bi[c];
     }
     signed_svd3(F, U, S, V);
     double sg[3];
-    force_tet_grad(mt, grp, a.spl, S, sg);
+    (void)tet_energy_grad(ln.grp, mt.type, mt.mu, mt.la, mt.k, mt.kappa, v.spl + (size_t)(ln.grp == 4 && mt.type == 3 ? mt.table : 0) * kSplineTableDoubles, S, sg);
     const double vol = w2 / mt.k;      // w = sqrt(k vol), src/TetEnergyTerm.cpp:46-47
     if (a.stress) {
         double P[9];
@@ -149,75 +73,41 @@ __device__ __forceinline__ void force_tets(const ForceArgs &a, int chunk, LdsDk 
         const double J = S[0] * S[1] * S[2];
         const double tau[3] = {sg[0] * S[0] / J, sg[1] * S[1] / J, sg[2] * S[2] / J};      // Cauchy = P F^T / J = U diag(tau) U^T
         const double d0 = tau[0] - tau[1], d1 = tau[1] - tau[2], d2 = tau[2] - tau[0];
-        if (valid) {
+        if (ln.valid) {
 #pragma unroll
-            for (int c = 0; c < 9; ++c) a.stress[(size_t)c * a.ldt + t] = P[c];
+            for (int c = 0; c < 9; ++c) a.stress[(size_t)c * v.ldt + t] = P[c];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) a.stress[(size_t)(9 + i) * a.ldt + t] = S[i];
-            a.stress[(size_t)12 * a.ldt + t] = sqrt(0.5 * (d0 * d0 + d1 * d1 + d2 * d2));
+            for (int i = 0; i < 3; ++i) a.stress[(size_t)(9 + i) * v.ldt + t] = S[i];
+            a.stress[(size_t)12 * v.ldt + t] = sqrt(0.5 * (d0 * d0 + d1 * d1 + d2 * d2));
         }
     }
-    double G[9];
+    double G[9], f[12];
     {
         const double dg[3] = {-vol * sg[0], -vol * sg[1], -vol * sg[2]};
         usvt(U, dg, V, G);
     }
-    // corner forces: H(j,m) = sum_r G(j,r) Binv(m,r); corner m+1 gets H(:,m), corner 0 gets -sum_m H(:,m)  (as tet_compute_store)
-    double f[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        const double b0 = sBi[(0 + m) * kChunkLdK], b1 = sBi[(3 + m) * kChunkLdK], b2 = sBi[(6 + m) * kChunkLdK];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double h = fma(G[j], b0, fma(G[3 + j], b1, G[6 + j] * b2));
-            f[3 * (m + 1) + j] = h;
-            f[j] -= h;
-        }
-    }
-    // the chunk's reduction: thread j of pass p sums the <= 8 corner forces of record 256 p + j and stores it as one 32-byte sector
+    tet_corner_forces(G, sBi, f);
 #pragma unroll
     for (int c = 0; c < 12; ++c) sBi[c * kChunkLdK] = f[c];
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rr = soa_rsrc(a.rec);
-    for (int g = g0; g < g1; ++g) {
-        if (g > g0) e.v = __builtin_amdgcn_raw_buffer_load_b128(re, (g * 256 + tid) * 16, 0, kStreamLdAux);
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int i = 0; i < kChunkFanK; ++i) {
-            const LdsDk *q = (const LdsDk *)((const __attribute__((address_space(3))) char *)sL + e.h[i]);
-            s0 += q[0]; s1 += q[kChunkLdK]; s2 += q[2 * kChunkLdK];
-        }
-        const int j = (g - g0) * 256 + tid;
-        if (j < nrec) {
-            union { double d[2]; bv4u v; } p0; p0.d[0] = s0; p0.d[1] = s1;
-            union { double d; bv2u v; } p1; p1.d = s2;
-            __builtin_amdgcn_raw_buffer_store_b128(p0.v, rr, (r0 + j) * 32, 0, kStreamStAux);
-            __builtin_amdgcn_raw_buffer_store_b64(p1.v, rr, (r0 + j) * 32 + 16, 0, kStreamStAux);
-        }
-    }
+    chunk_reduce_store(sL, re, e0, g0, g1, r0, nrec, a.rec);
 }
 
 __global__ __launch_bounds__(256) void k_forces(ForceArgs a) {
     __shared__ double sLm[12 * kChunkLdK];      // rows 0..8: Binv across the SVD; rows 0..11: the chunk's corner forces
     if (a.stop && *a.stop) return;
+    const ElemView &v = a.v;
     const int blk = xcd_block(), tid = (int)threadIdx.x;
     if (blk < a.nb_t) {
         force_tets(a, blk, (LdsDk *)sLm);
     } else if (blk < a.nb_r) {
         const int t = (blk - a.nb_t) * 256 + tid;
-        if (t >= a.ntri) return;
-        const int4 id = a.r_idx[t];
+        if (t >= v.ntri) return;
         double R[4], F[6];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) R[c] = a.r_rest[(size_t)c * a.ldr + t];
-        const double *p0 = a.x + 3 * (size_t)id.x, *p1 = a.x + 3 * (size_t)id.y, *p2 = a.x + 3 * (size_t)id.z;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {      // F (3x2) = [x1 - x0, x2 - x0] rest, as k_local_tris
-            const double b = p0[j], e1 = p1[j] - b, e2 = p2[j] - b;
-            F[j] = fma(e1, R[0], e2 * R[1]);
-            F[3 + j] = fma(e1, R[2], e2 * R[3]);
-        }
-        const double w2 = a.r_sc[t] / a.dt2;
+        for (int c = 0; c < 4; ++c) R[c] = v.r_rest[(size_t)c * v.ldr + t];
+        tri_F(R, v.r_idx[t], v.x, F);
+        const double w2 = v.r_sc[t] / v.dt2;
         // C = F^T F; sqrt(C) = (C + s I) / q with s = sqrt(det C) = sigma_1 sigma_2, q = sqrt(tr C + 2 s) = sigma_1 + sigma_2;
         // C^(-1/2) = adj(C + s I) / (q s); the closest isometry Q = F C^(-1/2)
         const double c00 = dot3(F, F), c01 = dot3(F, F + 3), c11 = dot3(F + 3, F + 3);
@@ -228,31 +118,22 @@ __global__ __launch_bounds__(256) void k_forces(ForceArgs a) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const double q0 = fma(F[j], i00, F[3 + j] * i01), q1 = fma(F[j], i01, F[3 + j] * i11);
-            const double G0 = -w2 * (F[j] - q0), G1 = -w2 * (F[3 + j] - q1);      // G = -P
-            const double h1 = fma(G0, R[0], G1 * R[2]);
-            const double h2 = fma(G0, R[1], G1 * R[3]);
-            a.r_cf[(size_t)(0 + j) * a.ldr + t] = -(h1 + h2);
-            a.r_cf[(size_t)(3 + j) * a.ldr + t] = h1;
-            a.r_cf[(size_t)(6 + j) * a.ldr + t] = h2;
+            tri_corner_store(-w2 * (F[j] - q0), -w2 * (F[3 + j] - q1), R, a.r_cf + (size_t)j * v.ldr, v.ldr, t);      // G = -P
         }
     } else {
         const int t = (blk - a.nb_r) * 256 + tid;
-        if (t >= a.nbend) return;
-        const int4 id = a.h_idx[t];
+        if (t >= v.nbend) return;
+        const int4 id = v.h_idx[t];
         const int vid[4] = {id.x, id.y, id.z, id.w};
-        double c[4], Dx[3] = {0.0, 0.0, 0.0};
+        double c[4], Dx[3];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {      // D_i x = sum_k c_k x_{v_k}, as k_local_bends
-            c[k] = a.h_coef[(size_t)k * a.ldb + t];
-            const double *p = a.x + 3 * (size_t)vid[k];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Dx[j] = fma(c[k], p[j], Dx[j]);
-        }
-        const double ks = -a.h_k[t];
+        for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
+        hinge_Dx(c, vid, v.x, Dx);
+        const double ks = -v.h_k[t];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * a.ldb + t] = c[k] * (ks * Dx[j]);
+            for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * v.ldb + t] = c[k] * (ks * Dx[j]);
     }
 }
 

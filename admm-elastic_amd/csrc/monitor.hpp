@@ -3,8 +3,8 @@
 // What the library could not say before: how large the elastic energy is (EnergyTerm::energy, src/EnergyTerm.hpp:82,142-147;
 // src/TetEnergyTerm.cpp:94-100,138-149; src/TriEnergyTerm.cpp:104-114) and how far an ADMM iteration is from its fixed point.  One
 // kernel walks the families -- tets, triangles, bending hinges, pin terms, and (objective) the nodes -- in block ranges like
-// k_local_tets_fused; a lane owns one element and reads what the local step reads (idx, Binv or the rest positions, sc = dt^2 w^2,
-// mats, the spline tables) plus z and z_prev.  Per block and quantity one partial; k_mon_final sums the partials.
+// k_local_tets_fused; a lane owns one element and reads it through elements.hpp (idx, Binv or the rest positions, sc = dt^2 w^2, mats,
+// the spline tables) plus z and z_prev.  Per block and quantity one partial; k_mon_final sums the partials.
 //
 // Quantities (kMonQ = 8 per block partial and per record):
 //   0  sum w_i^2 |D_i x - z_i|^2        2  sum w_i^2 |z_i|^2          4  energy of the tets       6  energy of the hinges
@@ -18,7 +18,7 @@
 // z_prev is kept by WRITE-BACK: the residual pass stores z into z_prev after it has used both (INIT: stores D x, the reference's
 // curr_z = D m_x of src/Solver.cpp:70).  The local step and its buffers stay as they are.
 #pragma once
-#include "kernels.hpp"
+#include "elements.hpp"
 
 namespace admm_k {
 
@@ -38,16 +38,10 @@ __host__ __device__ inline bool admm_stop_test(const double *rec, double tol) {
 }
 
 struct MonArgs {
-    const double *x;          // [nv][3] positions D is applied to
-    double dt2;               // sc = dt^2 w^2  ->  w^2 = sc / dt2
-    // tets (device order: sorted by model group, kb = the groups' starts, admm_hip_ctx::kind_begin)
-    int nt, ldt; const int4 *t_idx; const double *t_Binv, *t_x0, *t_sc; const int *t_mat; const Mat *mats; const double *spl;
-    int kb[6];
+    ElemView v;               // the scene at x
     const double *t_z; double *t_zp;
-    // triangles
-    int ntri, ldr; const int4 *r_idx; const double *r_rest, *r_sc, *r_z; double *r_zp;
-    // bending hinges
-    int nbend, ldb; const int4 *h_idx; const double *h_coef, *h_sc, *h_k, *h_z; double *h_zp;
+    const double *r_z; double *r_zp;
+    const double *h_sc, *h_z; double *h_zp;
     // pin terms: pin_dim rows per pin (3: the rows the device keeps; 6: the reference's row layout, rows 3..5 of D are empty)
     int npin, pin_dim; const int *pin_vert; const double *pin_z; double *pin_zp; double pin_w2;
     // nodes (inertia term of the objective); m == nullptr: none
@@ -64,76 +58,14 @@ __device__ __forceinline__ void mon_row(double dx, double z, double zp, double *
     r[0] = fma(a, a, r[0]); r[1] = fma(b, b, r[1]); r[2] = fma(z, z, r[2]); r[3] = fma(dx, dx, r[3]);
 }
 
-// F = D_i x of tet t (column-major, rows 3 r + j of the term), with Binv streamed or recomputed from the rest positions exactly as
-// the local step does (kernels.hpp: tet_rest_binv, tet_compute_store)
-__device__ __forceinline__ void mon_tet_F(const MonArgs &a, int t, double *F) {
-    const int4 id = a.t_idx[t];
-    const int vid[4] = {id.x, id.y, id.z, id.w};
-    double Bi[9];
-    if (a.t_x0) {
-        double p[12];
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) p[3 * v + j] = a.t_x0[3 * (size_t)vid[v] + j];
-        double e0[3], e1[3], e2[3], c0[3], c1[3], c2[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { e0[j] = p[3 + j] - p[j]; e1[j] = p[6 + j] - p[j]; e2[j] = p[9 + j] - p[j]; }
-        cross3(e1, e2, c0); cross3(e2, e0, c1); cross3(e0, e1, c2);
-        const double idet = fast_rcp(fma(e0[0], c0[0], fma(e0[1], c0[1], e0[2] * c0[2])));
-#pragma unroll
-        for (int r = 0; r < 3; ++r) { Bi[r * 3 + 0] = c0[r] * idet; Bi[r * 3 + 1] = c1[r] * idet; Bi[r * 3 + 2] = c2[r] * idet; }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) Bi[c] = a.t_Binv[(size_t)c * a.ldt + t];
-    }
-    double x[12], Ds[9];
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) x[3 * v + j] = a.x[3 * (size_t)vid[v] + j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) F[r * 3 + j] = fma(Ds[j], Bi[r * 3 + 0], fma(Ds[3 + j], Bi[r * 3 + 1], Ds[6 + j] * Bi[r * 3 + 2]));
-}
-
-// EnergyTerm::energy of tet t at F.  The densities are the stretch models' own eval (device_math.hpp) with the prox's quadratic
-// switched off (k = 0); the signs follow the reference: the linear tet takes |sigma| (src/TetEnergyTerm.cpp:94-100), Neo-Hookean and
-// every SplineTet flip a negative smallest stretch (:138-149), StVK is even in the stretches, stable Neo-Hookean keeps the sign (its point).
-__device__ __forceinline__ double mon_tet_energy(const MonArgs &a, int t, const double *F, double w2) {
-    double U[9], S[3], V[9];
+// EnergyTerm::energy of tet t at F: its density (device_math.hpp: tet_energy_grad, the gradient discarded) times its volume
+__device__ __forceinline__ double mon_tet_energy(const ElemView &a, int t, const double *F, double w2) {
+    double U[9], S[3], V[9], sg[3];
     signed_svd3(F, U, S, V);
     const Mat mt = a.mats[a.t_mat[t]];
     const double vol = w2 / mt.k;      // w = sqrt(k vol), src/TetEnergyTerm.cpp:46-47
     const int grp = (t >= a.kb[1]) + (t >= a.kb[2]) + (t >= a.kb[3]) + (t >= a.kb[4]);
-    const double A[3] = {fabs(S[0]), fabs(S[1]), fabs(S[2])};
-    double g[3], D[3], w[3], H[6], psi;
-    if (grp == 0) {
-        psi = 0.5 * mt.k * ((A[0] - 1.0) * (A[0] - 1.0) + (A[1] - 1.0) * (A[1] - 1.0) + (A[2] - 1.0) * (A[2] - 1.0));
-    } else if (grp == 1) {
-        StretchModel<1, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        psi = m.eval(A, g, D, w);
-    } else if (grp == 2) {
-        StretchModel<2, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
-        psi = m.eval(S, g, D, w);
-    } else if (grp == 3) {
-        StretchModel<3, double> m; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        psi = m.eval(A, g, D, w);
-    } else if (mt.type == 3) {
-        SplineTableModel m; m.type = 1; m.tab = a.spl + (size_t)mt.table * kSplineTableDoubles; m.mu = 0.0; m.la = 0.0; m.k = 0.0; m.lo = 0.0;
-        m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        psi = m.eval(A, g, H);
-    } else if (mt.type == 4) {
-        StableNHModel m; m.type = 0; m.mu = (4.0 / 3.0) * mt.mu; m.la = mt.la + (5.0 / 6.0) * mt.mu; m.k = 0.0; m.alpha = 1.0 + 0.75 * m.mu / m.la;
-        m.x0[0] = S[0]; m.x0[1] = S[1]; m.x0[2] = S[2];
-        psi = m.eval(S, g, H);
-    } else {
-        SplineKappaModel m; m.type = mt.type; m.mu = mt.mu; m.la = mt.la; m.k = 0.0; m.kappa = mt.kappa; m.x0[0] = A[0]; m.x0[1] = A[1]; m.x0[2] = A[2];
-        psi = m.eval(A, g, H);
-    }
+    const double psi = tet_energy_grad(grp, mt.type, mt.mu, mt.la, mt.k, mt.kappa, a.spl + (size_t)(grp == 4 && mt.type == 3 ? mt.table : 0) * kSplineTableDoubles, S, sg);
     return psi * vol;
 }
 
@@ -143,61 +75,55 @@ template <bool RES, bool ENERGY, bool INIT, bool STOP = false>
 __global__ __launch_bounds__(256) void k_monitor(MonArgs a) {
     __shared__ double lds[4 * kMonQ];
     if (STOP && *a.stop) return;
+    const ElemView &v = a.v;
     const int blk = xcd_block(), tid = (int)threadIdx.x;
     double q[kMonQ] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (blk < a.nb_t) {
         // every lane of the block computes (signed_svd3 takes wave-uniform decisions): lanes past the end redo the last tet and add nothing
         const int t0 = blk * 256 + tid;
-        const bool valid = t0 < a.nt;
-        const int t = valid ? t0 : a.nt - 1;
-        double F[9];
-        mon_tet_F(a, t, F);
-        const double w2 = a.t_sc[t] / a.dt2;
+        const bool valid = t0 < v.nt;
+        const int t = valid ? t0 : v.nt - 1;
+        double F[9], Bi[9];
+        tet_F_binv(v, v.t_idx[t], t, F, Bi);
+        const double w2 = v.t_sc[t] / v.dt2;
         if (INIT && valid) {
 #pragma unroll
-            for (int c = 0; c < 9; ++c) a.t_zp[(size_t)c * a.ldt + t] = F[c];
+            for (int c = 0; c < 9; ++c) a.t_zp[(size_t)c * v.ldt + t] = F[c];
         }
         if (RES && valid) {
             double r[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int c = 0; c < 9; ++c) {
-                const double z = a.t_z[(size_t)c * a.ldt + t];
-                mon_row(F[c], z, a.t_zp[(size_t)c * a.ldt + t], r);
-                a.t_zp[(size_t)c * a.ldt + t] = z;
+                const double z = a.t_z[(size_t)c * v.ldt + t];
+                mon_row(F[c], z, a.t_zp[(size_t)c * v.ldt + t], r);
+                a.t_zp[(size_t)c * v.ldt + t] = z;
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) q[i] = w2 * r[i];
         }
         if (ENERGY) {
-            const double e = mon_tet_energy(a, t, F, w2);
+            const double e = mon_tet_energy(v, t, F, w2);
             if (valid) { q[4] = e; if (a.term) a.term[t] = e; }
         }
     } else if (blk < a.nb_r) {
         const int t = (blk - a.nb_t) * 256 + tid;
-        if (t < a.ntri) {
-            const int4 id = a.r_idx[t];
+        if (t < v.ntri) {
             double R[4], F[6];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) R[c] = a.r_rest[(size_t)c * a.ldr + t];
-            const double *p0 = a.x + 3 * (size_t)id.x, *p1 = a.x + 3 * (size_t)id.y, *p2 = a.x + 3 * (size_t)id.z;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {      // F (3x2) = [x1 - x0, x2 - x0] rest, as k_local_tris
-                const double b = p0[j], e1 = p1[j] - b, e2 = p2[j] - b;
-                F[j] = fma(e1, R[0], e2 * R[1]);
-                F[3 + j] = fma(e1, R[2], e2 * R[3]);
-            }
-            const double w2 = a.r_sc[t] / a.dt2;
+            for (int c = 0; c < 4; ++c) R[c] = v.r_rest[(size_t)c * v.ldr + t];
+            tri_F(R, v.r_idx[t], v.x, F);
+            const double w2 = v.r_sc[t] / v.dt2;
             if (INIT) {
 #pragma unroll
-                for (int c = 0; c < 6; ++c) a.r_zp[(size_t)c * a.ldr + t] = F[c];
+                for (int c = 0; c < 6; ++c) a.r_zp[(size_t)c * v.ldr + t] = F[c];
             }
             if (RES) {
                 double r[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int c = 0; c < 6; ++c) {
-                    const double z = a.r_z[(size_t)c * a.ldr + t];
-                    mon_row(F[c], z, a.r_zp[(size_t)c * a.ldr + t], r);
-                    a.r_zp[(size_t)c * a.ldr + t] = z;
+                    const double z = a.r_z[(size_t)c * v.ldr + t];
+                    mon_row(F[c], z, a.r_zp[(size_t)c * v.ldr + t], r);
+                    a.r_zp[(size_t)c * v.ldr + t] = z;
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) q[i] = w2 * r[i];
@@ -213,49 +139,45 @@ __global__ __launch_bounds__(256) void k_monitor(MonArgs a) {
                 const double s2 = s1 > 0.0 ? sqrt(dot3(cr, cr)) / s1 : 0.0;
                 const double e = 0.5 * w2 * ((s1 - 1.0) * (s1 - 1.0) + (s2 - 1.0) * (s2 - 1.0));
                 q[5] = e;
-                if (a.term) a.term[a.nt + t] = e;
+                if (a.term) a.term[v.nt + t] = e;
             }
         }
     } else if (blk < a.nb_h) {
         const int t = (blk - a.nb_r) * 256 + tid;
-        if (t < a.nbend) {
-            const int4 id = a.h_idx[t];
+        if (t < v.nbend) {
+            const int4 id = v.h_idx[t];
             const int vid[4] = {id.x, id.y, id.z, id.w};
-            double Dx[3] = {0.0, 0.0, 0.0};
+            double c[4], Dx[3];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {      // D_i x = sum_k c_k x_{v_k}, as k_local_bends
-                const double ck = a.h_coef[(size_t)k * a.ldb + t];
-                const double *p = a.x + 3 * (size_t)vid[k];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) Dx[j] = fma(ck, p[j], Dx[j]);
-            }
+            for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
+            hinge_Dx(c, vid, v.x, Dx);
             if (INIT) {
 #pragma unroll
-                for (int j = 0; j < 3; ++j) a.h_zp[(size_t)j * a.ldb + t] = Dx[j];
+                for (int j = 0; j < 3; ++j) a.h_zp[(size_t)j * v.ldb + t] = Dx[j];
             }
             if (RES) {
-                const double w2 = a.h_sc[t] / a.dt2;
+                const double w2 = a.h_sc[t] / v.dt2;
                 double r[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const double z = a.h_z[(size_t)j * a.ldb + t];
-                    mon_row(Dx[j], z, a.h_zp[(size_t)j * a.ldb + t], r);
-                    a.h_zp[(size_t)j * a.ldb + t] = z;
+                    const double z = a.h_z[(size_t)j * v.ldb + t];
+                    mon_row(Dx[j], z, a.h_zp[(size_t)j * v.ldb + t], r);
+                    a.h_zp[(size_t)j * v.ldb + t] = z;
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) q[i] = w2 * r[i];
             }
             if (ENERGY) {
-                const double e = 0.5 * a.h_k[t] * dot3(Dx, Dx);      // E = stiffness / 2 |D_i x|^2 (include/admm_hip.h: desc.bend_*)
+                const double e = 0.5 * v.h_k[t] * dot3(Dx, Dx);      // E = stiffness / 2 |D_i x|^2 (include/admm_hip.h: desc.bend_*)
                 q[6] = e;
-                if (a.term) a.term[a.nt + a.ntri + t] = e;
+                if (a.term) a.term[v.nt + v.ntri + t] = e;
             }
         }
     } else if (blk < a.nb_p) {
         // SpringPin terms (src/SpringEnergyTerm.hpp:31-73): D-block I3 on the pinned vertex; no energy (the reference throws, :63-66)
         const int p = (blk - a.nb_h) * 256 + tid;
         if (p < a.npin && (RES || INIT)) {
-            const double *xv = a.x + 3 * (size_t)a.pin_vert[p];
+            const double *xv = v.x + 3 * (size_t)a.pin_vert[p];
             double r[4] = {0.0, 0.0, 0.0, 0.0};
             for (int j = 0; j < a.pin_dim; ++j) {
                 const double dx = j < 3 ? xv[j] : 0.0;
@@ -276,7 +198,7 @@ __global__ __launch_bounds__(256) void k_monitor(MonArgs a) {
         if (i < a.n3) {
             const double mi = a.m[i];
             if (mi > 0.0) {
-                const double d = a.x[i] - a.Mxbar[i] / mi;
+                const double d = v.x[i] - a.Mxbar[i] / mi;
                 q[7] = mi * d * d;
             }
         }
@@ -289,15 +211,22 @@ __global__ __launch_bounds__(256) void k_monitor(MonArgs a) {
     }
 }
 
-// the one block that sums the partials: thread j adds partials j, j + 256, ... in index order, then the block sum; out [kMonQ]
-__global__ __launch_bounds__(256) void k_mon_final(const double *__restrict__ part, int nb, double *__restrict__ out) {
-    __shared__ double lds[4 * kMonQ];
-    double q[kMonQ] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+// thread j adds the partials j, j + 256, ... in index order, then the block sum: q [kMonQ] holds the totals in thread 0
+__device__ __forceinline__ void mon_sum_partials(const double *__restrict__ part, int nb, double *q, double *lds) {
+#pragma unroll
+    for (int i = 0; i < kMonQ; ++i) q[i] = 0.0;
     for (int b = (int)threadIdx.x; b < nb; b += 256) {
 #pragma unroll
         for (int i = 0; i < kMonQ; ++i) q[i] += part[(size_t)b * kMonQ + i];
     }
     block_sum<kMonQ>(q, lds);
+}
+
+// the one block that sums the partials; out [kMonQ]
+__global__ __launch_bounds__(256) void k_mon_final(const double *__restrict__ part, int nb, double *__restrict__ out) {
+    __shared__ double lds[4 * kMonQ];
+    double q[kMonQ];
+    mon_sum_partials(part, nb, q, lds);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < kMonQ; ++i) out[i] = q[i];
@@ -312,12 +241,8 @@ __global__ __launch_bounds__(256) void k_mon_decide(const double *__restrict__ p
                                                     int s, int *__restrict__ cnt, int *__restrict__ sig) {
     __shared__ double lds[4 * kMonQ];
     if (cnt[kCntAdmmStop]) return;
-    double q[kMonQ] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = (int)threadIdx.x; b < nb; b += 256) {
-#pragma unroll
-        for (int i = 0; i < kMonQ; ++i) q[i] += part[(size_t)b * kMonQ + i];
-    }
-    block_sum<kMonQ>(q, lds);
+    double q[kMonQ];
+    mon_sum_partials(part, nb, q, lds);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < kMonQ; ++i) out[i] = q[i];

@@ -16,6 +16,12 @@ void hm_tet_tangent(int n, int nd, int grp, int type, double mu, double la, doub
         for (int j = 0; j < nd; ++j) tet_tangent_apply(U, V, Hs, a, b, dF + 9 * ((size_t)i * nd + j), dP + 9 * ((size_t)i * nd + j));
     }
 }
+// n stretch triples of one model, taken as they are (no SVD): S [n][3] signed -> psi [n] the density, sg [n][3] the diagonal of dpsi/dF in
+// the frame of the signed SVD (device_math.hpp: tet_energy_grad, the one dispatch under energy() and forces())
+void hm_tet_energy_grad(int n, int grp, int type, double mu, double la, double k, double kappa, const double *tab, const double *S,
+                        double *psi, double *sg) {
+    for (int i = 0; i < n; ++i) psi[i] = tet_energy_grad(grp, type, mu, la, k, kappa, tab, S + 3 * i, sg + 3 * i);
+}
 // n triangles: F [n][6] (3x2 column-major), dF and out [n][nd][6]; out = dF - dQ (the caller scales by w^2)
 void hm_tri_tangent(int n, int nd, const double *F, const double *dF, double *out) {
     for (int i = 0; i < n; ++i) {

@@ -27,7 +27,8 @@ from admm_elastic_amd import capi, meshes
 from admm_elastic_amd.solver import Lame, Settings, Solver
 from test_cpp_api import _build_exe
 from test_device_math_host import _rot
-from test_energy_monitor import check_state, cloth_with_hinges, kind_solver, plain_state, pushed_state, signed_stretches, tet_F
+from test_energy_monitor import (check_state, cloth_with_hinges, kind_solver, plain_state, pushed_state, signed_stretches, tet_F,
+                                 tet_energies)
 from test_forces import (ALL_KINDS, SPLINE_KINDS, _one_tet_state, _tet_scene, cloth_states, kind_description, numpy_forces, rigid,
                          stretch_gradient, table_fgh)
 
@@ -530,6 +531,64 @@ def test_element_tangent_on_the_host_against_mp(kind, th):
     print("kind %d: worst |dP - ref| / (h_el |dF|) per family: %s  (bar %.0e)" % (kind, " ".join("%.1e" % w for w in worst), bar))
     for name, w in zip(FAMILIES, worst):
         assert w <= bar, (kind, name, w)
+
+
+def host_energy_grad(L, grp, typ, mu, la, k, kappa, tab, S):
+    """hm_tet_energy_grad: signed stretches S [n, 3] -> psi [n], sg [n, 3]"""
+    n = len(S)
+    Sc = np.ascontiguousarray(S, dtype=np.float64); psi = np.zeros(n); sg = np.zeros((n, 3))
+    L.hm_tet_energy_grad(C.c_int(n), C.c_int(grp), C.c_int(typ), C.c_double(mu), C.c_double(la), C.c_double(k), C.c_double(kappa),
+                         None if tab is None else tab.ctypes.data_as(dp), Sc.ctypes.data_as(dp), psi.ctypes.data_as(dp), sg.ctypes.data_as(dp))
+    return psi, sg
+
+
+# E: the largest relative deviation of the host-compiled tet_energy_grad from the numpy functions over the eight kinds and the ten families,
+# as measured with g++ -O2 on x86-64 (per kind: the docstring of test_element_energy_and_gradient_on_the_host); the assertion is 10 x that.
+# Relative: |psi - ref| / max(|ref|, k max(1, |s|^2)) and max_i |sg_i - ref_i| / max(max_i |ref_i|, k max(1, |s|^2)) -- the value's own
+# size, with k max(1, |s|^2) as the floor where it cancels (at and near rest psi and g vanish).  The floor alone does not serve as the unit:
+# at the stretches of 1e3 of the scaled family the quartic and the c(J) ~ J^3 densities reach 1e12 .. 1e27 k, and one ulp of them is far
+# above 1e-12 k |s|^2 without anything being wrong.
+E_MEASURED = 4.4e-15
+E_ASSERT = 10.0 * E_MEASURED
+
+
+@pytest.mark.parametrize("kind", ALL_KINDS)
+def test_element_energy_and_gradient_on_the_host(kind, th):
+    """device_math.hpp's tet_energy_grad -- the ONE dispatch from (grp, type) to a stretch model under energy() and forces() -- compiled for
+    the host, at the stretches of the ten families of family_F() (rest, equal, nearly equal, one inverted, equal and inverted, scaled ...),
+    taken as they are built (no SVD in between): psi against test_energy_monitor.tet_energies at F = diag(s), s_i g_i against
+    test_forces.stretch_gradient and against density2 (through tangent_coefs), the numpy functions the GPU parity tests trust.  Both sides
+    are float64 evaluations of the same formulas, so they differ by a few ulp of the value (the order of the sums, fma on one side).
+
+    Measured (host build), the worst relative deviation (E_MEASURED's units) over the ten families, value / gradient: linear 1.5e-16 / 0,
+    Neo-Hookean 5.2e-16 / 3.0e-16, StVK 4.0e-16 / 2.1e-16, the kappa splines 1.0e-15 / 6.9e-16 (all three at the 1e+-3-scaled family),
+    stable Neo-Hookean 4.3e-16 / 2.2e-16, the tabulated spline 4.2e-15 / 4.4e-15 (the nearly equal families: both sides call the same
+    table evaluator, the sums around it differ).  Every kind is three decades under 1e-12; at rest and rotated rest both are 0 or below 1e-17."""
+    _, S, _ = family_F()
+    tab = kind_description(1, kind)[2] if kind == pkg.TET_SPLINE_TABLE else None
+    kappa = KAPPA if pkg.TET_SPLINE_NH <= kind <= pkg.TET_SPLINE_COROTATED else 0.0
+    grp, typ = model_args(kind)
+    fgh, dfgh = table_fgh(tab) if tab is not None else (None, None)
+    ntab = NpTable(tab) if tab is not None else None
+    one = np.ones(1)
+    worst_psi, worst_sg = [], []
+    for f, name in enumerate(FAMILIES):
+        psi, sg = host_energy_grad(th, grp, typ, MU, LA, KK, kappa, tab, S[f])
+        e_psi = e_sg = 0.0
+        for i in range(N_FAM):
+            s = S[f][i]
+            floor = KK * max(1.0, float(np.sum(s * s)))
+            ref_psi = tet_energies(np.diag(s)[None], one, [kind], MU * one, LA * one, KK * one, kappa * one, fgh)[0][0]
+            ref_a = stretch_gradient(s, kind, MU, LA, KK, kappa, dfgh)
+            ref_b = np.array(tangent_coefs([float(v) for v in s], kind, MU, LA, KK, kappa, np.log, ntab, grad_only=True)[0], dtype=np.float64)
+            scale = max(floor, np.abs(ref_a).max())
+            e_psi = max(e_psi, abs(psi[i] - ref_psi) / max(floor, abs(ref_psi)))
+            e_sg = max(e_sg, np.abs(sg[i] - ref_a).max() / scale, np.abs(sg[i] - ref_b).max() / scale)
+        worst_psi.append(e_psi); worst_sg.append(e_sg)
+    print("kind %d: worst |psi - ref| / max(|ref|, k max(1, |s|^2)) per family: %s" % (kind, " ".join("%.1e" % w for w in worst_psi)))
+    print("kind %d: worst |sg - ref| / max(|ref|, k max(1, |s|^2)) per family:  %s  (bar %.1e)" % (kind, " ".join("%.1e" % w for w in worst_sg), E_ASSERT))
+    for name, a, b in zip(FAMILIES, worst_psi, worst_sg):
+        assert a <= E_ASSERT and b <= E_ASSERT, (kind, name, a, b)
 
 
 def test_element_tangent_at_rest_is_linear_elasticity(th):
