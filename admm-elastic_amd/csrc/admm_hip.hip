@@ -25,6 +25,7 @@
 #include "monitor.hpp"
 #include "forces.hpp"
 #include "tangent.hpp"
+#include "newton.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
 #include "gs_persist.hpp"
@@ -403,6 +404,15 @@ struct admm_hip_ctx {
     // and again by a call with more directions
     DevBuf<double> k_rec, k_rcf, k_hcf, k_d, k_out;      // records, corner contributions, the directions and the result [k_cap][3 nv]
     int k_cap = 0;
+    // frozen tangent, tangent_solve and newton_polish (newton.hpp): buffers of their own, allocated by the first call
+    DevBuf<double> nw_tfr, nw_rfr, nw_rec, nw_rcf, nw_hcf;      // the frames [30][ldt], [11][ldr]; records and corner contributions of one direction
+    DevBuf<double> nw_dinv, nw_y, nw_r, nw_p, nw_ap, nw_rhs, nw_part;      // [3 nv] each; block partials [3][blocks]
+    DevBuf<NwCg> nw_st; DevBuf<int> nw_stop, nw_pin;      // the PCG's scalars [3], its stop word, the held vertices [nv]
+    int *nw_hstop = nullptr;      // pinned: the stop word as the host reads it between chunks
+    hipEvent_t nw_ev[2] = {nullptr, nullptr};
+    bool nw_ready = false;
+    bool tri_limited = false;     // a triangle carries a strain limit that can act (min > 0 or max < 100)
+    bool xbar_of_state = false;   // Mxbar is the last step's and x its result (no set_state since)
 
     ~admm_hip_ctx() {      // (every DevBuf member, lane and dynamic collider frees its own memory after this body)
         (void)hipSetDevice(device);
@@ -411,6 +421,8 @@ struct admm_hip_ctx {
         if (comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
         if (cm_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(cm_comm);
         if (uz_fork) (void)hipEventDestroy(uz_fork);
+        if (nw_hstop) (void)hipHostFree(nw_hstop);
+        for (hipEvent_t e : nw_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_phase) (void)hipEventDestroy(e);
         for (hipEvent_t e : lt_ev) (void)hipEventDestroy(e);
         if (gs_exec) (void)hipGraphExecDestroy(gs_exec);
@@ -2510,6 +2522,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
             for (int k = 0; k < 4; ++k) rest[(size_t)k * ld + t] = d->tri_rest[4 * (size_t)o + k];
             sc[t] = dt2 * d->tri_weight[o] * d->tri_weight[o];
             lmin[t] = d->tri_limit_min[o]; lmax[t] = d->tri_limit_max[o];
+            if (lmin[t] > 0.0 || lmax[t] < 100.0) c->tri_limited = true;
         }
         HIP_TRY(c->r_idx.upload(idx)); HIP_TRY(c->r_rest.upload(rest)); HIP_TRY(c->r_sc.upload(sc));
         HIP_TRY(c->r_lmin.upload(lmin)); HIP_TRY(c->r_lmax.upload(lmax));
@@ -2888,6 +2901,7 @@ static int set_state_impl(admm_hip_ctx *c, const double *x, const double *v) {
     }
     c->pending.clear();
     c->state_set = true;
+    c->xbar_of_state = false;
     return ADMM_HIP_OK;
 }
 
@@ -3240,6 +3254,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     c->uz_iters_step = 0; c->uz_detected = false;
     struct InStep { admm_hip_ctx *c; ~InStep() { c->in_step = false; } } in_step_guard{c};
     c->in_step = true;
+    c->xbar_of_state = false;     // (newton_polish: true again where this step commits its state, below)
     // monitor (admm_hip_set_monitor): one record per ADMM iteration, written on the stream -- nothing here waits for the device
     // early exit (admm_hip_set_admm_stop): the step runs with the monitor (mode max(mode, 1)), k_mon_decide takes the place of k_mon_final,
     // and the iterations behind the stop are either never launched (the host decides: one event synchronisation per iteration) or launched
@@ -3345,6 +3360,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     if (timed && c->lk_launch > 0)
         hipLaunchKernelGGL(k_ts_reduce, dim3(c->lk_launch), dim3(256), 0, st, c->lk_ts.p, c->lk_tsn, c->lk_launch, c->lk_out.p);
     hipLaunchKernelGGL(k_finish, dim3(blocks_for(c->n3)), dim3(256), 0, st, c->n3, 1.0 / c->dt, c->x.p, c->v.p, c->curr.p);
+    c->xbar_of_state = true;      // x is this step's result and Mxbar its x_bar (newton_polish)
     HIP_TRY(hipEventRecord(c->ev_step1, st));
     HIP_TRY(hipGetLastError());
     int n_exec = admm_iters;      // iterations executed
@@ -3535,6 +3551,7 @@ int admm_hip_local_step(admm_hip_ctx *c, const double *x, double *u_inout, doubl
     if (c->ntri) HIP_TRY(hipMemcpyAsync(c->r_u.p, ru.data(), ru.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (c->npin_terms) HIP_TRY(hipMemcpyAsync(c->pin_u.p, pu.data(), pu.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (c->nbend) HIP_TRY(hipMemcpyAsync(c->h_u.p, hu.data(), hu.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    c->xbar_of_state = false;      // (Mxbar is the caller's from here on, not the last step's: newton_polish refuses)
     if (Mxbar) HIP_TRY(hipMemcpyAsync(c->Mxbar.p, Mxbar, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
     else HIP_TRY(hipMemsetAsync(c->Mxbar.p, 0, c->n3 * sizeof(double), st));
     launch_local<true>(c);
@@ -3700,6 +3717,246 @@ int admm_hip_stiffness_apply(admm_hip_ctx *c, const double *x, int32_t n_vec, co
     launch_tangent(c, xd, n_vec, shift);
     HIP_TRY(hipGetLastError());
     if (n) HIP_TRY(hipMemcpyAsync(out, c->k_out.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
+
+// ---- frozen tangent, tangent_solve, newton_polish (newton.hpp) ----
+static hipError_t newton_ensure(admm_hip_ctx *c) {
+    if (c->nw_ready) return hipSuccess;
+    hipError_t e;
+    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {      // (the padding record / element the incidence lists point at must be zero)
+        const hipError_t e2 = b.alloc(n);
+        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
+    };
+    if (c->nt) {
+        if ((e = fresh(c->nw_tfr, (size_t)kFrameTet * c->ldt)) != hipSuccess) return e;
+        if ((e = fresh(c->nw_rec, (size_t)4 * (c->n_rec + 1))) != hipSuccess) return e;
+    }
+    if (c->ntri) {
+        if ((e = fresh(c->nw_rfr, (size_t)kFrameTri * c->ldr)) != hipSuccess) return e;
+        if ((e = fresh(c->nw_rcf, (size_t)12 * c->ldr)) != hipSuccess) return e;
+    }
+    if (c->nbend && (e = fresh(c->nw_hcf, (size_t)12 * c->ldb)) != hipSuccess) return e;
+    const size_t n = (size_t)std::max(1, c->n3);
+    for (DevBuf<double> *b : {&c->nw_dinv, &c->nw_y, &c->nw_r, &c->nw_p, &c->nw_ap, &c->nw_rhs})
+        if ((e = fresh(*b, n)) != hipSuccess) return e;
+    if ((e = fresh(c->nw_part, (size_t)3 * std::max(1, blocks_for(c->nv)) + 8)) != hipSuccess) return e;      // (+ 8: the polish's sums)
+    if ((e = c->nw_st.alloc(3)) != hipSuccess) return e;
+    if ((e = c->nw_stop.alloc(1)) != hipSuccess) return e;
+    if ((e = c->nw_pin.alloc((size_t)std::max(1, c->nv))) != hipSuccess) return e;
+    if (!c->nw_hstop && (e = hipHostMalloc((void **)&c->nw_hstop, 2 * sizeof(int), hipHostMallocDefault)) != hipSuccess) return e;      // (a call that failed further down is made again)
+    for (hipEvent_t &ev : c->nw_ev)
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+    c->nw_ready = true;
+    return hipSuccess;
+}
+static int nw_blocks(const admm_hip_ctx *c) { return std::max(1, blocks_for(c->nv)); }
+static FrozenArgs frozen_args(const admm_hip_ctx *c, const double *x, const double *d, int psd, const int *stop) {
+    FrozenArgs a{};
+    a.f = force_args(c, x, c->nw_rec.p, c->nw_rcf.p, c->nw_hcf.p);
+    a.t_fr = c->nw_tfr.p; a.r_fr = c->nw_rfr.p; a.d = d; a.psd = psd; a.stop = stop;
+    return a;
+}
+// the frames of the tangent at x (device) into nw_tfr / nw_rfr
+static void launch_tangent_setup(admm_hip_ctx *c, const double *x, int psd) {
+    const FrozenArgs a = frozen_args(c, x, nullptr, psd, nullptr);
+    if (a.f.nb_r <= 0) return;
+    if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent_setup<true>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_tangent_setup<false>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
+}
+static NewtonGatherArgs newton_gather_args(const admm_hip_ctx *c, const FrozenArgs &a, const double *d, double *out, double shift, const int *pin, const int *stop) {
+    NewtonGatherArgs q{};
+    q.g = force_gather_args(c, a.f, out);
+    q.d = d; q.m = c->m.p; q.shift = shift; q.pin = pin; q.part = c->nw_part.p; q.stop = stop;
+    return q;
+}
+// out = K_frozen d + shift m o d (rows of held vertices zero); nw_part[0 .. blocks) = the partials of d . out
+static void launch_frozen(admm_hip_ctx *c, const double *d, double *out, double shift, const int *pin, const int *stop) {
+    const FrozenArgs a = frozen_args(c, nullptr, d, 0, stop);
+    const int nb = a.f.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_tangent_frozen, dim3(nb), dim3(256), 0, c->stream, a);
+    const NewtonGatherArgs q = newton_gather_args(c, a, d, out, shift, pin, stop);
+    hipLaunchKernelGGL(k_newton_gather<false>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
+}
+// nw_dinv = 1 / (diag K_frozen + shift m), 0 on held vertices
+static void launch_frozen_diag(admm_hip_ctx *c, double shift, const int *pin) {
+    const FrozenArgs a = frozen_args(c, nullptr, nullptr, 0, nullptr);
+    const int nb = a.f.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_tangent_diag, dim3(nb), dim3(256), 0, c->stream, a);
+    const NewtonGatherArgs q = newton_gather_args(c, a, nullptr, c->nw_dinv.p, shift, pin, nullptr);
+    hipLaunchKernelGGL(k_newton_gather<true>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
+}
+// nw_pin = the vertices k_stationarity skips
+static void launch_pin_mask(admm_hip_ctx *c) {
+    const bool gs = c->linsolver == 1;
+    hipLaunchKernelGGL(k_nw_pin_mask, dim3(nw_blocks(c)), dim3(256), 0, c->stream, c->nv, (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr,
+                       c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->nw_pin.p);
+}
+// Jacobi-PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device; leaves y in nw_y and the verdict in nw_st[2].
+// Iterations are enqueued in chunks, one chunk ahead of the device; the host reads the stop word of the chunk before (pinned, behind an
+// event) and stops enqueueing.  The caller synchronises.
+static int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    hipLaunchKernelGGL(k_nw_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_p.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_nw_cg_init2, dim3(1), dim3(256), 0, st, nb, c->nw_part.p, c->nw_st.p, c->nw_stop.p);
+    constexpr int chunk = 8;
+    int launched = 0, chunks = 0;
+    while (launched < max_iters) {
+        const int n = std::min(chunk, max_iters - launched);
+        for (int it = launched; it < launched + n; ++it) {
+            launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
+            hipLaunchKernelGGL(k_nw_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
+                               c->nw_y.p, c->nw_r.p, c->nw_part.p);
+            hipLaunchKernelGGL(k_nw_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
+                               c->nw_r.p, c->nw_p.p, c->nw_part.p);
+        }
+        launched += n;
+        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
+        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
+            if (c->nw_hstop[(chunks - 1) & 1]) break;
+        }
+        ++chunks;
+    }
+    // the TRUE residual rhs - (K + shift M) y of the iterate the solve returns, over the free rows: what info4 reports.  The recursive residual
+    // the stop test reads drifts from it by about eps cond(A) |rhs| -- 7e-4 of a residual of 1e-12 |rhs|.  (The launches of a chunk enqueued
+    // behind the stop are no-ops; this one carries no stop word.)
+    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);
+    hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
+    HIP_TRY(hipGetLastError());
+    return ADMM_HIP_OK;
+}
+static int newton_args_ok(const char *who, double shift, int32_t flags) {
+    if (!std::isfinite(shift)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": shift must be finite");
+    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
+    return ADMM_HIP_OK;
+}
+
+// admm_hip_stiffness_apply on the frozen tangent: one setup, then one frozen pass per direction.  flags bit 0: the element tangents are
+// projected to their positive semi-definite part; bit 1: pinned vertices are held (their rows are zero, d is ignored there)
+int admm_hip_stiffness_apply_ex(admm_hip_ctx *c, const double *x, int32_t n_vec, const double *d, double shift, int32_t flags, double *out) {
+    if (!c || !d || !out || n_vec < 1 || n_vec > 65535) return fail(ADMM_HIP_ERR_ARG, "stiffness_apply_ex: NULL argument, n_vec < 1 or n_vec > 65535");
+    if (int rc = newton_args_ok("stiffness_apply_ex", shift, flags)) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, "stiffness_apply_ex", x, &xd)) return rc;
+    HIP_TRY(newton_ensure(c));
+    hipStream_t st = c->stream;
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    launch_tangent_setup(c, xd, flags & 1);
+    for (int j = 0; j < n_vec && c->n3; ++j) {
+        HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, d + (size_t)j * c->n3, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_nw_mask, dim3(nw_blocks(c)), dim3(256), 0, st, c->nv, pin, c->nw_rhs.p, c->nw_p.p);
+        launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, nullptr);
+        HIP_TRY(hipMemcpyAsync(out + (size_t)j * c->n3, c->nw_ap.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
+
+// (K(x) [projected] + shift M) y = rhs on the free vertices by Jacobi-PCG on the device.  info4: iterations, converged, |r| / |rhs| with
+// r = rhs - A y formed once more at the end (not the recursive residual of the stop test), |rhs|
+int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, double shift, int32_t flags, double tol, int32_t max_iters,
+                           double *y, double *info4) {
+    if (!c || !rhs || !y || !info4) return fail(ADMM_HIP_ERR_ARG, "tangent_solve: NULL argument");
+    if (int rc = newton_args_ok("tangent_solve", shift, flags)) return rc;
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "tangent_solve: tol must be finite and >= 0, max_iters >= 1");
+    const double *xd;
+    if (int rc = eval_begin(c, "tangent_solve", x, &xd)) return rc;
+    HIP_TRY(newton_ensure(c));
+    hipStream_t st = c->stream;
+    if (c->n3) HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, rhs, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (int rc = tangent_solve_device(c, xd, shift, flags, tol, max_iters)) return rc;
+    NwCg h;
+    double rr_true = 0.0;
+    if (c->n3) HIP_TRY(hipMemcpyAsync(y, c->nw_y.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h, c->nw_st.p + 2, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&rr_true, c->nw_part.p + (size_t)3 * nw_blocks(c) + 2, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    info4[0] = h.it; info4[1] = h.conv; info4[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info4[3] = std::sqrt(h.bb);
+    return ADMM_HIP_OK;
+}
+
+// Projected Newton on the step's objective Phi(x) = |x - x_bar|_M^2 / (2 dt^2) + E(x), from the device-resident state of the last step.
+// records [cap][5]: Phi, |g_free|, the CG iterations and the accepted step length of the step taken from this iterate (0, 0: none), E.
+int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol, double cg_tol, int32_t cg_max, int32_t cap, int32_t *n,
+                           double *records) {
+    if (!c || !n || cap < 0 || (cap > 0 && !records)) return fail(ADMM_HIP_ERR_ARG, "newton_polish: bad argument");
+    if (max_newton < 0 || !(grad_tol >= 0.0) || !(cg_tol >= 0.0) || !std::isfinite(cg_tol) || cg_max < 1)
+        return fail(ADMM_HIP_ERR_ARG, "newton_polish: max_newton >= 0, grad_tol >= 0, cg_tol finite and >= 0, cg_max >= 1");
+    if (int rc = mon_refuse(c, "newton_polish")) return rc;      // (single-GPU contexts only: the rules of energy(), forces() and stiffness_apply())
+    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has colliders; contact is not part of the objective the polish minimises");
+    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has strain-limited triangles; the energy ignores the limits");
+    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has slide pins");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = settle(c)) return rc;
+    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "newton_polish: no step has run on this state yet (the objective needs the step's x_bar)");
+    HIP_TRY(newton_ensure(c));
+    HIP_TRY(force_ensure(c, false, 0));
+    HIP_TRY(mon_ensure(c, false, false));
+    const int nv = c->nv, nb = nw_blocks(c);
+    const double idt2 = 1.0 / (c->dt * c->dt);
+    double *sums = c->nw_part.p + (size_t)3 * nb;      // [0] |g|^2, [1] g . delta
+    auto objective = [&](const double *xd, double *phi, double *el) -> int {      // (one synchronisation)
+        const MonArgs a = mon_args(c, xd, true);
+        launch_monitor<false, true>(c, a, c->mon_out.p);
+        double h[kMonQ];
+        HIP_TRY(hipMemcpyAsync(h, c->mon_out.p, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *el = (h[4] + h[5]) + h[6];
+        *phi = *el + 0.5 * idt2 * h[7];
+        return ADMM_HIP_OK;
+    };
+    launch_pin_mask(c);
+    double phi = 0.0, el = 0.0;
+    if (int rc = objective(c->x.p, &phi, &el)) return rc;
+    *n = 0;
+    for (int k = 0; ; ++k) {
+        launch_forces(c, c->x.p, false, nullptr);
+        hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->nw_rhs.p, c->nw_part.p);
+        hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+        double g2 = 0.0;
+        HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const double gn = std::sqrt(g2);
+        double *rec = (*n < cap) ? records + 5 * (size_t)*n : nullptr;
+        if (rec) { rec[0] = phi; rec[1] = gn; rec[2] = 0.0; rec[3] = 0.0; rec[4] = el; }
+        *n += 1;
+        if (!(gn > grad_tol) || k >= max_newton) break;      // (a NaN gradient ends the polish too)
+        if (int rc = tangent_solve_device(c, c->x.p, idt2, 3, cg_tol, cg_max)) return rc;
+        hipLaunchKernelGGL(k_nw_slope, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, c->nw_y.p, c->nw_part.p);
+        hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums + 1, nullptr);
+        NwCg h;
+        double slope = 0.0;
+        HIP_TRY(hipMemcpyAsync(&h, c->nw_st.p + 2, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&slope, sums + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (rec) rec[2] = h.it;
+        double t = 1.0, phi_t = 0.0, el_t = 0.0;
+        bool accepted = false;
+        for (int trial = 0; trial < 10; ++trial, t *= 0.5) {      // Armijo, c = 1e-4; a non-finite Phi is a rejection
+            hipLaunchKernelGGL(k_nw_axpy, dim3(blocks_for(c->n3)), dim3(256), 0, st, c->n3, t, 0.0, c->nw_y.p, c->x.p, c->curr.p, (double *)nullptr);
+            if (int rc = objective(c->curr.p, &phi_t, &el_t)) return rc;
+            if (std::isfinite(phi_t) && phi_t <= phi + 1e-4 * t * slope) { accepted = true; break; }
+        }
+        if (!accepted) break;
+        hipLaunchKernelGGL(k_nw_axpy, dim3(blocks_for(c->n3)), dim3(256), 0, st, c->n3, t, t / c->dt, c->nw_y.p, c->x.p, c->x.p, c->v.p);
+        phi = phi_t; el = el_t;
+        if (rec) rec[3] = t;
+    }
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return ADMM_HIP_OK;
 }

@@ -1168,6 +1168,52 @@ __device__ __forceinline__ void tet_tangent_coef(int grp, int type, double mu, d
             if ((S[pi[q]] < 0.0) != (S[pj[q]] < 0.0)) { Hs[ph[q]] = -Hs[ph[q]]; const double t = al[q]; al[q] = be[q]; be[q] = t; }
     }
 }
+// One Jacobi rotation of the symmetric 3x3 A in the plane (p, q), r the third index, accumulated into the eigenvector columns vp, vq
+__device__ __forceinline__ void sym3_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *vp, double *vq) {
+    if (apq == 0.0) return;
+    const double th = (aqq - app) / (2.0 * apq);
+    const double t = (th < 0.0 ? -1.0 : 1.0) / (fabs(th) + sqrt(fma(th, th, 1.0)));      // th = +-inf: t = 0
+    const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+    app = fma(-t, apq, app); aqq = fma(t, apq, aqq); apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = fma(c, rp, -s * rq); arq = fma(s, rp, c * rq);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { const double a = vp[i], b = vq[i]; vp[i] = fma(c, a, -s * b); vq[i] = fma(s, a, c * b); }
+}
+// The Frobenius-nearest positive semi-definite tangent of a tet, on the coefficients of tet_tangent_coef: in the frame of the signed SVD
+// dP/dF is block-diagonal -- three twist eigenvalues al, three flip eigenvalues be, the 3x3 block Hs -- so al <- max(al, 0),
+// be <- max(be, 0), Hs <- its positive part (cyclic Jacobi in FP64, 6 sweeps; Hs - sum_{lambda_k < 0} lambda_k v_k v_k^T).  An Hs
+// without a negative eigenvalue is left UNTOUCHED: an element that is positive semi-definite already keeps its bits.
+// NEGATIVE means below -kPsdNoise h, h the largest coefficient of the element.  A stress-free element has exact zero eigenvalues (be = 0:
+// an infinitesimal rotation costs nothing), which the arithmetic returns as +-(a few ulp of h); clamping on their sign would change the
+// bits of elements at rest for nothing.  What is left below zero is <= 5.7e-14 h, the rounding of the coefficients themselves.
+constexpr double kPsdNoise = 0x1p-44;
+__device__ __forceinline__ void tet_tangent_psd(double *Hs, double *al, double *be) {
+    double h = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) h = fmax(h, fabs(Hs[q]));
+#pragma unroll
+    for (int q = 0; q < 3; ++q) h = fmax(h, fmax(fabs(al[q]), fabs(be[q])));
+    const double neg = -kPsdNoise * h;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { al[q] = al[q] < neg ? 0.0 : al[q]; be[q] = be[q] < neg ? 0.0 : be[q]; }
+    double a00 = Hs[0], a01 = Hs[1], a02 = Hs[2], a11 = Hs[3], a12 = Hs[4], a22 = Hs[5];
+    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < 6; ++sweep) {
+        sym3_rotate(a00, a11, a01, a02, a12, v0, v1);
+        sym3_rotate(a00, a22, a02, a01, a12, v0, v2);
+        sym3_rotate(a11, a22, a12, a01, a02, v1, v2);
+    }
+    const double n0 = a00 < neg ? a00 : 0.0, n1 = a11 < neg ? a11 : 0.0, n2 = a22 < neg ? a22 : 0.0;
+    if (n0 == 0.0 && n1 == 0.0 && n2 == 0.0) return;
+    const int hi[6] = {0, 0, 0, 1, 1, 2}, hj[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        const int i = hi[q], j = hj[q];
+        Hs[q] -= fma(n0 * v0[i], v0[j], fma(n1 * v1[i], v1[j], n2 * v2[i] * v2[j]));
+    }
+}
+
 // dP = U B V^T, B from A = U^T dF V: B_ii = sum_j Hs_ij A_jj, B_ij = a_ij A_ij + b_ij A_ji with a = (al + be) / 2, b = (al - be) / 2
 // (pairs (0,1), (0,2), (1,2)).  dF, dP column-major.
 __device__ __forceinline__ void tet_tangent_apply(const double *U, const double *V, const double *Hs, const double *a, const double *b,
@@ -1223,6 +1269,28 @@ __device__ __forceinline__ void tri_tangent_apply(const double *Q, const double 
         out[j] = dF[j] - fma(om, Q[3 + j], fma(n0, Si[0], n1 * Si[1]));
         out[3 + j] = dF[3 + j] - fma(-om, Q[j], fma(n0, Si[1], n1 * Si[2]));
     }
+}
+// The positive semi-definite part of a triangle's operator I - dQ/dF, on the frame of tri_tangent_frame.  Its eigenvalues: 1 (the
+// in-plane symmetric modes), 1 - 2 / (sigma_1 + sigma_2) (the in-plane twist), 1 - 1 / sigma_i (the two out-of-plane modes, in the
+// eigenbasis of S).  The twist factor is clamped at 0 (itr <- min(itr, 1/2)) and W = I - S^-1 replaced by its positive part (closed-form
+// 2x2 symmetric eigen-decomposition; Si <- I - W+).  A frame without a negative eigenvalue keeps its bits; negative means below
+// -kPsdNoise (the operator's scale is 1), as in tet_tangent_psd: a triangle at rest has these three eigenvalues at 0 +- rounding.
+__device__ __forceinline__ void tri_tangent_psd(double *Si, double &itr) {
+    if (1.0 - 2.0 * itr < -kPsdNoise) itr = 0.5;
+    const double a = 1.0 - Si[0], b = -Si[1], d = 1.0 - Si[2];
+    const double mean = 0.5 * (a + d), diff = 0.5 * (a - d), r = sqrt(fma(diff, diff, b * b));
+    if (mean - r >= -kPsdNoise) return;
+    if (mean + r <= 0.0) { Si[0] = 1.0; Si[1] = 0.0; Si[2] = 1.0; return; }
+    const double lp = 0.5 * (mean + r), ir = 1.0 / r;      // W+ = lambda_+ / 2 (I + [[diff, b], [b, -diff]] / r)
+    Si[0] = 1.0 - lp * fma(diff, ir, 1.0);
+    Si[1] = -lp * (b * ir);
+    Si[2] = 1.0 - lp * fma(-diff, ir, 1.0);
+}
+// out = the positive semi-definite part of (I - dQ/dF) applied to dF; the caller scales it by w^2
+__device__ __forceinline__ void tri_tangent_apply_psd(const double *Q, const double *Si, double itr, const double *dF, double *out) {
+    double Sp[3] = {Si[0], Si[1], Si[2]}, tw = itr;
+    tri_tangent_psd(Sp, tw);
+    tri_tangent_apply(Q, Sp, tw, dF, out);
 }
 
 } // namespace admm_dev

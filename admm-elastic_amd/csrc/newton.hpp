@@ -1,0 +1,477 @@
+// newton.hpp -- the second-order finish of a step on the device: a tangent FROZEN at x (optionally projected to its positive
+// semi-definite part), applied many times; the Jacobi-PCG built on it (admm_hip_tangent_solve) and the vector kernels of the projected
+// Newton polish (admm_hip_newton_polish).  Included once by admm_hip.hip, after tangent.hpp.
+//
+// k_tangent (tangent.hpp) runs the signed SVD and the coefficient evaluation on every call; a CG iteration must not.
+//   k_tangent_setup<TABLE>  once per x.  The block ranges of k_tangent without the hinges, lane = tet / triangle, elements read through
+//             elements.hpp.  Per tet: tet_F_binv, signed_svd3, tet_tangent_coef, with `psd` tet_tangent_psd; stores the frame, SoA
+//             [kFrameTet][ldt] (one coalesced 512-byte wave access per component):  U (9), N = Binv V (9), vol {Hs (6), a (3), b (3)}.
+//             Per triangle [kFrameTri][ldr]: Q (6), Si (3), itr (with `psd` through tri_tangent_psd), w^2.
+//   k_tangent_frozen        per application.  A = U^T Ds(d) N, B from A and the coefficients (as tet_tangent_apply), corner contributions
+//             U B N^T -- neither V nor Binv is needed again -- reduced per chunk into the 32-byte records of k_forces / k_tangent
+//             (chunk_reduce_store, the same host plan).  Triangles: tri_tangent_apply on the stored frame; hinges as k_tangent.
+//   k_tangent_diag          the diagonal of the frozen operator: per tet and corner the three entries e_k . K_el e_k from twelve frozen
+//             applications to dF = e_k (x) grad N_a; they travel in the same records and corner buffers.
+//   k_newton_gather<DIAG>   lane = vertex, the incidence lists of k_gather_rhs in list order.  DIAG = false: out = K d + shift m o d, rows
+//             of held vertices zero, and the block's partial of d . out; DIAG = true: out = 1 / (diag K + shift m), 0 on held vertices.
+// The PCG (y, r, p, Ap, D^-1; z = D^-1 r is not stored) per iteration: k_tangent_frozen on p, k_newton_gather, k_nw_cg_step (alpha; y, r;
+// partials of r.z and r.r), k_nw_cg_dir (beta; p; the stop decision).  The update of p needs the complete r.z of the SAME iteration, so
+// it is a launch of its own: no grid barrier, no persistent kernel.  Every block re-reduces the partials in the same order (as k_big_vec,
+// k_stat_final), so all blocks hold the same alpha, beta and verdict.  WHO WRITES WHAT: the scalars of iteration it + 1 (NwCg st[(it + 1)
+// & 1], the copy for the host st[2]) and the stop word are written by block 0 of k_nw_cg_dir(it) only and read by later launches only --
+// k_nw_cg_dir itself looks at st[it & 1] -- its .done, and its iteration number, which tells a launch enqueued behind the end of the solve
+// (two slots: the one behind the final one still says "running") -- not at the stop word (kernels.hpp: the rule of kCntAdmmStop).  The stop
+// test reads the RECURSIVE residual; what the solve reports is the true one, rhs - A y formed once more after the last iteration.
+//
+// REPRODUCIBLE to the bit: fixed summation orders, ordinary vector stores, no floating-point atomics.
+#pragma once
+#include "tangent.hpp"
+
+namespace admm_k {
+
+constexpr int kFrameTet = 30, kFrameTri = 11;
+
+struct FrozenArgs {
+    ForceArgs f;              // the chunk plan and the element lists (f.v.x: the positions, read by the setup only); rec, r_cf, h_cf: the pass's output
+    double *t_fr, *r_fr;      // the frames [kFrameTet][ldt], [kFrameTri][ldr]
+    const double *d;          // the direction [3 nv] (k_tangent_frozen)
+    int psd;                  // the setup projects the element tangents
+    const int *stop;          // set: the launch is a no-op (or nullptr)
+};
+
+// corner contributions f [12] of a frozen tet (U, N column-major; Hs, a, b scaled by vol) for the edge matrix Ds (Ds[3 m + j] = (d_{m+1} - d_0)_j)
+__device__ __forceinline__ void tet_frozen_apply(const double *U, const double *N, const double *Hs, const double *a, const double *b,
+                                                 const double *Ds, double *f) {
+    double T[9], A[9], B[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ADMM_M3(T, j, c) = fma(Ds[j], ADMM_M3(N, 0, c), fma(Ds[3 + j], ADMM_M3(N, 1, c), Ds[6 + j] * ADMM_M3(N, 2, c)));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(A, r, c) = fma(ADMM_M3(U, 0, r), ADMM_M3(T, 0, c), fma(ADMM_M3(U, 1, r), ADMM_M3(T, 1, c), ADMM_M3(U, 2, r) * ADMM_M3(T, 2, c)));
+    const double a0 = ADMM_M3(A, 0, 0), a1 = ADMM_M3(A, 1, 1), a2 = ADMM_M3(A, 2, 2);
+    ADMM_M3(B, 0, 0) = fma(Hs[0], a0, fma(Hs[1], a1, Hs[2] * a2));
+    ADMM_M3(B, 1, 1) = fma(Hs[1], a0, fma(Hs[3], a1, Hs[4] * a2));
+    ADMM_M3(B, 2, 2) = fma(Hs[2], a0, fma(Hs[4], a1, Hs[5] * a2));
+    ADMM_M3(B, 0, 1) = fma(a[0], ADMM_M3(A, 0, 1), b[0] * ADMM_M3(A, 1, 0)); ADMM_M3(B, 1, 0) = fma(a[0], ADMM_M3(A, 1, 0), b[0] * ADMM_M3(A, 0, 1));
+    ADMM_M3(B, 0, 2) = fma(a[1], ADMM_M3(A, 0, 2), b[1] * ADMM_M3(A, 2, 0)); ADMM_M3(B, 2, 0) = fma(a[1], ADMM_M3(A, 2, 0), b[1] * ADMM_M3(A, 0, 2));
+    ADMM_M3(B, 1, 2) = fma(a[2], ADMM_M3(A, 1, 2), b[2] * ADMM_M3(A, 2, 1)); ADMM_M3(B, 2, 1) = fma(a[2], ADMM_M3(A, 2, 1), b[2] * ADMM_M3(A, 1, 2));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ADMM_M3(T, j, c) = fma(ADMM_M3(U, j, 0), ADMM_M3(B, 0, c), fma(ADMM_M3(U, j, 1), ADMM_M3(B, 1, c), ADMM_M3(U, j, 2) * ADMM_M3(B, 2, c)));
+#pragma unroll
+    for (int j = 0; j < 3; ++j) f[j] = 0.0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double h = fma(ADMM_M3(T, j, 0), ADMM_M3(N, m, 0), fma(ADMM_M3(T, j, 1), ADMM_M3(N, m, 1), ADMM_M3(T, j, 2) * ADMM_M3(N, m, 2)));
+            f[3 * (m + 1) + j] = h;
+            f[j] -= h;
+        }
+}
+
+template <bool TABLE>
+__global__ __launch_bounds__(256) void k_tangent_setup(FrozenArgs fa) {
+    if (fa.stop && *fa.stop) return;
+    const ForceArgs &a = fa.f;
+    const ElemView &v = a.v;
+    const int blk = xcd_block(), tid = (int)threadIdx.x;
+    if (blk < a.nb_t) {
+        const ChunkLane ln = chunk_locate(v.kb, a.cb, blk, tid);      // lanes past the model's range redo its last tet (signed_svd3 takes wave votes)
+        const int t = ln.t, grp = ln.grp;
+        const double w2 = v.t_sc[t] / v.dt2;
+        const Mat mt = v.mats[v.t_mat[t]];
+        double U[9], S[3], V[9], N[9];
+        {
+            double Bi[9], F[9];
+            tet_F_binv(v, v.t_idx[t], t, F, Bi);
+            signed_svd3(F, U, S, V);
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int m = 0; m < 3; ++m) ADMM_M3(N, m, c) = fma(Bi[m], ADMM_M3(V, 0, c), fma(Bi[3 + m], ADMM_M3(V, 1, c), Bi[6 + m] * ADMM_M3(V, 2, c)));
+        }
+        double Hs[6], al[3], be[3];
+        tet_tangent_coef<TABLE>(grp, mt.type, mt.mu, mt.la, mt.k, mt.kappa, v.spl + (size_t)(TABLE && grp == 4 && mt.type == 3 ? mt.table : 0) * kSplineTableDoubles,
+                                S, Hs, al, be);
+        if (fa.psd) tet_tangent_psd(Hs, al, be);
+        const double vol = w2 / mt.k;      // w = sqrt(k vol), src/TetEnergyTerm.cpp:46-47
+        if (!ln.valid) return;
+        double *fr = fa.t_fr + t;
+        const size_t ld = (size_t)v.ldt;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) { fr[c * ld] = U[c]; fr[(9 + c) * ld] = N[c]; }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) fr[(18 + c) * ld] = vol * Hs[c];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { fr[(24 + q) * ld] = vol * (0.5 * (al[q] + be[q])); fr[(27 + q) * ld] = vol * (0.5 * (al[q] - be[q])); }
+    } else {
+        const int t = (blk - a.nb_t) * 256 + tid;
+        if (t >= v.ntri) return;
+        double R[4], F[6], Q[6], Si[3], itr;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) R[c] = v.r_rest[(size_t)c * v.ldr + t];
+        tri_F(R, v.r_idx[t], v.x, F);
+        tri_tangent_frame(F, Q, Si, itr);
+        if (fa.psd) tri_tangent_psd(Si, itr);
+        double *fr = fa.r_fr + t;
+        const size_t ld = (size_t)v.ldr;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) fr[c * ld] = Q[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) fr[(6 + c) * ld] = Si[c];
+        fr[9 * ld] = itr;
+        fr[10 * ld] = v.r_sc[t] / v.dt2;
+    }
+}
+
+// the frame of tet t into registers
+__device__ __forceinline__ void tet_frame_load(const double *t_fr, size_t ld, int t, double *U, double *N, double *Hs, double *a, double *b) {
+    const double *fr = t_fr + t;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) { U[c] = fr[c * ld]; N[c] = fr[(9 + c) * ld]; }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) Hs[c] = fr[(18 + c) * ld];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { a[q] = fr[(24 + q) * ld]; b[q] = fr[(27 + q) * ld]; }
+}
+
+// DIAG = false: the frozen operator applied to fa.d; DIAG = true: its diagonal (every corner's three entries in the place of its contribution)
+template <bool DIAG>
+__device__ __forceinline__ void tangent_frozen_body(const FrozenArgs &fa, double *sLm) {
+    const ForceArgs &a = fa.f;
+    const ElemView &v = a.v;
+    const int blk = xcd_block(), tid = (int)threadIdx.x;
+    if (blk < a.nb_t) {
+        LdsDk *sL = (LdsDk *)sLm;
+        const ChunkLane ln = chunk_locate(v.kb, a.cb, blk, tid);
+        const int t = ln.t;
+        LdsDk *sCf = sL + tid;
+        if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;                 // the padding column of the reduction lists
+        const int g0 = __builtin_amdgcn_readfirstlane(a.ch_group[blk]), g1 = __builtin_amdgcn_readfirstlane(a.ch_group[blk + 1]);
+        const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[blk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[blk + 1]) - r0;
+        const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
+        const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+        double U[9], N[9], Hs[6], ca[3], cb[3], f[12];
+        tet_frame_load(fa.t_fr, (size_t)v.ldt, t, U, N, Hs, ca, cb);
+        if (!DIAG) {
+            const int4 id = v.t_idx[t];
+            const int vid[4] = {id.x, id.y, id.z, id.w};
+            double x[12], Ds[9];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) x[3 * c + j] = fa.d[3 * (size_t)vid[c] + j];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
+            tet_frozen_apply(U, N, Hs, ca, cb, Ds, f);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 12; ++q) f[q] = 0.0;
+#pragma unroll 1
+            for (int q = 0; q < 12; ++q) {      // corner q / 3, coordinate q % 3: d = e_k at that corner
+                const int c = q / 3, k = q - 3 * c;
+                double Ds[9], g[12];
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) Ds[3 * m + j] = j != k ? 0.0 : c == 0 ? -1.0 : c == m + 1 ? 1.0 : 0.0;
+                tet_frozen_apply(U, N, Hs, ca, cb, Ds, g);
+#pragma unroll
+                for (int p = 0; p < 12; ++p) f[p] = p == q ? g[p] : f[p];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 12; ++c) sCf[c * kChunkLdK] = f[c];
+        __syncthreads();
+        chunk_reduce_store(sL, re, e0, g0, g1, r0, nrec, a.rec);
+    } else if (blk < a.nb_r) {
+        const int t = (blk - a.nb_t) * 256 + tid;
+        if (t >= v.ntri) return;
+        const int4 id = v.r_idx[t];
+        double R[4], Q[6], Si[3];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) R[c] = v.r_rest[(size_t)c * v.ldr + t];
+        const double *fr = fa.r_fr + t;
+        const size_t ld = (size_t)v.ldr;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) Q[c] = fr[c * ld];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Si[c] = fr[(6 + c) * ld];
+        const double itr = fr[9 * ld], w2 = fr[10 * ld];
+        if (!DIAG) {
+            double dF[6], G[6];
+            tri_F(R, id, fa.d, dF);
+            tri_tangent_apply(Q, Si, itr, dF, G);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) tri_corner_store(w2 * G[j], w2 * G[3 + j], R, a.r_cf + (size_t)j * v.ldr, v.ldr, t);
+        } else {
+#pragma unroll 1
+            for (int q = 0; q < 9; ++q) {      // corner q / 3, coordinate q % 3
+                const int c = q / 3, k = q - 3 * c;
+                const double e1 = c == 1 ? 1.0 : c == 0 ? -1.0 : 0.0, e2 = c == 2 ? 1.0 : c == 0 ? -1.0 : 0.0;
+                double dF[6], G[6];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { dF[j] = j == k ? fma(e1, R[0], e2 * R[1]) : 0.0; dF[3 + j] = j == k ? fma(e1, R[2], e2 * R[3]) : 0.0; }
+                tri_tangent_apply(Q, Si, itr, dF, G);
+                const double G0 = w2 * (k == 0 ? G[0] : k == 1 ? G[1] : G[2]), G1 = w2 * (k == 0 ? G[3] : k == 1 ? G[4] : G[5]);
+                const double h1 = fma(G0, R[0], G1 * R[2]), h2 = fma(G0, R[1], G1 * R[3]);
+                a.r_cf[(size_t)q * v.ldr + t] = c == 0 ? -(h1 + h2) : c == 1 ? h1 : h2;
+            }
+        }
+    } else {
+        const int t = (blk - a.nb_r) * 256 + tid;
+        if (t >= v.nbend) return;
+        const int4 id = v.h_idx[t];
+        const int vid[4] = {id.x, id.y, id.z, id.w};
+        double c[4], Dx[3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
+        const double ks = v.h_k[t];
+        if (!DIAG) hinge_Dx(c, vid, fa.d, Dx);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * v.ldb + t] = DIAG ? c[k] * (ks * c[k]) : c[k] * (ks * Dx[j]);
+    }
+}
+__global__ __launch_bounds__(256) void k_tangent_frozen(FrozenArgs fa) {
+    __shared__ double sLm[12 * kChunkLdK];      // the chunk's corner contributions
+    if (fa.stop && *fa.stop) return;
+    tangent_frozen_body<false>(fa, sLm);
+}
+__global__ __launch_bounds__(256) void k_tangent_diag(FrozenArgs fa) {
+    __shared__ double sLm[12 * kChunkLdK];
+    tangent_frozen_body<true>(fa, sLm);
+}
+
+// lane = vertex: the sum of the records and corner contributions incident to it (the lists of k_gather_rhs, in list order)
+struct NewtonGatherArgs {
+    ForceGatherArgs g;        // t_rec, r_cf, h_cf: what the frozen pass left; f: the result [nv][3]
+    const double *d, *m;      // the direction (DIAG: unused), the masses [3 nv]
+    double shift;
+    const int *pin;           // [nv] nonzero: a held vertex (row and column dropped), or nullptr
+    double *part;             // [blocks] partials of d . out (DIAG: unused)
+    const int *stop;
+};
+template <bool DIAG>
+__global__ __launch_bounds__(256) void k_newton_gather(NewtonGatherArgs na) {
+    __shared__ double lds[4];
+    if (na.stop && *na.stop) return;
+    const ForceGatherArgs &a = na.g;
+    const int lane = threadIdx.x & 63;
+    const int s = wave_slice();
+    double q[1] = {0.0};
+    if (s < a.n_slices) {
+        const int r = s * 64 + lane;
+        const int v = r < a.nv ? a.order[r] : a.nv;
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (a.t_inc) gather_records(a.t_inc + a.t_ptr[s] + lane, a.t_w[s], a.t_rec, acc);
+        if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf, a.r_ld, acc);
+        if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf, a.h_ld, acc);
+        if (v < a.nv) {
+            const bool held = na.pin && na.pin[v] != 0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const size_t i = 3 * (size_t)v + j;
+                if (DIAG) {
+                    const double dg = fma(na.shift, na.m[i], acc[j]);
+                    a.f[i] = held ? 0.0 : dg > 0.0 ? 1.0 / dg : 1.0;      // (an indefinite unprojected operator: no scaling on that row)
+                } else {
+                    const double di = na.d[i], o = held ? 0.0 : fma(na.shift * na.m[i], di, acc[j]);
+                    a.f[i] = o;
+                    q[0] = fma(di, o, q[0]);
+                }
+            }
+        }
+    }
+    if (!DIAG) {
+        block_sum<1>(q, lds);
+        if (threadIdx.x == 0) na.part[xcd_block()] = q[0];
+    }
+}
+
+// ---- the vector kernels of the PCG: grid = blocks_for(nv), lane = vertex ----
+struct NwCg { double rz, rr, bb; int it, done, conv, pad_; };      // r . z, r . r, |rhs|^2 over the free rows; iterations done; ended; met its tolerance
+
+// q[i] = the sum of part[i nb + 0 .. nb) in a fixed order, in every thread
+template <int NQ>
+__device__ __forceinline__ void nw_reduce(const double *__restrict__ part, int nb, double *q, double *lds) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        q[i] = 0.0;
+        for (int b = (int)threadIdx.x; b < nb; b += 256) q[i] += part[(size_t)i * nb + b];
+    }
+    block_sum<NQ>(q, lds);
+}
+__device__ __forceinline__ bool nw_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (false for NaN)
+
+// pin[v] = 1 where k_stationarity skips a vertex: an active pin term (vert_pin / pin_active) or a pin of the GS sweeps (pin_flag)
+__global__ __launch_bounds__(256) void k_nw_pin_mask(int nv, const int *__restrict__ vert_pin, const int *__restrict__ pin_active,
+                                                     const int *__restrict__ pin_flag, int *__restrict__ pin) {
+    const int v = blockIdx.x * 256 + (int)threadIdx.x;
+    if (v >= nv) return;
+    bool held = false;
+    if (vert_pin) { const int pi = vert_pin[v]; held = pi >= 0 && pin_active[pi] != 0; }
+    if (pin_flag) held = held || pin_flag[v] != 0;
+    pin[v] = held ? 1 : 0;
+}
+// out = in with the held vertices zeroed
+__global__ __launch_bounds__(256) void k_nw_mask(int nv, const int *__restrict__ pin, const double *__restrict__ in, double *__restrict__ out) {
+    const int v = blockIdx.x * 256 + (int)threadIdx.x;
+    if (v >= nv) return;
+    const bool held = pin && pin[v] != 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; out[i] = held ? 0.0 : in[i]; }
+}
+// y = 0, r = rhs on the free rows, p = z = D^-1 r; partials of r . z and r . r
+__global__ __launch_bounds__(256) void k_nw_cg_init(int nv, int nb, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ dinv,
+                                                    double *__restrict__ y, double *__restrict__ r, double *__restrict__ p, double *__restrict__ part) {
+    __shared__ double lds[8];
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[2] = {0.0, 0.0};
+    if (v < nv) {
+        const bool held = pin && pin[v] != 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            const double ri = held ? 0.0 : rhs[i], zi = dinv[i] * ri;
+            y[i] = 0.0; r[i] = ri; p[i] = zi;
+            q[0] = fma(ri, zi, q[0]); q[1] = fma(ri, ri, q[1]);
+        }
+    }
+    block_sum<2>(q, lds);
+    if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
+}
+// one block: the scalars of iteration 0 and the stop word (a zero or non-finite right-hand side ends the solve here)
+__global__ __launch_bounds__(256) void k_nw_cg_init2(int nb, const double *__restrict__ part, NwCg *__restrict__ st, int *__restrict__ stop) {
+    __shared__ double lds[8];
+    double q[2];
+    nw_reduce<2>(part + nb, nb, q, lds);
+    if (threadIdx.x == 0) {
+        NwCg s;
+        s.rz = q[0]; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
+        s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(q[0] > 0.0) || !nw_finite(q[0]);
+        s.conv = q[1] == 0.0;
+        st[0] = s; st[2] = s;
+        *stop = s.done;
+    }
+}
+// alpha = r.z / p.Ap; y += alpha p, r -= alpha Ap; partials of the new r . z (z = D^-1 r) and r . r.  A breakdown (p.Ap <= 0 or a
+// non-finite scalar) leaves y and r as they are; k_nw_cg_dir reaches the same verdict from the same numbers and ends the solve.
+__global__ __launch_bounds__(256) void k_nw_cg_step(int it, int nv, int nb, const NwCg *__restrict__ st, const int *stop, const double *__restrict__ dinv,
+                                                    const double *__restrict__ p, const double *__restrict__ ap, double *__restrict__ y,
+                                                    double *__restrict__ r, double *__restrict__ part) {
+    __shared__ double lds[8];
+    if (*stop) return;
+    const NwCg s = st[it & 1];
+    double pap[1];
+    nw_reduce<1>(part, nb, pap, lds);
+    if (!(pap[0] > 0.0) || !nw_finite(pap[0])) return;
+    const double alpha = s.rz / pap[0];
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[2] = {0.0, 0.0};
+    if (v < nv) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            y[i] = fma(alpha, p[i], y[i]);
+            const double ri = fma(-alpha, ap[i], r[i]);
+            r[i] = ri;
+            q[0] = fma(ri * dinv[i], ri, q[0]); q[1] = fma(ri, ri, q[1]);
+        }
+    }
+    block_sum<2>(q, lds);
+    if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
+}
+// beta = r.z new / r.z old; p = D^-1 r + beta p; block 0 writes the scalars of iteration it + 1, the verdict and the stop word
+__global__ __launch_bounds__(256) void k_nw_cg_dir(int it, int nv, int nb, NwCg *st, int *stop, double tol2, int max_iters, const double *__restrict__ dinv,
+                                                   const double *__restrict__ r, double *__restrict__ p, const double *__restrict__ part) {
+    __shared__ double lds[12];
+    const NwCg s = st[it & 1];
+    if (s.done || s.it != it) return;      // ended, or a launch behind the end: st[it & 1] is then the slot of iteration it - 2
+    double q[3];
+    nw_reduce<3>(part, nb, q, lds);
+    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);
+    NwCg n = s;
+    if (broke) { n.done = 1; n.conv = 0; }
+    else {
+        n.rz = q[1]; n.rr = q[2]; n.it = s.it + 1;
+        n.conv = q[2] <= tol2 * s.bb;
+        n.done = n.conv || n.it >= max_iters || !nw_finite(q[1]) || !nw_finite(q[2]) || !(q[1] > 0.0);
+    }
+    if (!n.done) {
+        const double beta = q[1] / s.rz;
+        const int v = xcd_block() * 256 + (int)threadIdx.x;
+        if (v < nv) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; p[i] = fma(beta, p[i], dinv[i] * r[i]); }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st[(it + 1) & 1] = n; st[2] = n;
+        if (n.done) *stop = 1;
+    }
+}
+
+// block partials of |rhs - ay|^2 over the free rows, ay = (K + shift M) y as k_newton_gather left it: the true residual of the iterate a
+// solve returns
+__global__ __launch_bounds__(256) void k_nw_true_resid(int nv, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ ay,
+                                                       double *__restrict__ part) {
+    __shared__ double lds[4];
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[1] = {0.0};
+    if (v < nv && !(pin && pin[v] != 0)) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; const double r = rhs[i] - ay[i]; q[0] = fma(r, r, q[0]); }
+    }
+    block_sum<1>(q, lds);
+    if (threadIdx.x == 0) part[blk] = q[0];
+}
+
+// ---- the vector kernels of the Newton polish ----
+// rhs = -g, g = (m o x - M x_bar) / dt^2 - f on the free rows (0 on held vertices); block partials of |g|^2 (k_stat_final sums them)
+__global__ __launch_bounds__(256) void k_nw_grad(int nv, const double *__restrict__ x, const double *__restrict__ m, const double *__restrict__ Mxbar,
+                                                 const double *__restrict__ f, double idt2, const int *__restrict__ pin, double *__restrict__ rhs,
+                                                 double *__restrict__ part) {
+    __shared__ double lds[4];
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[1] = {0.0};
+    if (v < nv) {
+        const bool held = pin[v] != 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            const double g = held ? 0.0 : fma(m[i], x[i], -Mxbar[i]) * idt2 - f[i];
+            rhs[i] = -g;
+            q[0] = fma(g, g, q[0]);
+        }
+    }
+    block_sum<1>(q, lds);
+    if (threadIdx.x == 0) part[blk] = q[0];
+}
+// block partials of g . delta (g = -rhs): the slope of the line search
+__global__ __launch_bounds__(256) void k_nw_slope(int nv, const double *__restrict__ rhs, const double *__restrict__ delta, double *__restrict__ part) {
+    __shared__ double lds[4];
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[1] = {0.0};
+    if (v < nv) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; q[0] = fma(-rhs[i], delta[i], q[0]); }
+    }
+    block_sum<1>(q, lds);
+    if (threadIdx.x == 0) part[blk] = q[0];
+}
+// out = x + t delta; v_out = v + (t / dt) delta when v is given (the accepted step: x and out may be the same array)
+__global__ __launch_bounds__(256) void k_nw_axpy(int n3, double t, double t_dt, const double *__restrict__ delta, const double *x, double *out, double *v) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n3) return;
+    out[i] = fma(t, delta[i], x[i]);
+    if (v) v[i] = fma(t_dt, delta[i], v[i]);
+}
+
+} // namespace admm_k

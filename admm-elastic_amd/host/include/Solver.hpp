@@ -115,6 +115,17 @@ public:
     // K(x) d + shift (m o d), K = d2E/dx2 = -d forces / dx the exact tangent stiffness of that energy at x, m the nodal masses
     // (admm_hip_stiffness_apply); shift = 1 / dt^2: the Jacobian of the implicit-Euler residual.  Pins are not masked; after initialize()
     VecX stiffness_apply(const VecX &d, const VecX &x, double shift = 0.0);
+    // The same from the tangent frozen at x (admm_hip_stiffness_apply_ex): psd projects every element tangent to its nearest positive
+    // semi-definite one, hold_pins holds the pinned vertices (their rows are 0, d is ignored there)
+    VecX stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins);
+    // y with (K(x) + shift M) y = rhs on the free vertices: Jacobi-PCG on the device (admm_hip_tangent_solve); shift < 0 means 1 / dt^2
+    struct SolveInfo { int iterations; bool converged; double residual, rhs_norm; };
+    VecX tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info = nullptr, double shift = -1.0, bool psd = true, bool hold_pins = true,
+                       double tol = 1e-10, int max_iters = 1000);
+    // Projected Newton with a backtracking line search on the objective of the last step(), applied to its result; m_x and m_v are
+    // updated (admm_hip_newton_polish).  One record per iterate, the first is the state the step left
+    struct NewtonRecord { double objective, grad_norm, cg_iterations, step, energy; };
+    std::vector<NewtonRecord> newton_polish(int max_iters = 10, double grad_tol = 1e-8, double cg_tol = 1e-8, int cg_max = 500);
     // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)

@@ -648,6 +648,39 @@ VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift) {
     return out;
 }
 
+VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins) {
+    if (!initialized) throw std::runtime_error("Solver::stiffness_apply: initialize() first");
+    if (x.rows() != m_x.rows() || d.rows() != m_x.rows()) throw std::runtime_error("Solver::stiffness_apply: x and d must hold three values per node");
+    VecX out(m_x.rows());
+    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0);
+    check(admm_hip_stiffness_apply_ex((admm_hip_ctx *)m_ctx, x.data(), 1, d.data(), shift, flags, out.data()), "Solver::stiffness_apply");
+    return out;
+}
+
+VecX Solver::tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info, double shift, bool psd, bool hold_pins, double tol, int max_iters) {
+    if (!initialized) throw std::runtime_error("Solver::tangent_solve: initialize() first");
+    if (x.rows() != m_x.rows() || rhs.rows() != m_x.rows()) throw std::runtime_error("Solver::tangent_solve: x and rhs must hold three values per node");
+    VecX y(m_x.rows());
+    double i4[4] = {0.0, 0.0, 0.0, 0.0};
+    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0);
+    if (shift < 0.0) shift = 1.0 / (m_settings.timestep_s * m_settings.timestep_s);
+    check(admm_hip_tangent_solve((admm_hip_ctx *)m_ctx, x.data(), rhs.data(), shift, flags, tol, (int32_t)max_iters, y.data(), i4), "Solver::tangent_solve");
+    if (info) { info->iterations = (int)i4[0]; info->converged = i4[1] != 0.0; info->residual = i4[2]; info->rhs_norm = i4[3]; }
+    return y;
+}
+
+std::vector<Solver::NewtonRecord> Solver::newton_polish(int max_iters, double grad_tol, double cg_tol, int cg_max) {
+    if (!initialized) throw std::runtime_error("Solver::newton_polish: initialize() first");
+    admm_hip_ctx *ctx = (admm_hip_ctx *)m_ctx;
+    static_assert(sizeof(NewtonRecord) == 5 * sizeof(double), "NewtonRecord is the 5 doubles of admm_hip_newton_polish");
+    std::vector<NewtonRecord> rec((size_t)std::max(0, max_iters) + 1);
+    int32_t n = 0;
+    check(admm_hip_newton_polish(ctx, (int32_t)max_iters, grad_tol, cg_tol, (int32_t)cg_max, (int32_t)rec.size(), &n, &rec[0].objective), "Solver::newton_polish");
+    rec.resize(std::min((size_t)std::max(0, (int)n), rec.size()));
+    check(admm_hip_get_state(ctx, m_x.data(), m_v.data()), "Solver::newton_polish");
+    return rec;
+}
+
 std::vector<Solver::TetStress> Solver::stress(const VecX &x) {
     if (!initialized) throw std::runtime_error("Solver::stress: initialize() first");
     if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::stress: x must hold three values per node");

@@ -639,6 +639,55 @@ class Solver:
         check(lib().admm_hip_stiffness_apply(self._ctx, dptr(xc), 1 if dc.ndim == 2 else dc.shape[0], dptr(dc), float(shift), dptr(out)))
         return out
 
+    def stiffness_apply_ex(self, d, x=None, shift=0.0, psd=False, hold_pins=False):
+        """admm_hip_stiffness_apply_ex: stiffness_apply from the tangent FROZEN at x (csrc/newton.hpp: one setup pass with the SVD, then
+        one pass per direction).  psd replaces every element tangent by its nearest positive semi-definite one (an element that is
+        positive semi-definite already keeps its bits); hold_pins holds the pinned vertices (the rule of `stationarity`): their rows of
+        the result are 0 and d is ignored there.  With neither it is stiffness_apply in another summation order.  Shapes, sign, limits
+        and reproducibility as there.  Single-GPU contexts."""
+        self._need_ctx()
+        xc = self._state_arg(x, "stiffness_apply_ex")
+        dc = f64(d).copy()
+        nv = self.m_x.size // 3
+        if dc.ndim not in (2, 3) or dc.shape[-2:] != (nv, 3) or (dc.ndim == 3 and dc.shape[0] < 1):
+            raise ValueError("stiffness_apply_ex: d must be [n_verts, 3] or [k, n_verts, 3]")
+        out = np.zeros(dc.shape)
+        check(lib().admm_hip_stiffness_apply_ex(self._ctx, dptr(xc), 1 if dc.ndim == 2 else dc.shape[0], dptr(dc), float(shift),
+                                                (1 if psd else 0) | (2 if hold_pins else 0), dptr(out)))
+        return out
+
+    def tangent_solve(self, rhs, x=None, shift=None, psd=True, hold_pins=True, tol=1e-10, max_iters=1000):
+        """admm_hip_tangent_solve: y with (K(x) + shift M) y = rhs on the free vertices, by Jacobi-preconditioned CG on the device
+        (matrix-free on the frozen tangent; no host synchronisation inside the solve).  shift=None means 1 / dt^2: the Hessian of the
+        implicit-Euler objective.  psd, hold_pins as in stiffness_apply_ex (held vertices: y = 0).  Returns (y [n_verts, 3], info) with
+        info = dict(iterations, converged, residual = |rhs - A y| / |rhs| of the returned y over the free rows (formed once more at the
+        end: not the recursive residual the stop test reads), rhs_norm).  With psd=False the operator can be
+        indefinite: the solve then ends with converged=False at the first p.Ap <= 0 and returns the iterate before it."""
+        self._need_ctx()
+        xc = self._state_arg(x, "tangent_solve")
+        rc = f64(rhs).ravel().copy()
+        if rc.size != self.m_x.size:
+            raise ValueError("tangent_solve: rhs must hold 3 values per node")
+        if shift is None:
+            shift = 1.0 / (self._settings.timestep_s ** 2)
+        y = np.zeros(rc.size); info = np.zeros(4)
+        check(lib().admm_hip_tangent_solve(self._ctx, dptr(xc), dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0), float(tol),
+                                           int(max_iters), dptr(y), dptr(info)))
+        return y.reshape(-1, 3), dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]))
+
+    def newton_polish(self, max_iters=10, grad_tol=1e-8, cg_tol=1e-8, cg_max=500):
+        """admm_hip_newton_polish: projected Newton with a backtracking line search on the objective of the last step, applied to the
+        device-resident state; m_x and m_v are downloaded afterwards.  Returns one dict per iterate (the first is the state the step left):
+        objective, grad_norm (|g| over the free rows: the `stationarity` of that iterate), cg_iterations and step (of the Newton step
+        taken from that iterate; 0, 0.0: none), energy.  grad_tol is absolute, in the units of a force.  Refused for multi-GPU contexts,
+        contexts with colliders, strain-limited triangles or slide pins, and before the first step."""
+        self._need_ctx()
+        cap = int(max_iters) + 1
+        rec = np.zeros((cap, 5)); n = C.c_int32(0)
+        check(lib().admm_hip_newton_polish(self._ctx, int(max_iters), float(grad_tol), float(cg_tol), int(cg_max), cap, C.byref(n), dptr(rec)))
+        self.download()
+        return [dict(objective=r[0], grad_norm=r[1], cg_iterations=int(r[2]), step=r[3], energy=r[4]) for r in rec[:min(n.value, cap)]]
+
     def residuals(self, x, z, z_prev):
         """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""
         self._need_ctx()

@@ -308,6 +308,43 @@ int admm_hip_stress(admm_hip_ctx *ctx, const double *x, double *out13);  /* [13 
  * bit-identical to the same direction applied alone, and from run to run.  Single-GPU contexts only.  Synchronises the stream. */
 int admm_hip_stiffness_apply(admm_hip_ctx *ctx, const double *x, int32_t n_vec, const double *d, double shift, double *out);
 
+/* The same operator from a tangent FROZEN at x (csrc/newton.hpp): one setup pass runs the SVD and the coefficients of every tet once and
+ * stores a 30-double frame, every direction is then one frozen pass.  flags: ADMM_HIP_TANGENT_PSD -- every element tangent is replaced by
+ * its Frobenius-nearest positive semi-definite one (tets: the twist and flip eigenvalues clamped at 0, the 3x3 block of the stretches by
+ * its positive part; triangles: the twist and the two out-of-plane eigenvalues; hinges are positive semi-definite already); an element that
+ * is positive semi-definite keeps its bits (eigenvalues above -2^-44 of the element's largest coefficient count as zero: the rotation
+ * modes of an element at rest).  ADMM_HIP_TANGENT_HOLD_PINS -- pinned vertices (the rule of `stationarity`: active pin terms, or the pins
+ * of the sweeps under linsolver 1) are held: their rows of out are 0 and d is ignored there.  flags = 0 is admm_hip_stiffness_apply in
+ * another summation order (measured: <= 2e-16 of its per-vertex scale).  Bit-reproducible; a column does not depend on the others.
+ * Single-GPU contexts only.  Synchronises the stream. */
+#define ADMM_HIP_TANGENT_PSD 1
+#define ADMM_HIP_TANGENT_HOLD_PINS 2
+int admm_hip_stiffness_apply_ex(admm_hip_ctx *ctx, const double *x, int32_t n_vec, const double *d, double shift, int32_t flags, double *out);
+
+/* Solves (K(x) + shift M) y = rhs on the free vertices by Jacobi-preconditioned CG, matrix-free on the frozen tangent, on the context's
+ * stream.  x as above; rhs and y [3 n_verts] host; flags as above (on held vertices y = 0 and rhs is ignored).  Stops at
+ * |r| <= tol |rhs| (2-norms over the free rows, r the recursive residual) or after max_iters iterations.  alpha, beta and the stop
+ * decision live on the device: iterations are enqueued in chunks of 8 (four launches each), the host reads one pinned word per chunk
+ * and synchronises once at the end; no grid barrier, no persistent kernel, no floating-point atomics: bit-reproducible.
+ * info4 = {iterations, converged (0 / 1), |rhs - A y| / |rhs| of the returned y, |rhs|}: the residual is formed once more at the end (one
+ * more application); the recursive one of the stop test drifts from it by about eps cond(A) |rhs|, 7e-4 of a residual of 1e-12 |rhs|.  Without ADMM_HIP_TANGENT_PSD the operator can be indefinite and CG can
+ * break down: the solve then ends with converged = 0 at the first p.Ap <= 0 or non-finite scalar and returns the iterate before it.
+ * Single-GPU contexts only (tabulated-spline tets need the context's table, which admm_hip_create already demands). */
+int admm_hip_tangent_solve(admm_hip_ctx *ctx, const double *x, const double *rhs, double shift, int32_t flags, double tol, int32_t max_iters,
+                           double *y, double *info4);
+
+/* Projected Newton on the objective of the LAST step, Phi(x) = |x - x_bar|_M^2 / (2 dt^2) + E(x) (what monitor mode 2 sums), applied to
+ * the device-resident state: per iteration g = (m o x - M x_bar) / dt^2 - f(x) with the pinned rows zeroed; stop at |g| <= grad_tol;
+ * else (K_psd(x) + M / dt^2) delta = -g by admm_hip_tangent_solve (both flags, cg_tol, cg_max), Armijo backtracking on Phi (c = 1e-4,
+ * halving, at most 10 trials, a non-finite Phi is a rejection); x += t delta, v += t delta / dt.  Without an accepted trial the polish
+ * ends with the last accepted iterate.  At most max_newton steps.  records [cap][5], *n of them written (one per iterate, the first is
+ * the state the step left): Phi, |g_free|, the CG iterations and the accepted step length of the step taken FROM that iterate (0, 0: none
+ * -- converged, max_newton reached or no trial accepted), the elastic energy E.  One host synchronisation per Newton iteration and per
+ * line-search trial, none inside a solve.  Refused (ADMM_HIP_ERR_ARG): multi-GPU contexts, contexts with colliders, with strain-limited
+ * triangles (a limit min > 0 or max < 100) or with slide pins, and a state no step has run on (admm_hip_set_state resets that). */
+int admm_hip_newton_polish(admm_hip_ctx *ctx, int32_t max_newton, double grad_tol, double cg_tol, int32_t cg_max, int32_t cap, int32_t *n,
+                           double *records);
+
 /* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
  * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
 int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
