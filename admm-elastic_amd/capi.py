@@ -102,6 +102,8 @@ SYMBOLS = [
     ("admm_hip_set_admm_stop", C.c_int, [C.c_void_p, C.c_double, C.c_int32]),
     ("admm_hip_get_admm_stop", C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_int_p, c_int_p, c_int_p]),
     ("admm_host_admm_stop_test", C.c_int, [c_double_p, C.c_double]),
+    ("admm_hip_set_anderson", C.c_int, [C.c_void_p, C.c_int32]),
+    ("admm_hip_get_anderson", C.c_int, [C.c_void_p, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_set_solver_params", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     ("admm_hip_get_solver_params", C.c_int, [C.c_void_p, C.c_int32, c_int_p, c_double_p, c_double_p]),
     ("admm_hip_set_soft_modes", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),

@@ -26,6 +26,7 @@
 #include "forces.hpp"
 #include "tangent.hpp"
 #include "newton.hpp"
+#include "anderson.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
 #include "gs_persist.hpp"
@@ -411,6 +412,12 @@ struct admm_hip_ctx {
     int *nw_hstop = nullptr;      // pinned: the stop word as the host reads it between chunks
     hipEvent_t nw_ev[2] = {nullptr, nullptr};
     bool nw_ready = false;
+    // Anderson acceleration of the ADMM loop (anderson.hpp; admm_hip_set_anderson): buffers of their own, allocated by the first step that
+    // runs with a window, and again by a step with a larger one
+    int aa_window = 0, aa_slots = 0, aa_n = 0;      // window in effect from the next step; ring slots allocated; records the last step wrote
+    bool aa_on = false;                             // while step_impl enqueues an accelerated step
+    DevBuf<double> aa_hg, aa_hf, aa_scopy, aa_part, aa_rec;      // the ring [slots][N] twice, the copy [N], block partials [kAaQ][blocks], records [admm_iters][kAaRec]
+    DevBuf<AaCtl> aa_ctl;
     bool tri_limited = false;     // a triangle carries a strain limit that can act (min > 0 or max < 100)
     bool xbar_of_state = false;   // Mxbar is the last step's and x its result (no set_state since)
 
@@ -588,7 +595,8 @@ void launch_monitor(admm_hip_ctx *c, const MonArgs &a, double *out, int s = -1) 
     const int nb = std::max(1, a.nb_p + (a.m ? blocks_for(a.n3) : 0));
     hipLaunchKernelGGL((k_monitor<RES, ENERGY, false, STOP>), dim3(nb), dim3(256), 0, c->stream, a);
     if (s < 0) hipLaunchKernelGGL(k_mon_final, dim3(1), dim3(256), 0, c->stream, a.part, nb, out);
-    else hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig);
+    else hipLaunchKernelGGL(k_mon_decide, dim3(1), dim3(256), 0, c->stream, a.part, nb, out, c->stop_tol, c->stop_min, s, c->counters.p, c->d_sig,
+                            c->aa_on ? (const int *)&c->aa_ctl.p->mode : nullptr);
 }
 // z_prev <- D x: the reference's curr_z = D m_x at step entry (src/Solver.cpp:70)
 void launch_monitor_init(admm_hip_ctx *c, const double *x) {
@@ -608,6 +616,62 @@ void launch_monitor_step(admm_hip_ctx *c, int s, bool decide = false) {
         if (c->mon_mode >= 2) launch_monitor<true, true>(c, a, out, sd);
         else launch_monitor<true, false>(c, a, out, sd);
     }
+}
+
+// ---- Anderson acceleration of the ADMM loop (anderson.hpp) ----
+// the state (curr, t_u, r_u, h_u, pin_u) as the three phases walk it: families present, their blocks, their place in a history vector
+AaArgs aa_args(const admm_hip_ctx *c) {
+    AaArgs a{};
+    const double idt2 = 1.0 / (c->dt * c->dt);
+    int nb = 0; long long off = 0;
+    auto add = [&](double *live, const double *sc, double wk, int n, int nc, int stride_c, int stride_e, long long len) {
+        if (n <= 0) return;
+        AaSeg &g = a.seg[a.nseg++];
+        g.live = live; g.sc = sc; g.wk = wk; g.off = off; g.n = n; g.nc = nc; g.stride_c = stride_c; g.stride_e = stride_e; g.blk0 = nb;
+        nb += blocks_for(n); off += len;
+    };
+    add(c->curr.p, c->m.p, idt2, c->n3, 1, 0, 1, c->n3);
+    add(c->t_u.p, c->t_sc.p, idt2, c->nt, 9, c->ldt, 1, 9LL * c->ldt);
+    add(c->r_u.p, c->r_sc.p, idt2, c->ntri, 6, c->ldr, 1, 6LL * c->ldr);
+    add(c->h_u.p, c->h_sc.p, idt2, c->nbend, 3, c->ldb, 1, 3LL * c->ldb);
+    add(c->pin_u.p, nullptr, c->pin_weight * c->pin_weight, c->npin_terms, 3, 1, 3, 3LL * c->npin_terms);
+    a.nb = std::max(1, nb); a.N = std::max(1LL, off); a.S = c->aa_window + 1;
+    a.hg = c->aa_hg.p; a.hf = c->aa_hf.p; a.scopy = c->aa_scopy.p; a.ctl = c->aa_ctl.p; a.part = c->aa_part.p; a.stop = c->stop_dev;
+    return a;
+}
+// buffers, allocated by the first step that needs them (and again for a larger window or more iterations)
+hipError_t aa_ensure(admm_hip_ctx *c, int iters) {
+    hipError_t e;
+    const AaArgs a = aa_args(c);
+    if (c->aa_slots < a.S) {
+        if ((e = c->aa_hg.alloc((size_t)a.S * a.N)) != hipSuccess) return e;
+        if ((e = c->aa_hf.alloc((size_t)a.S * a.N)) != hipSuccess) return e;
+        c->aa_slots = a.S;
+    }
+    if (!c->aa_scopy.p && (e = c->aa_scopy.alloc((size_t)a.N)) != hipSuccess) return e;
+    if (!c->aa_part.p && (e = c->aa_part.alloc((size_t)kAaQ * a.nb)) != hipSuccess) return e;
+    if (!c->aa_ctl.p) {
+        if ((e = c->aa_ctl.alloc(1)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c->aa_ctl.p, 0, sizeof(AaCtl), c->stream)) != hipSuccess) return e;
+    }
+    if (c->aa_rec.n < (size_t)kAaRec * std::max(1, iters) && (e = c->aa_rec.alloc((size_t)kAaRec * std::max(1, iters))) != hipSuccess) return e;
+    return hipSuccess;
+}
+void launch_aa_init(admm_hip_ctx *c) {
+    const AaArgs a = aa_args(c);
+    hipLaunchKernelGGL(k_aa_init, dim3(a.nb), dim3(256), 0, c->stream, a);
+}
+// after the global solve of ADMM iteration s: the record pass and the decision
+void launch_aa_record(admm_hip_ctx *c, int s) {
+    AaArgs a = aa_args(c);
+    a.rec = c->aa_rec.p + (size_t)kAaRec * s;
+    hipLaunchKernelGGL(k_aa_record, dim3(a.nb), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_aa_solve, dim3(1), dim3(256), 0, c->stream, a);
+}
+void launch_aa_apply(admm_hip_ctx *c, bool last) {
+    AaArgs a = aa_args(c);
+    a.last = last ? 1 : 0;
+    hipLaunchKernelGGL(k_aa_apply, dim3(a.nb), dim3(256), 0, c->stream, a);
 }
 
 // ---- internal forces, stress, stationarity (forces.hpp) ----
@@ -3278,6 +3342,11 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         launch_monitor_init(c, c->x.p);
         c->mon_n = admm_iters;
     }
+    // Anderson acceleration (admm_hip_set_anderson): three more launches behind every global solve, the decisions on the device
+    struct AaOn { admm_hip_ctx *c; ~AaOn() { c->aa_on = false; } } aa_on_guard{c};
+    c->aa_on = c->aa_window > 0 && admm_iters > 0;
+    c->aa_n = 0;
+    if (c->aa_on) { HIP_TRY(aa_ensure(c, admm_iters)); c->aa_n = admm_iters; }
     const bool stat = mon && c->mon_mode == 3;      // (mode 3: mode 2 plus the stationarity residual, forces.hpp)
     c->mon_stat_n = 0;
     if (stat) {
@@ -3321,6 +3390,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
     if (c->ntri) HIP_TRY(hipMemsetAsync(c->r_u.p, 0, c->r_u.n * sizeof(double), st));
     if (c->nbend) HIP_TRY(hipMemsetAsync(c->h_u.p, 0, c->h_u.n * sizeof(double), st));
     if (c->npin_terms) HIP_TRY(hipMemsetAsync(c->pin_u.p, 0, c->pin_u.n * sizeof(double), st));
+    if (c->aa_on) launch_aa_init(c);      // s_0 = (x_bar, 0), the ring empty: nothing carries over from the step before
     int n_launched = 0;      // iterations enqueued (all of them, unless the host has seen the stop)
     for (int s = 0; s < admm_iters; ++s) {
         if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * s], st));
@@ -3347,6 +3417,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         if (grc == -2) return kStepAborted;       // a grid barrier timed out in a column solve of UzawaCG: same recovery as any aborted on-chip solve
         if (grc) return fail(ADMM_HIP_ERR_DEVICE, "PCG: the device stopped signalling progress");
         if (stat) launch_stationarity(c, s);
+        if (c->aa_on) launch_aa_record(c, s);             // F_k, the safeguard, theta: before the monitor's decision, which a rejection vetoes
         if (mon) launch_monitor_step(c, s, stopping);     // x = x^{s+1}, z = z^{s+1}, z_prev = z^s
         if (stopping && !stop_on_dev) {      // the host decides: wait for the decision, read its pinned copy
             HIP_TRY(hipEventRecord(c->ev_stop, st));
@@ -3354,6 +3425,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
             if (c->h_sig[kSigAbort]) break;      // (a persistent launch gave up: seen again below)
             if (((volatile int *)c->h_sig)[kSigAdmmStop]) break;
         }
+        if (c->aa_on) launch_aa_apply(c, s + 1 == admm_iters);      // s_{k+1} (behind the stop: a no-op, the step's x is the solve's output)
     }
     c->timing = false;
     if (timed) HIP_TRY(hipEventRecord(c->ev_phase[3 * n_launched], st));
@@ -3372,6 +3444,7 @@ static int step_impl(admm_hip_ctx *c, int32_t admm_iters, double gravity, admm_h
         n_exec = std::min(n_launched, std::max(1, (int)((volatile int *)c->h_sig)[kSigAdmmIters]));
         c->stop_last = n_exec; c->stop_on_dev = stop_on_dev ? 1 : 0;
         c->mon_n = n_exec;
+        if (c->aa_on) c->aa_n = n_exec;
         if (c->rc_iter > n_exec) c->rc_iter = n_exec;      // the pairs this frame really wrote: next frame's rc_prev_valid, then rc_prev2_valid
         if (stop_on_dev) {      // every skipped iteration took one solve number (and, k_pcg2, one place in the verification sample): give them back
             const int skipped = n_launched - n_exec;
@@ -4045,6 +4118,38 @@ int admm_hip_get_admm_stop(admm_hip_ctx *c, double *tol, int32_t *min_iters, int
     }
     if (last_iters) *last_iters = c->stop_last;
     if (on_device) *on_device = c->stop_on_dev;
+    return ADMM_HIP_OK;
+}
+
+// ---- Anderson acceleration of the ADMM loop (anderson.hpp; step_impl) ----
+int admm_hip_set_anderson(admm_hip_ctx *c, int32_t window) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "set_anderson: NULL context");
+    if (window < 0 || window > kAaMax) return fail(ADMM_HIP_ERR_ARG, "set_anderson: window must be 0 (off) .. 8");
+    if (window > 0) {
+        if (!monitor_allowed(c)) return fail(ADMM_HIP_ERR_ARG, "set_anderson: single-GPU contexts only (world_size > 1, a communicator or a caller all-reduce splits the state over ranks)");
+        if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "set_anderson: the context has colliders (obstacles or dynamic meshes); contact is not part of the accelerated fixed-point map");
+        if (c->linsolver != 0) return fail(ADMM_HIP_ERR_ARG, "set_anderson: linsolver 1 and 2 are not supported (their inexact sweeps and multiplier updates are another fixed-point map); use linsolver 0");
+    }
+    c->aa_window = window;
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_get_anderson(admm_hip_ctx *c, int32_t cap, int32_t *n, double *records) {
+    if (!c || !n || cap < 0 || (cap > 0 && !records)) return fail(ADMM_HIP_ERR_ARG, "get_anderson: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = settle(c)) return rc;      // (a replayed step has rewritten its records)
+    *n = c->aa_n;
+    const int m = std::min((int)cap, c->aa_n);
+    if (m <= 0) return ADMM_HIP_OK;
+    std::vector<double> h((size_t)kAaRec * m);
+    HIP_TRY(hipMemcpy(h.data(), c->aa_rec.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < m; ++s) {
+        const double *q = h.data() + (size_t)kAaRec * s;
+        double *r = records + (size_t)kAaRec * s;
+        for (int i = 0; i < kAaRec; ++i) r[i] = q[i];
+        r[3] = std::sqrt(q[3]);
+    }
     return ADMM_HIP_OK;
 }
 

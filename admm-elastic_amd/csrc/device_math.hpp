@@ -1293,4 +1293,49 @@ __device__ __forceinline__ void tri_tangent_apply_psd(const double *Q, const dou
     tri_tangent_apply(Q, Sp, tw, dF, out);
 }
 
+// ---- Anderson acceleration (anderson.hpp): the small regularised solve ----
+// theta = (H + kAaReg (tr H / n) I)^-1 b for the Gram matrix H [n][n] (n <= kAaMax; row-major with row stride kAaMax, the lower
+// triangle is read) by Cholesky in FP64.  false -- the caller clears its history -- on a pivot that is not positive and finite or a
+// theta that is not finite; theta is then zero.  work [kAaWork]: the factor and the intermediate vector (the device passes LDS: arrays
+// indexed by a run-time n would otherwise live in scratch, a memory round trip per access of one serial thread).
+constexpr int kAaMax = 8;
+constexpr int kAaWork = kAaMax * kAaMax + kAaMax;
+constexpr double kAaReg = 1e-10;
+__device__ __forceinline__ bool aa_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (false for NaN)
+__device__ __forceinline__ bool aa_small_solve(int n, const double *H, const double *b, double *theta, double *work) {
+    double *L = work, *y = work + kAaMax * kAaMax;
+    for (int i = 0; i < kAaMax; ++i) theta[i] = 0.0;
+    if (n < 1 || n > kAaMax) return false;
+    double tr = 0.0;
+    for (int i = 0; i < n; ++i) tr += H[i * kAaMax + i];
+    const double reg = kAaReg * (tr / (double)n);
+    bool ok = true;
+    for (int j = 0; j < n && ok; ++j) {
+        double d = H[j * kAaMax + j] + reg;
+        for (int k = 0; k < j; ++k) d = fma(-L[j * kAaMax + k], L[j * kAaMax + k], d);
+        if (!(d > 0.0) || !aa_finite(d)) { ok = false; break; }
+        const double l = sqrt(d);
+        L[j * kAaMax + j] = l;
+        for (int i = j + 1; i < n; ++i) {
+            double s = H[i * kAaMax + j];
+            for (int k = 0; k < j; ++k) s = fma(-L[i * kAaMax + k], L[j * kAaMax + k], s);
+            L[i * kAaMax + j] = s / l;
+        }
+    }
+    if (!ok) return false;
+    for (int i = 0; i < n; ++i) {
+        double s = b[i];
+        for (int k = 0; k < i; ++k) s = fma(-L[i * kAaMax + k], y[k], s);
+        y[i] = s / L[i * kAaMax + i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double s = y[i];
+        for (int k = i + 1; k < n; ++k) s = fma(-L[k * kAaMax + i], theta[k], s);
+        theta[i] = s / L[i * kAaMax + i];
+    }
+    for (int i = 0; i < n; ++i) ok = ok && aa_finite(theta[i]);
+    if (!ok) for (int i = 0; i < kAaMax; ++i) theta[i] = 0.0;
+    return ok;
+}
+
 } // namespace admm_dev

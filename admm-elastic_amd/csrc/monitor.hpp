@@ -237,8 +237,10 @@ __global__ __launch_bounds__(256) void k_mon_final(const double *__restrict__ pa
 // without the feature -- then the decision on it.  s = the ADMM iteration.  A set stop word makes the launch a no-op like every other
 // kernel of the loop.  Thread 0 writes, with ordinary vector stores: the executed count (cnt[kCntAdmmIters], sig[kSigAdmmIters]) and,
 // when iteration s is the last, the stop word (cnt[kCntAdmmStop], sig[kSigAdmmStop]); sig is pinned host memory, for the host.
+// veto (Anderson acceleration, anderson.hpp: AaCtl::mode of this iteration, written by the completed k_aa_solve; else nullptr): 2 = the
+// evaluation was rejected -- its record is written, but it cannot end the step.
 __global__ __launch_bounds__(256) void k_mon_decide(const double *__restrict__ part, int nb, double *__restrict__ out, double tol, int min_iters,
-                                                    int s, int *__restrict__ cnt, int *__restrict__ sig) {
+                                                    int s, int *__restrict__ cnt, int *__restrict__ sig, const int *__restrict__ veto) {
     __shared__ double lds[4 * kMonQ];
     if (cnt[kCntAdmmStop]) return;
     double q[kMonQ];
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(256) void k_mon_decide(const double *__restrict__ p
 #pragma unroll
         for (int i = 0; i < kMonQ; ++i) out[i] = q[i];
         const double rec[4] = {sqrt(q[0]), sqrt(q[1]), sqrt(q[2]), sqrt(q[3])};      // (as admm_hip_get_monitor converts the sums)
-        const bool stop = s + 1 >= min_iters && admm_stop_test(rec, tol);
+        const bool stop = s + 1 >= min_iters && admm_stop_test(rec, tol) && !(veto && *veto == 2);
         cnt[kCntAdmmIters] = s + 1;
         __hip_atomic_store(sig + kSigAdmmIters, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (stop) {

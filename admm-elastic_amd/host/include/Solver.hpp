@@ -20,7 +20,7 @@ namespace solver_detail {
 
 // Solver::Settings (src/Solver.hpp:39-50): command-line switches in the comments
 struct SolverSettings {
-    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0), monitor(0), admm_tol(0.0), admm_min_iters(1) {}
+    SolverSettings() : timestep_s(1.0 / 24.0), verbose(1), admm_iters(10), gravity(-9.8), linsolver(0), constraint_w(-1), soft_modes(0), monitor(0), admm_tol(0.0), admm_min_iters(1), anderson(0) {}
     double timestep_s;   // -dt
     int verbose;         // -v
     int admm_iters;      // -it
@@ -34,6 +34,7 @@ struct SolverSettings {
     double admm_tol;     // -tol (GPU build, appended) early exit of a step's ADMM loop (admm_hip_set_admm_stop): the loop stops after the iteration whose
                          //      residuals meet  |W(Dx - z)| <= tol max(|W z|, |W D x|)  and  |W(z - z_prev)| <= tol |W z|; 0 = off
     int admm_min_iters;  //      (GPU build, appended) ... but not before this many iterations (>= 1)
+    int anderson;        // -aa  (GPU build, appended) Anderson acceleration of a step's ADMM loop (admm_hip_set_anderson): window 0 (off) .. 8
     void help();
     bool parse_args(int argc, char **argv);   // true when help() was printed
 };
@@ -52,6 +53,10 @@ struct SolverRuntimeData {
 // 1/(2 dt^2) |x - x_bar|^2_M and their sum, the objective (the last three 0 with monitor = 1); stationarity = |(M (x - x_bar) / dt^2 +
 // grad E(x))_free| over the nodes without an active pin (monitor = 3, else 0).
 struct AdmmRecord { double primal, dz, wz, wdx, energy, inertia, objective, stationarity; };
+// One ADMM iteration of the last step as the Anderson acceleration decided it (Settings::anderson; include/admm_hip.h: admm_hip_get_anderson):
+// the evaluation was accepted; it started from an extrapolated state; entries in the ring after it (0 after a rejection or a cleared
+// ring); |F_k|; theta (zeros beyond entries - 1).
+struct AndersonRecord { bool accepted, accelerated; int entries; double resid, theta[8]; };
 // Stress of one tet (include/admm_hip.h: admm_hip_stress): first Piola-Kirchhoff stress P = dpsi/dF column-major, the signed stretches, the von
 // Mises stress of the Cauchy stress P F^T / J (at J -> 0: what the arithmetic gives)
 struct TetStress { double P[9], stretches[3], von_mises; };
@@ -62,6 +67,7 @@ class Solver {
 public:
     typedef solver_detail::SolverSettings Settings;
     typedef solver_detail::SolverRuntimeData RuntimeData;
+    typedef solver_detail::AndersonRecord AndersonRecord;
     typedef solver_detail::AdmmRecord AdmmRecord;
     typedef solver_detail::TetStress TetStress;
 
@@ -130,6 +136,10 @@ public:
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)
     void set_admm_stop(double tol, int min_iters = 1);
+    // admm_hip_set_anderson after initialize(): in effect from the next step (window 0: off)
+    void set_anderson(int window);
+    // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::anderson = 0
+    std::vector<AndersonRecord> anderson_history();
     void *context() { return m_ctx; }                             // the admm_hip_ctx behind this solver (include/admm_hip.h), for the C ABI's extras
 
 protected:

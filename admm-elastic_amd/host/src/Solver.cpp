@@ -585,6 +585,7 @@ bool Solver::initialize(const Settings &settings_) { // src/Solver.cpp:167-261
     if (m_settings.monitor) check(admm_hip_set_monitor(ctx, (int32_t)m_settings.monitor), "Solver::initialize (monitor)");
     if (m_settings.admm_tol != 0.0 || m_settings.admm_min_iters != 1)
         check(admm_hip_set_admm_stop(ctx, m_settings.admm_tol, (int32_t)m_settings.admm_min_iters), "Solver::initialize (admm_tol)");
+    if (m_settings.anderson) check(admm_hip_set_anderson(ctx, (int32_t)m_settings.anderson), "Solver::initialize (anderson)");
     m_history.clear();
     if (m_settings.verbose >= 1) printf("%d nodes, %d energy terms\n", (int)m_x.size() / 3, (int)energyterms.size());
     initialized = true;
@@ -622,6 +623,30 @@ void Solver::set_admm_stop(double tol, int min_iters) {
     if (!initialized) throw std::runtime_error("Solver::set_admm_stop: initialize() first");
     check(admm_hip_set_admm_stop((admm_hip_ctx *)m_ctx, tol, (int32_t)min_iters), "Solver::set_admm_stop");
     m_settings.admm_tol = tol; m_settings.admm_min_iters = min_iters;
+}
+
+void Solver::set_anderson(int window) {
+    if (!initialized) throw std::runtime_error("Solver::set_anderson: initialize() first");
+    check(admm_hip_set_anderson((admm_hip_ctx *)m_ctx, (int32_t)window), "Solver::set_anderson");
+    m_settings.anderson = window;
+}
+
+std::vector<Solver::AndersonRecord> Solver::anderson_history() {
+    if (!initialized) throw std::runtime_error("Solver::anderson_history: initialize() first");
+    admm_hip_ctx *ctx = (admm_hip_ctx *)m_ctx;
+    int32_t n = 0;
+    check(admm_hip_get_anderson(ctx, 0, &n, nullptr), "Solver::anderson_history");
+    std::vector<double> rec(12 * (size_t)std::max(1, (int)n));
+    if (n > 0) check(admm_hip_get_anderson(ctx, n, &n, rec.data()), "Solver::anderson_history");
+    std::vector<AndersonRecord> out;
+    for (int s = 0; s < (int)n; ++s) {
+        const double *r = rec.data() + 12 * (size_t)s;
+        AndersonRecord a;
+        a.accepted = r[0] != 0.0; a.accelerated = r[1] != 0.0; a.entries = (int)r[2]; a.resid = r[3];
+        for (int j = 0; j < 8; ++j) a.theta[j] = r[4 + j];
+        out.push_back(a);
+    }
+    return out;
 }
 
 double Solver::energy(const VecX &x) {
@@ -715,6 +740,7 @@ const Switch kSwitches[] = {
     {"-sm", nullptr, &Solver::Settings::soft_modes, "soft modes of the PCG's end projection (GPU build; 0 = off) "},
     {"-tol", &Solver::Settings::admm_tol, nullptr, "early exit of the admm loop on its residuals (GPU build; 0 = off) "},
     {"-monitor", nullptr, &Solver::Settings::monitor, "ADMM monitor (GPU build; 0 = off, 1 residuals, 2 + objective, 3 + stationarity) "},
+    {"-aa", nullptr, &Solver::Settings::anderson, "Anderson acceleration of the admm loop (GPU build; window 0 = off .. 8) "},
 };
 bool wants_help(const char *a) { const std::string s(a); return s == "-help" || s == "--help" || s == "-h"; }
 } // namespace

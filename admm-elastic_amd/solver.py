@@ -67,6 +67,7 @@ class Settings:
         self.monitor = 0             # GPU build: ADMM monitor of every step (admm_hip_set_monitor): 0 off, 1 residuals, 2 residuals + objective, 3 = 2 + stationarity
         self.admm_tol = 0.0          # GPU build: early exit of a step's ADMM loop on its residuals (admm_hip_set_admm_stop); 0 = off
         self.admm_min_iters = 1      #            ... but not before this many iterations
+        self.anderson = 0            # GPU build: Anderson acceleration of a step's ADMM loop (admm_hip_set_anderson): window 0 (off) .. 8
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown setting " + k)
@@ -488,6 +489,8 @@ class Solver:
             check(lib().admm_hip_set_monitor(ctx, int(s.monitor)))
         if s.admm_tol != 0.0 or s.admm_min_iters != 1:
             check(lib().admm_hip_set_admm_stop(ctx, float(s.admm_tol), int(s.admm_min_iters)))
+        if s.anderson:
+            check(lib().admm_hip_set_anderson(ctx, int(s.anderson)))
         self.initialized = True
         return True
 
@@ -734,6 +737,27 @@ class Solver:
             check(lib().admm_hip_get_monitor(self._ctx, n.value, C.byref(n), dptr(rec)))
         keys = ("primal", "dz", "wz", "wdx", "energy", "inertia", "objective", "stationarity")
         return {k: rec[:, i].copy() for i, k in enumerate(keys)}
+
+    def set_anderson(self, window):
+        """admm_hip_set_anderson: Anderson acceleration of a step's ADMM loop over the newest window + 1 accepted evaluations of the
+        fixed-point map (x, u) -> (x after the global solve, u after the local step), safeguarded on the residual; window 0 switches it
+        off, 8 is the largest.  In effect from the next step.  linsolver 0, single-GPU contexts without colliders."""
+        self._need_ctx()
+        check(lib().admm_hip_set_anderson(self._ctx, int(window)))
+        self._settings.anderson = int(window)
+
+    def anderson_history(self):
+        """Records of the last step (admm_hip_get_anderson), one entry per executed ADMM iteration: dict of arrays accepted, accelerated
+        (the iteration started from an extrapolated state), entries (the ring after the evaluation; 0 after a rejection or a cleared
+        ring), resid = |F_k| and theta [n][8] (zeros beyond entries - 1).  Empty arrays when the step ran with the window 0."""
+        self._need_ctx()
+        n = C.c_int32(0)
+        check(lib().admm_hip_get_anderson(self._ctx, 0, C.byref(n), None))
+        rec = np.zeros((n.value, 12))
+        if n.value:
+            check(lib().admm_hip_get_anderson(self._ctx, n.value, C.byref(n), dptr(rec)))
+        return dict(accepted=rec[:, 0].astype(np.int32), accelerated=rec[:, 1].astype(np.int32), entries=rec[:, 2].astype(np.int32),
+                    resid=rec[:, 3].copy(), theta=rec[:, 4:12].copy())
 
     def set_solver_params(self, kind, max_iters=0, tol=-1.0, omega=0.0):
         """admm_hip_set_solver_params: the LinearSolver objects' public tuning members after initialize (the reference reads them on

@@ -391,6 +391,29 @@ int admm_hip_get_admm_stop(admm_hip_ctx *ctx, double *tol, int32_t *min_iters, i
  * the same inline function the device decision calls. */
 int admm_host_admm_stop_test(const double *rec8, double tol);
 
+/* ANDERSON ACCELERATION of a step's ADMM loop (Zhang, Peng, Ouyang, Deng 2019).  The fixed-point map G takes the state s = (x, u) an
+ * iteration starts from to g = (x after the global solve, u after the local step); F = g - s, measured in
+ * <a, b> = sum_v m_v / dt^2 a_x b_x + sum_rows w^2 a_u b_u.  A ring keeps the newest window + 1 accepted pairs (g_j, F_j); it is empty
+ * and r_acc = +inf at the start of EVERY step.  After the global solve of iteration k:
+ *   - s_k was extrapolated and |F_k|^2 > r_acc: the evaluation is REJECTED -- the next state is the g of the last accepted evaluation,
+ *     the ring is cleared, r_acc stays; the evaluation that follows is accepted whatever its residual;
+ *   - otherwise ACCEPTED: r_acc = |F_k|^2, (g_k, F_k) is pushed, and with p >= 2 entries theta solves
+ *     (H + 1e-10 (tr H / (p - 1)) I) theta = dF^T F_k, H = dF^T dF over the differences of consecutive entries (FP64 Cholesky);
+ *     s_{k+1} = g_k - sum_j theta_j (g_{j+1} - g_j).  A pivot that is not positive and finite or a theta that is not finite clears the
+ *     ring, s_{k+1} = g_k; so does p < 2 without clearing;
+ *   - nothing is extrapolated behind the last iteration: the step's x is the solve output of the last accepted evaluation;
+ *   - with admm_hip_set_admm_stop, a rejected evaluation cannot end the step.
+ * Every decision is taken on the device; the host enqueues three launches more per iteration and never waits.  window = 0 (default)
+ * switches it off: a step is then exactly what it was -- the same kernels, the same bits.  In effect from the next step.  Refused
+ * (ADMM_HIP_ERR_ARG): a window outside 0..8, and with window > 0 multi-GPU contexts, contexts with colliders (obstacles or dynamic meshes)
+ * and linsolver 1 and 2. */
+int admm_hip_set_anderson(admm_hip_ctx *ctx, int32_t window);
+/* Records of the LAST step, one per executed ADMM iteration k (none when it ran with window 0).  records [cap][12]: accepted (1 / 0),
+ * accelerated (s_k was an extrapolated state), entries (the ring after this evaluation: p; 0 after a rejection or a cleared ring),
+ * |F_k|, theta [8] (zeros beyond p - 1; computed and recorded at the step's last iteration too, where it is not applied).
+ * *n = iterations recorded (may exceed cap).  Synchronises the stream. */
+int admm_hip_get_anderson(admm_hip_ctx *ctx, int32_t cap, int32_t *n, double *records);
+
 /* The LinearSolver objects' public tuning members, changed AFTER Solver::initialize.  The reference reads them on every solve --
  * NodalMultiColorGS::max_iters / m_tol / m_omega (src/NodalMultiColorGS.hpp:40-46, used at :100 and :136-140), UzawaCG::max_iters /
  * m_tol (src/UzawaCG.hpp:44-45, used at :92 and :109) -- so a caller may cast Solver::m_linsolver and change them between steps.
