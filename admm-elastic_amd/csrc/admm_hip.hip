@@ -89,6 +89,13 @@ struct DevBuf {
         const hipError_t e = hipMemset(p, 0, n * sizeof(T));
         return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
     }
+    // Allocated (again) and zeroed ON THE STREAM THAT USES THE BUFFER (z_prev, the padding record / element the incidence lists point at).
+    // Not zero(): its hipMemset on the NULL stream could land AFTER the work enqueued next on the non-blocking stream -- a z_prev <- D x
+    // overwritten with zeros made dz of iteration 0 |W z|, off by 3e5 in test_monitor_matches_oracle_trace[cloth6], once in a few runs.
+    hipError_t alloc_zeroed(size_t count, hipStream_t st) {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess || !count ? e : hipMemsetAsync(p, 0, count * sizeof(T), st);
+    }
     void release() {
         if (p) { (void)hipFree(p); g_dev_buffers -= 1; g_dev_bytes -= (int64_t)(n * sizeof(T)); }
         p = nullptr; n = 0;
@@ -138,6 +145,14 @@ struct RcclApi {
     }
 };
 RcclApi g_rccl;
+
+// Where a pass over the energy terms leaves what the vertex gather sums (elements.hpp: the write side), for `dirs` directions: records
+// [dirs][n_rec + 1][4], corner rows [dirs][12][ldr] and [dirs][12][ldb]; no buffer for a family the scene lacks.  Zeroed: the lists' padding.
+struct ElemScratch {
+    DevBuf<double> rec, rcf, hcf;
+    int dirs = 0;
+    hipError_t ensure(admm_hip_ctx *c, int dirs);      // room for `dirs` directions; a call that failed is made again
+};
 
 } // namespace
 
@@ -399,14 +414,13 @@ struct admm_hip_ctx {
     DevBuf<double> mon_part, mon_rec, mon_out, mon_term;          // block partials, records [admm_iters][8], one result [8], per-term energies
     // internal forces / stress / stationarity (forces.hpp; admm_hip_forces, admm_hip_stress, monitor mode 3): buffers of their own, allocated
     // by the first call that needs them -- the step's t_rec, r_cf, h_cf are not borrowed
-    DevBuf<double> f_rec, f_rcf, f_hcf, f_out, f_stress, f_part, f_stat;   // records, corner forces, f [3 nv], stress [13][ldt], block partials, sums [admm_iters]
+    ElemScratch f_el; DevBuf<double> f_out, f_stress, f_part, f_stat;      // f [3 nv], stress [13][ldt], block partials, sums [admm_iters]
     int mon_stat_n = 0;      // stationarity sums the last step wrote (mode 3), else 0
-    // tangent stiffness (tangent.hpp; admm_hip_stiffness_apply): buffers of their own for k_cap directions, allocated by the first call
+    // tangent stiffness (tangent.hpp; admm_hip_stiffness_apply): buffers of their own for k_el.dirs directions, allocated by the first call
     // and again by a call with more directions
-    DevBuf<double> k_rec, k_rcf, k_hcf, k_d, k_out;      // records, corner contributions, the directions and the result [k_cap][3 nv]
-    int k_cap = 0;
+    ElemScratch k_el; DevBuf<double> k_d, k_out;      // the directions and the result [k_el.dirs][3 nv]
     // frozen tangent, tangent_solve and newton_polish (newton.hpp): buffers of their own, allocated by the first call
-    DevBuf<double> nw_tfr, nw_rfr, nw_rec, nw_rcf, nw_hcf;      // the frames [30][ldt], [11][ldr]; records and corner contributions of one direction
+    DevBuf<double> nw_tfr, nw_rfr; ElemScratch nw_el;      // the frames [30][ldt], [11][ldr]; the scratch of one direction
     DevBuf<double> nw_dinv, nw_y, nw_r, nw_p, nw_ap, nw_rhs, nw_part;      // [3 nv] each; block partials [3][blocks]
     DevBuf<NwCg> nw_st; DevBuf<int> nw_stop, nw_pin;      // the PCG's scalars [3], its stop word, the held vertices [nv]
     int *nw_hstop = nullptr;      // pinned: the stop word as the host reads it between chunks
@@ -547,18 +561,10 @@ hipError_t mon_ensure(admm_hip_ctx *c, bool zprev, bool term) {
     if (c->mon_part.n < np && (e = c->mon_part.alloc(np)) != hipSuccess) return e;
     if (!c->mon_out.p && (e = c->mon_out.alloc(kMonQ)) != hipSuccess) return e;
     if (zprev) {
-        // zeroed ON THE CONTEXT'S STREAM: DevBuf::zero() is a hipMemset on the NULL stream, which this non-blocking stream does not wait
-        // for -- it could land AFTER the z_prev <- D x of the step that follows (dz of iteration 0 then came out as |W z|, off by 3e5
-        // in test_monitor_matches_oracle_trace[cloth6], once in a few runs)
-        auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
-            if (b.p) return hipSuccess;
-            const hipError_t e2 = b.alloc(n);
-            return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
-        };
-        if (c->nt && (e = fresh(c->mon_tzp, (size_t)9 * c->ldt)) != hipSuccess) return e;
-        if (c->ntri && (e = fresh(c->mon_rzp, (size_t)6 * c->ldr)) != hipSuccess) return e;
-        if (c->nbend && (e = fresh(c->mon_hzp, (size_t)3 * c->ldb)) != hipSuccess) return e;
-        if (c->npin_terms && (e = fresh(c->mon_pzp, (size_t)6 * c->npin_terms)) != hipSuccess) return e;
+        if (c->nt && !c->mon_tzp.p && (e = c->mon_tzp.alloc_zeroed((size_t)9 * c->ldt, c->stream)) != hipSuccess) return e;
+        if (c->ntri && !c->mon_rzp.p && (e = c->mon_rzp.alloc_zeroed((size_t)6 * c->ldr, c->stream)) != hipSuccess) return e;
+        if (c->nbend && !c->mon_hzp.p && (e = c->mon_hzp.alloc_zeroed((size_t)3 * c->ldb, c->stream)) != hipSuccess) return e;
+        if (c->npin_terms && !c->mon_pzp.p && (e = c->mon_pzp.alloc_zeroed((size_t)6 * c->npin_terms, c->stream)) != hipSuccess) return e;
     }
     const size_t nterm = (size_t)c->nt + c->ntri + c->nbend;
     if (term && nterm && !c->mon_term.p && (e = c->mon_term.alloc(nterm)) != hipSuccess) return e;
@@ -674,33 +680,37 @@ void launch_aa_apply(admm_hip_ctx *c, bool last) {
     hipLaunchKernelGGL(k_aa_apply, dim3(a.nb), dim3(256), 0, c->stream, a);
 }
 
+hipError_t ElemScratch::ensure(admm_hip_ctx *c, int want) {
+    if (want <= dirs) return hipSuccess;
+    hipError_t e;
+    dirs = 0;
+    const size_t k = (size_t)want;
+    if (c->nt && (e = rec.alloc_zeroed(k * 4 * (c->n_rec + 1), c->stream)) != hipSuccess) return e;
+    if (c->ntri && (e = rcf.alloc_zeroed(k * 12 * c->ldr, c->stream)) != hipSuccess) return e;
+    if (c->nbend && (e = hcf.alloc_zeroed(k * 12 * c->ldb, c->stream)) != hipSuccess) return e;
+    dirs = want;
+    return hipSuccess;
+}
+
 // ---- internal forces, stress, stationarity (forces.hpp) ----
-// buffers, allocated by the first call that needs them; the padding record / element the incidence lists point at must be zero: zeroed
-// on the context's stream (see mon_ensure)
+// buffers, allocated by the first call that needs them
 hipError_t force_ensure(admm_hip_ctx *c, bool stress, int stat_records) {
     hipError_t e;
-    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
-        if (b.p) return hipSuccess;
-        const hipError_t e2 = b.alloc(n);
-        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
-    };
-    if (c->nt && (e = fresh(c->f_rec, (size_t)4 * (c->n_rec + 1))) != hipSuccess) return e;
-    if (c->ntri && (e = fresh(c->f_rcf, (size_t)12 * c->ldr)) != hipSuccess) return e;
-    if (c->nbend && (e = fresh(c->f_hcf, (size_t)12 * c->ldb)) != hipSuccess) return e;
-    if ((e = fresh(c->f_out, (size_t)std::max(1, c->n3))) != hipSuccess) return e;
-    if (stress && c->nt && (e = fresh(c->f_stress, (size_t)kStressQ * c->ldt)) != hipSuccess) return e;
+    if ((e = c->f_el.ensure(c, 1)) != hipSuccess) return e;
+    if (!c->f_out.p && (e = c->f_out.alloc_zeroed((size_t)std::max(1, c->n3), c->stream)) != hipSuccess) return e;
+    if (stress && c->nt && !c->f_stress.p && (e = c->f_stress.alloc_zeroed((size_t)kStressQ * c->ldt, c->stream)) != hipSuccess) return e;
     if (stat_records > 0) {
-        if ((e = fresh(c->f_part, (size_t)std::max(1, blocks_for(c->nv)))) != hipSuccess) return e;
+        if (!c->f_part.p && (e = c->f_part.alloc_zeroed((size_t)std::max(1, blocks_for(c->nv)), c->stream)) != hipSuccess) return e;
         if (c->f_stat.n < (size_t)stat_records && (e = c->f_stat.alloc((size_t)stat_records)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
-// the scene and the chunk plan at positions x; rec, r_cf, h_cf: where the pass leaves the records and corner forces
-ForceArgs force_args(const admm_hip_ctx *c, const double *x, double *rec, double *r_cf, double *h_cf) {
+// the scene and the chunk plan at positions x; el: where the pass leaves the records and corner forces
+ForceArgs force_args(const admm_hip_ctx *c, const double *x, const ElemScratch &el) {
     ForceArgs a{};
     a.v = elem_view(c, x);
     for (int i = 0; i < 6; ++i) a.cb[i] = c->chunk_base[i];
-    a.ch_ent = c->ch_ent.p; a.ch_group = c->ch_group.p; a.ch_rec = c->ch_rec.p; a.rec = rec; a.r_cf = r_cf; a.h_cf = h_cf;
+    a.plan = ChunkPlan{c->ch_ent.p, c->ch_group.p, c->ch_rec.p}; a.rec = el.rec.p; a.r_cf = el.rcf.p; a.h_cf = el.hcf.p;
     a.nb_t = c->nt > 0 ? c->chunk_base[5] : 0; a.nb_r = a.nb_t + blocks_for(c->ntri);
     return a;
 }
@@ -716,7 +726,7 @@ ForceGatherArgs force_gather_args(const admm_hip_ctx *c, const ForceArgs &a, dou
 }
 // f_out = -dE/dx at positions x (device); stress: also the per-tet stress into f_stress; stop: the stop word or nullptr
 void launch_forces(admm_hip_ctx *c, const double *x, bool stress, const int *stop) {
-    ForceArgs a = force_args(c, x, c->f_rec.p, c->f_rcf.p, c->f_hcf.p);
+    ForceArgs a = force_args(c, x, c->f_el);
     a.stress = stress ? c->f_stress.p : nullptr;
     a.stop = stop;
     const int nb = a.nb_r + blocks_for(c->nbend);
@@ -726,30 +736,21 @@ void launch_forces(admm_hip_ctx *c, const double *x, bool stress, const int *sto
     hipLaunchKernelGGL(k_gather_forces, dim3(std::max(1, (g.n_slices + 3) / 4)), dim3(256), 0, c->stream, g);
 }
 // ---- tangent stiffness (tangent.hpp) ----
-// buffers for n_vec directions; the padding record / element of every direction must be zero: zeroed on the context's stream
+// buffers for n_vec directions (a failed allocation leaves its buffer empty: the call is made again)
 hipError_t tangent_ensure(admm_hip_ctx *c, int n_vec) {
-    if (n_vec <= c->k_cap) return hipSuccess;
     hipError_t e;
-    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {
-        const hipError_t e2 = b.alloc(n);
-        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
-    };
-    c->k_cap = 0;
-    const size_t k = (size_t)n_vec;
-    if (c->nt && (e = fresh(c->k_rec, k * 4 * (c->n_rec + 1))) != hipSuccess) return e;
-    if (c->ntri && (e = fresh(c->k_rcf, k * 12 * c->ldr)) != hipSuccess) return e;
-    if (c->nbend && (e = fresh(c->k_hcf, k * 12 * c->ldb)) != hipSuccess) return e;
-    if ((e = fresh(c->k_d, k * std::max(1, c->n3))) != hipSuccess) return e;
-    if ((e = fresh(c->k_out, k * std::max(1, c->n3))) != hipSuccess) return e;
-    c->k_cap = n_vec;
+    const size_t n = (size_t)n_vec * std::max(1, c->n3);
+    if ((e = c->k_el.ensure(c, n_vec)) != hipSuccess) return e;
+    if (c->k_d.n < n && (e = c->k_d.alloc_zeroed(n, c->stream)) != hipSuccess) return e;
+    if (c->k_out.n < n && (e = c->k_out.alloc_zeroed(n, c->stream)) != hipSuccess) return e;
     return hipSuccess;
 }
 // k_out[j] = K(x) k_d[j] + shift m o k_d[j], j < n_vec, at positions x (device)
 void launch_tangent(admm_hip_ctx *c, const double *x, int n_vec, double shift) {
     TangentArgs t{};
-    t.f = force_args(c, x, c->k_rec.p, c->k_rcf.p, c->k_hcf.p);
+    t.f = force_args(c, x, c->k_el);
     t.d = c->k_d.p; t.n_vec = n_vec;
-    t.d_stride = (size_t)c->n3; t.rec_stride = (size_t)4 * (c->n_rec + 1); t.rcf_stride = (size_t)12 * c->ldr; t.hcf_stride = (size_t)12 * c->ldb;
+    t.s = DirStrides{(size_t)c->n3, (size_t)4 * (c->n_rec + 1), (size_t)12 * c->ldr, (size_t)12 * c->ldb};      // (the sizes of ElemScratch::ensure)
     const int nb = t.f.nb_r + blocks_for(c->nbend);
     if (nb > 0) {
         if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent<true>, dim3(nb), dim3(256), 0, c->stream, t);
@@ -757,8 +758,7 @@ void launch_tangent(admm_hip_ctx *c, const double *x, int n_vec, double shift) {
     }
     TangentGatherArgs q{};
     q.g = force_gather_args(c, t.f, c->k_out.p);
-    q.d = c->k_d.p; q.m = c->m.p; q.shift = shift;
-    q.d_stride = t.d_stride; q.rec_stride = t.rec_stride; q.rcf_stride = t.rcf_stride; q.hcf_stride = t.hcf_stride;
+    q.d = c->k_d.p; q.m = c->m.p; q.shift = shift; q.s = t.s;
     hipLaunchKernelGGL(k_gather_tangent, dim3(std::max(1, (q.g.n_slices + 3) / 4), n_vec), dim3(256), 0, c->stream, q);
 }
 
@@ -771,6 +771,117 @@ void launch_stationarity(admm_hip_ctx *c, int s) {
     hipLaunchKernelGGL(k_stationarity, dim3(nb), dim3(256), 0, c->stream, c->nv, c->curr.p, c->m.p, c->Mxbar.p, c->f_out.p, 1.0 / (c->dt * c->dt),
                        (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr, c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->f_part.p, c->stop_dev);
     hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, c->stream, c->f_part.p, nb, c->f_stat.p + s, c->stop_dev);
+}
+
+// ---- frozen tangent (newton.hpp) ----
+hipError_t newton_ensure(admm_hip_ctx *c) {
+    if (c->nw_ready) return hipSuccess;
+    hipError_t e;
+    hipStream_t st = c->stream;
+    if (c->nt && (e = c->nw_tfr.alloc_zeroed((size_t)kFrameTet * c->ldt, st)) != hipSuccess) return e;
+    if (c->ntri && (e = c->nw_rfr.alloc_zeroed((size_t)kFrameTri * c->ldr, st)) != hipSuccess) return e;
+    if ((e = c->nw_el.ensure(c, 1)) != hipSuccess) return e;
+    const size_t n = (size_t)std::max(1, c->n3);
+    for (DevBuf<double> *b : {&c->nw_dinv, &c->nw_y, &c->nw_r, &c->nw_p, &c->nw_ap, &c->nw_rhs})
+        if ((e = b->alloc_zeroed(n, st)) != hipSuccess) return e;
+    if ((e = c->nw_part.alloc_zeroed((size_t)3 * std::max(1, blocks_for(c->nv)) + 8, st)) != hipSuccess) return e;      // (+ 8: the polish's sums)
+    if ((e = c->nw_st.alloc(3)) != hipSuccess) return e;
+    if ((e = c->nw_stop.alloc(1)) != hipSuccess) return e;
+    if ((e = c->nw_pin.alloc((size_t)std::max(1, c->nv))) != hipSuccess) return e;
+    if (!c->nw_hstop && (e = hipHostMalloc((void **)&c->nw_hstop, 2 * sizeof(int), hipHostMallocDefault)) != hipSuccess) return e;      // (a call that failed further down is made again)
+    for (hipEvent_t &ev : c->nw_ev)
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+    c->nw_ready = true;
+    return hipSuccess;
+}
+int nw_blocks(const admm_hip_ctx *c) { return std::max(1, blocks_for(c->nv)); }
+FrozenArgs frozen_args(const admm_hip_ctx *c, const double *x, const double *d, int psd, const int *stop) {
+    FrozenArgs a{};
+    a.f = force_args(c, x, c->nw_el);
+    a.t_fr = c->nw_tfr.p; a.r_fr = c->nw_rfr.p; a.d = d; a.psd = psd; a.stop = stop;
+    return a;
+}
+// the frames of the tangent at x (device) into nw_tfr / nw_rfr
+void launch_tangent_setup(admm_hip_ctx *c, const double *x, int psd) {
+    const FrozenArgs a = frozen_args(c, x, nullptr, psd, nullptr);
+    if (a.f.nb_r <= 0) return;
+    if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent_setup<true>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_tangent_setup<false>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
+}
+NewtonGatherArgs newton_gather_args(const admm_hip_ctx *c, const FrozenArgs &a, const double *d, double *out, double shift, const int *pin, const int *stop) {
+    NewtonGatherArgs q{};
+    q.g = force_gather_args(c, a.f, out);
+    q.d = d; q.m = c->m.p; q.shift = shift; q.pin = pin; q.part = c->nw_part.p; q.stop = stop;
+    return q;
+}
+// out = K_frozen d + shift m o d (rows of held vertices zero); nw_part[0 .. blocks) = the partials of d . out
+void launch_frozen(admm_hip_ctx *c, const double *d, double *out, double shift, const int *pin, const int *stop) {
+    const FrozenArgs a = frozen_args(c, nullptr, d, 0, stop);
+    const int nb = a.f.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_tangent_frozen, dim3(nb), dim3(256), 0, c->stream, a);
+    const NewtonGatherArgs q = newton_gather_args(c, a, d, out, shift, pin, stop);
+    hipLaunchKernelGGL(k_newton_gather<false>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
+}
+// nw_dinv = 1 / (diag K_frozen + shift m), 0 on held vertices
+void launch_frozen_diag(admm_hip_ctx *c, double shift, const int *pin) {
+    const FrozenArgs a = frozen_args(c, nullptr, nullptr, 0, nullptr);
+    const int nb = a.f.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_tangent_diag, dim3(nb), dim3(256), 0, c->stream, a);
+    const NewtonGatherArgs q = newton_gather_args(c, a, nullptr, c->nw_dinv.p, shift, pin, nullptr);
+    hipLaunchKernelGGL(k_newton_gather<true>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
+}
+// nw_pin = the vertices k_stationarity skips
+void launch_pin_mask(admm_hip_ctx *c) {
+    const bool gs = c->linsolver == 1;
+    hipLaunchKernelGGL(k_nw_pin_mask, dim3(nw_blocks(c)), dim3(256), 0, c->stream, c->nv, (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr,
+                       c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->nw_pin.p);
+}
+// Jacobi-PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device; leaves y in nw_y and the verdict in nw_st[2].
+// Iterations are enqueued in chunks, one chunk ahead of the device; the host reads the stop word of the chunk before (pinned, behind an
+// event) and stops enqueueing.  The caller synchronises.
+int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    hipLaunchKernelGGL(k_nw_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_p.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_nw_cg_init2, dim3(1), dim3(256), 0, st, nb, c->nw_part.p, c->nw_st.p, c->nw_stop.p);
+    constexpr int chunk = 8;
+    int launched = 0, chunks = 0;
+    while (launched < max_iters) {
+        const int n = std::min(chunk, max_iters - launched);
+        for (int it = launched; it < launched + n; ++it) {
+            launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
+            hipLaunchKernelGGL(k_nw_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
+                               c->nw_y.p, c->nw_r.p, c->nw_part.p);
+            hipLaunchKernelGGL(k_nw_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
+                               c->nw_r.p, c->nw_p.p, c->nw_part.p);
+        }
+        launched += n;
+        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
+        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
+            if (c->nw_hstop[(chunks - 1) & 1]) break;
+        }
+        ++chunks;
+    }
+    // the TRUE residual rhs - (K + shift M) y of the iterate the solve returns, over the free rows: what info4 reports.  The recursive residual
+    // the stop test reads drifts from it by about eps cond(A) |rhs| -- 7e-4 of a residual of 1e-12 |rhs|.  (The launches of a chunk enqueued
+    // behind the stop are no-ops; this one carries no stop word.)
+    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);
+    hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
+    HIP_TRY(hipGetLastError());
+    return ADMM_HIP_OK;
+}
+int newton_args_ok(const char *who, double shift, int32_t flags) {
+    if (!std::isfinite(shift)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": shift must be finite");
+    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
+    return ADMM_HIP_OK;
 }
 
 void launch_gather(admm_hip_ctx *c) {
@@ -3716,15 +3827,20 @@ static int mon_refuse(const admm_hip_ctx *c, const char *who) {
     return ADMM_HIP_OK;
 }
 
+// the context's device current, its stream idle, no step pending (settle)
+static int quiesce(admm_hip_ctx *c) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return settle(c);
+}
+
 // The common entry of energy, forces / stress and stiffness_apply: refuses what mon_refuse refuses and a call without positions, waits for
 // the stream, settles and uploads x.  *xd = the positions on the device: the device-resident state, or curr when x is given (curr is scratch
 // between steps).
 static int eval_begin(admm_hip_ctx *c, const char *who, const double *x, const double **xd) {
     if (int rc = mon_refuse(c, who)) return rc;
     if (!x && !c->state_set) return fail(ADMM_HIP_ERR_STATE, std::string(who) + ": no device-resident state yet (admm_hip_set_state), and x is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = settle(c)) return rc;
+    if (int rc = quiesce(c)) return rc;
     *xd = c->x.p;
     if (x) { HIP_TRY(hipMemcpyAsync(c->curr.p, x, c->n3 * sizeof(double), hipMemcpyHostToDevice, c->stream)); *xd = c->curr.p; }
     return ADMM_HIP_OK;
@@ -3795,125 +3911,6 @@ int admm_hip_stiffness_apply(admm_hip_ctx *c, const double *x, int32_t n_vec, co
 }
 
 // ---- frozen tangent, tangent_solve, newton_polish (newton.hpp) ----
-static hipError_t newton_ensure(admm_hip_ctx *c) {
-    if (c->nw_ready) return hipSuccess;
-    hipError_t e;
-    auto fresh = [&](DevBuf<double> &b, size_t n) -> hipError_t {      // (the padding record / element the incidence lists point at must be zero)
-        const hipError_t e2 = b.alloc(n);
-        return e2 != hipSuccess ? e2 : hipMemsetAsync(b.p, 0, n * sizeof(double), c->stream);
-    };
-    if (c->nt) {
-        if ((e = fresh(c->nw_tfr, (size_t)kFrameTet * c->ldt)) != hipSuccess) return e;
-        if ((e = fresh(c->nw_rec, (size_t)4 * (c->n_rec + 1))) != hipSuccess) return e;
-    }
-    if (c->ntri) {
-        if ((e = fresh(c->nw_rfr, (size_t)kFrameTri * c->ldr)) != hipSuccess) return e;
-        if ((e = fresh(c->nw_rcf, (size_t)12 * c->ldr)) != hipSuccess) return e;
-    }
-    if (c->nbend && (e = fresh(c->nw_hcf, (size_t)12 * c->ldb)) != hipSuccess) return e;
-    const size_t n = (size_t)std::max(1, c->n3);
-    for (DevBuf<double> *b : {&c->nw_dinv, &c->nw_y, &c->nw_r, &c->nw_p, &c->nw_ap, &c->nw_rhs})
-        if ((e = fresh(*b, n)) != hipSuccess) return e;
-    if ((e = fresh(c->nw_part, (size_t)3 * std::max(1, blocks_for(c->nv)) + 8)) != hipSuccess) return e;      // (+ 8: the polish's sums)
-    if ((e = c->nw_st.alloc(3)) != hipSuccess) return e;
-    if ((e = c->nw_stop.alloc(1)) != hipSuccess) return e;
-    if ((e = c->nw_pin.alloc((size_t)std::max(1, c->nv))) != hipSuccess) return e;
-    if (!c->nw_hstop && (e = hipHostMalloc((void **)&c->nw_hstop, 2 * sizeof(int), hipHostMallocDefault)) != hipSuccess) return e;      // (a call that failed further down is made again)
-    for (hipEvent_t &ev : c->nw_ev)
-        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    c->nw_ready = true;
-    return hipSuccess;
-}
-static int nw_blocks(const admm_hip_ctx *c) { return std::max(1, blocks_for(c->nv)); }
-static FrozenArgs frozen_args(const admm_hip_ctx *c, const double *x, const double *d, int psd, const int *stop) {
-    FrozenArgs a{};
-    a.f = force_args(c, x, c->nw_rec.p, c->nw_rcf.p, c->nw_hcf.p);
-    a.t_fr = c->nw_tfr.p; a.r_fr = c->nw_rfr.p; a.d = d; a.psd = psd; a.stop = stop;
-    return a;
-}
-// the frames of the tangent at x (device) into nw_tfr / nw_rfr
-static void launch_tangent_setup(admm_hip_ctx *c, const double *x, int psd) {
-    const FrozenArgs a = frozen_args(c, x, nullptr, psd, nullptr);
-    if (a.f.nb_r <= 0) return;
-    if (c->spl_tab.p) hipLaunchKernelGGL(k_tangent_setup<true>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_tangent_setup<false>, dim3(a.f.nb_r), dim3(256), 0, c->stream, a);
-}
-static NewtonGatherArgs newton_gather_args(const admm_hip_ctx *c, const FrozenArgs &a, const double *d, double *out, double shift, const int *pin, const int *stop) {
-    NewtonGatherArgs q{};
-    q.g = force_gather_args(c, a.f, out);
-    q.d = d; q.m = c->m.p; q.shift = shift; q.pin = pin; q.part = c->nw_part.p; q.stop = stop;
-    return q;
-}
-// out = K_frozen d + shift m o d (rows of held vertices zero); nw_part[0 .. blocks) = the partials of d . out
-static void launch_frozen(admm_hip_ctx *c, const double *d, double *out, double shift, const int *pin, const int *stop) {
-    const FrozenArgs a = frozen_args(c, nullptr, d, 0, stop);
-    const int nb = a.f.nb_r + blocks_for(c->nbend);
-    if (nb > 0) hipLaunchKernelGGL(k_tangent_frozen, dim3(nb), dim3(256), 0, c->stream, a);
-    const NewtonGatherArgs q = newton_gather_args(c, a, d, out, shift, pin, stop);
-    hipLaunchKernelGGL(k_newton_gather<false>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
-}
-// nw_dinv = 1 / (diag K_frozen + shift m), 0 on held vertices
-static void launch_frozen_diag(admm_hip_ctx *c, double shift, const int *pin) {
-    const FrozenArgs a = frozen_args(c, nullptr, nullptr, 0, nullptr);
-    const int nb = a.f.nb_r + blocks_for(c->nbend);
-    if (nb > 0) hipLaunchKernelGGL(k_tangent_diag, dim3(nb), dim3(256), 0, c->stream, a);
-    const NewtonGatherArgs q = newton_gather_args(c, a, nullptr, c->nw_dinv.p, shift, pin, nullptr);
-    hipLaunchKernelGGL(k_newton_gather<true>, dim3(nw_blocks(c)), dim3(256), 0, c->stream, q);
-}
-// nw_pin = the vertices k_stationarity skips
-static void launch_pin_mask(admm_hip_ctx *c) {
-    const bool gs = c->linsolver == 1;
-    hipLaunchKernelGGL(k_nw_pin_mask, dim3(nw_blocks(c)), dim3(256), 0, c->stream, c->nv, (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr,
-                       c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->nw_pin.p);
-}
-// Jacobi-PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device; leaves y in nw_y and the verdict in nw_st[2].
-// Iterations are enqueued in chunks, one chunk ahead of the device; the host reads the stop word of the chunk before (pinned, behind an
-// event) and stops enqueueing.  The caller synchronises.
-static int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
-    hipStream_t st = c->stream;
-    const int nv = c->nv, nb = nw_blocks(c);
-    const int *pin = nullptr;
-    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
-    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
-    launch_tangent_setup(c, xd, flags & 1);
-    launch_frozen_diag(c, shift, pin);
-    hipLaunchKernelGGL(k_nw_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_p.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_nw_cg_init2, dim3(1), dim3(256), 0, st, nb, c->nw_part.p, c->nw_st.p, c->nw_stop.p);
-    constexpr int chunk = 8;
-    int launched = 0, chunks = 0;
-    while (launched < max_iters) {
-        const int n = std::min(chunk, max_iters - launched);
-        for (int it = launched; it < launched + n; ++it) {
-            launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
-            hipLaunchKernelGGL(k_nw_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
-                               c->nw_y.p, c->nw_r.p, c->nw_part.p);
-            hipLaunchKernelGGL(k_nw_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
-                               c->nw_r.p, c->nw_p.p, c->nw_part.p);
-        }
-        launched += n;
-        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
-        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
-            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
-            if (c->nw_hstop[(chunks - 1) & 1]) break;
-        }
-        ++chunks;
-    }
-    // the TRUE residual rhs - (K + shift M) y of the iterate the solve returns, over the free rows: what info4 reports.  The recursive residual
-    // the stop test reads drifts from it by about eps cond(A) |rhs| -- 7e-4 of a residual of 1e-12 |rhs|.  (The launches of a chunk enqueued
-    // behind the stop are no-ops; this one carries no stop word.)
-    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);
-    hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
-    HIP_TRY(hipGetLastError());
-    return ADMM_HIP_OK;
-}
-static int newton_args_ok(const char *who, double shift, int32_t flags) {
-    if (!std::isfinite(shift)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": shift must be finite");
-    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
-    return ADMM_HIP_OK;
-}
-
 // admm_hip_stiffness_apply on the frozen tangent: one setup, then one frozen pass per direction.  flags bit 0: the element tangents are
 // projected to their positive semi-definite part; bit 1: pinned vertices are held (their rows are zero, d is ignored there)
 int admm_hip_stiffness_apply_ex(admm_hip_ctx *c, const double *x, int32_t n_vec, const double *d, double shift, int32_t flags, double *out) {
@@ -3971,10 +3968,8 @@ int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol,
     if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has colliders; contact is not part of the objective the polish minimises");
     if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has strain-limited triangles; the energy ignores the limits");
     if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has slide pins");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = quiesce(c)) return rc;
     hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = settle(c)) return rc;
     if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "newton_polish: no step has run on this state yet (the objective needs the step's x_bar)");
     HIP_TRY(newton_ensure(c));
     HIP_TRY(force_ensure(c, false, 0));
@@ -4037,10 +4032,8 @@ int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol,
 int admm_hip_residuals(admm_hip_ctx *c, const double *x, const double *z, const double *z_prev, double *out4) {
     if (!c || !x || !z || !z_prev || !out4) return fail(ADMM_HIP_ERR_ARG, "residuals: NULL argument");
     if (int rc = mon_refuse(c, "residuals")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = quiesce(c)) return rc;
     hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = settle(c)) return rc;
     HIP_TRY(mon_ensure(c, true, false));
     if (c->npin_terms && !c->mon_pz6.p) HIP_TRY(c->mon_pz6.alloc((size_t)6 * c->npin_terms));
     std::vector<double> tz, rz, pz, hz, tp, rp, pp, hp;

@@ -1,7 +1,8 @@
-// elements.hpp -- the read side of an energy term: how a tet, a triangle and a bending hinge are read at positions x, and how a chunk of
-// tets returns its corner forces.  ONE text under the three device passes over all terms -- energy and residuals (monitor.hpp), forces and
-// stress (forces.hpp), K(x) d (tangent.hpp) -- so a change to how an element is read (a tet kind, a Binv mode, a chunk width) is made here
-// once.  Included by monitor.hpp.
+// elements.hpp -- both sides of an energy term.  READ: how a tet, a triangle and a bending hinge are read at positions x.  WRITE: how an
+// element's corner contributions leave the kernel -- a chunk of tets through its reduction into 32-byte records (chunk_out_begin / _store),
+// triangles and hinges through their corner rows -- for the incidence lists of k_gather_rhs to sum per vertex (forces.hpp: gather_vertex).
+// ONE text under the device passes over all terms -- energy and residuals (monitor.hpp), forces and stress (forces.hpp), K(x) d (tangent.hpp),
+// the frozen tangent (newton.hpp) -- so a change to how an element is read or written is made here once.  Included by monitor.hpp.
 //
 // The LOCAL STEP keeps its own text (kernels.hpp: tet_gather, tet_rest_binv, tet_compute_store): its 36 instances sit on spilled registers,
 // and calling these helpers from it changed their register allocation and schedule.  What must agree with it to the bit is restated here
@@ -25,6 +26,17 @@ struct ElemView {
     int nbend, ldb; const int4 *h_idx; const double *h_coef, *h_k;
 };
 
+// the edge matrix of a tet with the vertices vid at p (the positions or a direction): Ds[3 m + j] = (p_{m+1} - p_0)_j
+__device__ __forceinline__ void tet_edge_matrix(const double *p, const int *vid, double *Ds) {
+    double x[12];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) x[3 * v + j] = p[3 * (size_t)vid[v] + j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
+}
+
 // Binv (row-major: Bi[3 r + m] = Binv(m, r)) of tet t with the vertices id -- recomputed from the rest positions (t_x0 set) or streamed --
 // and F = D_i x = Ds Binv (column-major, rows 3 r + j of the term)
 __device__ __forceinline__ void tet_F_binv(const ElemView &a, const int4 id, int t, double *F, double *Bi) {
@@ -46,7 +58,7 @@ __device__ __forceinline__ void tet_F_binv(const ElemView &a, const int4 id, int
 #pragma unroll
         for (int c = 0; c < 9; ++c) Bi[c] = a.t_Binv[(size_t)c * a.ldt + t];
     }
-    double x[12], Ds[9];
+    double x[12], Ds[9];      // (the text of tet_edge_matrix restated: with the call, k_monitor's instances came out with another schedule)
 #pragma unroll
     for (int v = 0; v < 4; ++v)
 #pragma unroll
@@ -119,6 +131,29 @@ __device__ __forceinline__ void chunk_reduce_store(const LdsDk *sL, const __amdg
     }
 }
 
+// The way out of a chunk of tets, for every pass that writes records the incidence lists read.  chunk_out_begin, before the SVD or the
+// frame load: zeroes the padding column of the reduction lists and issues the load of this thread's first list, in flight across what
+// follows.  chunk_out_store: parks f [12] in this thread's column of rows 0..11 of sL, synchronises the block, reduces into rec.
+struct ChunkPlan { const unsigned short *ch_ent; const int *ch_group, *ch_rec; };      // the local step's chunk plan (host_setup.hpp: TetChunks)
+struct ChunkOut { __amdgpu_buffer_rsrc_t re; bv4u e0; int g0, g1, r0, nrec; };
+__device__ __forceinline__ ChunkOut chunk_out_begin(const ChunkPlan &p, int chunk, LdsDk *sL) {
+    const int tid = (int)threadIdx.x;
+    if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;
+    const int g0 = __builtin_amdgcn_readfirstlane(p.ch_group[chunk]), g1 = __builtin_amdgcn_readfirstlane(p.ch_group[chunk + 1]);
+    const int r0 = __builtin_amdgcn_readfirstlane(p.ch_rec[chunk]), nrec = __builtin_amdgcn_readfirstlane(p.ch_rec[chunk + 1]) - r0;
+    const __amdgpu_buffer_rsrc_t re = soa_rsrc(p.ch_ent);
+    const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+    return ChunkOut{re, e0, g0, g1, r0, nrec};
+}
+__device__ __forceinline__ void chunk_out_store(const ChunkOut &co, LdsDk *sL, const double *f, double *rec) {
+    LdsDk *sCf = sL + (int)threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 12; ++c) sCf[c * kChunkLdK] = f[c];
+    __syncthreads();
+    chunk_reduce_store(sL, co.re, co.e0, co.g0, co.g1, co.r0, co.nrec, rec);
+}
+struct DirStrides { size_t d, rec, rcf, hcf; };      // doubles between two directions: the vectors [3 nv], the records, the corner rows
+
 // F (3x2 column-major) = [p1 - p0, p2 - p0] R of a triangle with the vertices id and the rest matrix R (2x2 column-major); p = the
 // positions or a direction
 __device__ __forceinline__ void tri_F(const double *R, const int4 id, const double *p, double *F) {
@@ -151,6 +186,31 @@ __device__ __forceinline__ void hinge_Dx(const double *c, const int *vid, const 
 #pragma unroll
         for (int j = 0; j < 3; ++j) Dx[j] = fma(c[k], pk[j], Dx[j]);
     }
+}
+
+// hinge t: the vertices, the coefficients c and the stiffness
+__device__ __forceinline__ void hinge_load(const ElemView &v, int t, double *c, int *vid, double &ks) {
+    const int4 id = v.h_idx[t];
+    vid[0] = id.x; vid[1] = id.y; vid[2] = id.z; vid[3] = id.w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
+    ks = v.h_k[t];
+}
+// corner k of a hinge gets c_k s (D_i p): s = minus the stiffness for the forces, the stiffness for K d.  cf: the corner rows [12][ldb]
+__device__ __forceinline__ void hinge_corner_store(const double *c, double s, const double *Dx, double *cf, int ldb, int t) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cf[(size_t)(3 * k + j) * ldb + t] = c[k] * (s * Dx[j]);
+}
+
+// Is vertex v held?  vert_pin / pin_active: the SpringPin and slide-pin TERMS (linsolver 0 / 2); pin_flag: the pins applied inside the GS
+// sweeps (linsolver 1).  The one rule of the stationarity residual and of the frozen tangent's pin mask.
+__device__ __forceinline__ bool vertex_held(int v, const int *vert_pin, const int *pin_active, const int *pin_flag) {
+    bool held = false;
+    if (vert_pin) { const int pi = vert_pin[v]; held = pi >= 0 && pin_active[pi] != 0; }
+    if (pin_flag) held = held || pin_flag[v] != 0;
+    return held;
 }
 
 } // namespace admm_k

@@ -9,12 +9,11 @@
 // k_forces walks the families in block ranges like k_monitor and reads the elements through elements.hpp:
 //   tets      one block per 256-tet CHUNK of the local step's plan (host_setup.hpp: TetChunks), lane = tet.  F = D_i x = U diag(sigma) V^T
 //             (signed_svd3), P = U diag(s_i g_i) V^T with s_i g_i from the kind's own eval (device_math.hpp: tet_energy_grad -- the
-//             dispatch the energy uses, so the two cannot differ); corner forces H = -vol P Binv^T (corner m + 1: column m, corner 0: minus
-//             their sum), reduced per chunk into 32-byte records the way the local step reduces its own.  No density is restated here.
+//             dispatch the energy uses, so the two cannot differ); corner forces H = -vol P Binv^T.  No density is restated here.
 //   triangles lane = triangle: E = w^2 / 2 sum (sigma_i - 1)^2 of the 3x2 F, P = w^2 (F - R), R = F (F^T F)^(-1/2) the closest isometry
 //             (closed-form 2x2 inverse square root), corner forces through `rest`.
 //   hinges    f_{v_k} = -stiffness c_k (D_i x).
-// k_gather_forces (lane = vertex) sums records and corner forces through the incidence lists of k_gather_rhs, in list order.
+// How the corner forces leave k_forces and reach a vertex in k_gather_forces (lane = vertex): the write side of elements.hpp, gather_vertex.
 //
 // Limits.  At a stretch sigma_i = 0 the |sigma| kinds have a kink: the force there is a one-sided derivative (sign(0) counts as +).  The
 // stress divides by J = sigma_1 sigma_2 sigma_3 and a triangle's R by sigma_1 sigma_2: at J -> 0 (a flat tet, a collapsed triangle) the
@@ -32,7 +31,7 @@ constexpr int kStressQ = 13;      // per tet: P column-major (9), the signed str
 struct ForceArgs {
     ElemView v;               // the scene at x
     int cb[6];                // the model groups' first chunks (v.kb: their first tets)
-    const unsigned short *ch_ent; const int *ch_group, *ch_rec; double *rec;      // the local step's chunk plan; records [n_rec + 1][4]
+    ChunkPlan plan; double *rec;      // the local step's chunk plan; records [n_rec + 1][4]
     double *stress;           // [kStressQ][ldt] in device order, or nullptr
     double *r_cf;             // corner forces of the triangles [9 of 12][ldr]
     double *h_cf;             // of the hinges [12][ldb]
@@ -47,12 +46,8 @@ __device__ __forceinline__ void force_tets(const ForceArgs &a, int chunk, LdsDk 
     const ChunkLane ln = chunk_locate(v.kb, a.cb, chunk, tid);
     const int t = ln.t;
     LdsDk *sBi = sL + tid;                                   // row c of this thread: [c * kChunkLdK]
-    if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;            // the padding column of the reduction lists
     // the reduction list of this thread's record (first pass) and the tet's scalars: in flight across the SVD
-    const int g0 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk]), g1 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk + 1]);
-    const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk + 1]) - r0;
-    const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
-    const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+    const ChunkOut co = chunk_out_begin(a.plan, chunk, sL);
     const double w2 = v.t_sc[t] / v.dt2;
     const Mat mt = v.mats[v.t_mat[t]];
     double U[9], S[3], V[9], F[9];
@@ -87,10 +82,7 @@ __device__ __forceinline__ void force_tets(const ForceArgs &a, int chunk, LdsDk 
         usvt(U, dg, V, G);
     }
     tet_corner_forces(G, sBi, f);
-#pragma unroll
-    for (int c = 0; c < 12; ++c) sBi[c * kChunkLdK] = f[c];
-    __syncthreads();
-    chunk_reduce_store(sL, re, e0, g0, g1, r0, nrec, a.rec);
+    chunk_out_store(co, sL, f, a.rec);
 }
 
 __global__ __launch_bounds__(256) void k_forces(ForceArgs a) {
@@ -123,17 +115,11 @@ __global__ __launch_bounds__(256) void k_forces(ForceArgs a) {
     } else {
         const int t = (blk - a.nb_r) * 256 + tid;
         if (t >= v.nbend) return;
-        const int4 id = v.h_idx[t];
-        const int vid[4] = {id.x, id.y, id.z, id.w};
-        double c[4], Dx[3];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
+        int vid[4];
+        double c[4], Dx[3], ks;
+        hinge_load(v, t, c, vid, ks);
         hinge_Dx(c, vid, v.x, Dx);
-        const double ks = -v.h_k[t];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * v.ldb + t] = c[k] * (ks * Dx[j]);
+        hinge_corner_store(c, -ks, Dx, a.h_cf, v.ldb, t);
     }
 }
 
@@ -147,17 +133,23 @@ struct ForceGatherArgs {
     double *f;                // [nv][3]
     const int *stop;
 };
+// The head of every vertex gather: lane `lane` of slice s adds to acc [3] what is incident to its vertex in direction dir of a.t_rec,
+// a.r_cf, a.h_cf (st: the doubles between two directions), in list order, and returns the vertex (a.nv past the end).
+__device__ __forceinline__ int gather_vertex(const ForceGatherArgs &a, int s, int lane, double *acc, size_t dir = 0, const DirStrides &st = DirStrides{}) {
+    const int r = s * 64 + lane;
+    const int v = r < a.nv ? a.order[r] : a.nv;
+    if (a.t_inc) gather_records(a.t_inc + a.t_ptr[s] + lane, a.t_w[s], a.t_rec + dir * st.rec, acc);
+    if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf + dir * st.rcf, a.r_ld, acc);
+    if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf + dir * st.hcf, a.h_ld, acc);
+    return v;
+}
 __global__ __launch_bounds__(256) void k_gather_forces(ForceGatherArgs a) {
     if (a.stop && *a.stop) return;
     const int lane = threadIdx.x & 63;
     const int s = wave_slice();
     if (s >= a.n_slices) return;
-    const int r = s * 64 + lane;
-    const int v = r < a.nv ? a.order[r] : a.nv;
     double acc[3] = {0.0, 0.0, 0.0};
-    if (a.t_inc) gather_records(a.t_inc + a.t_ptr[s] + lane, a.t_w[s], a.t_rec, acc);
-    if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf, a.r_ld, acc);
-    if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf, a.h_ld, acc);
+    const int v = gather_vertex(a, s, lane, acc);
     if (v < a.nv) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) a.f[3 * (size_t)v + j] = acc[j];
@@ -166,7 +158,6 @@ __global__ __launch_bounds__(256) void k_gather_forces(ForceGatherArgs a) {
 
 // STATIONARITY of implicit Euler: sum of r_i^2 over the degrees of freedom of every vertex without an active pin,
 //   r = (m o x - M x_bar) / dt^2 - f      (the optimality condition M (x - x_bar) / dt^2 + grad E(x) = 0 of src/Solver.cpp:57-106)
-// vert_pin / pin_active: the SpringPin and slide-pin TERMS (linsolver 0 / 2); pin_flag: the pins applied inside the GS sweeps (linsolver 1).
 // Block partials by ordinary stores; k_stat_final sums them in index order and stores the sum (not its root).
 __global__ __launch_bounds__(256) void k_stationarity(int nv, const double *__restrict__ x, const double *__restrict__ m, const double *__restrict__ Mxbar,
                                                       const double *__restrict__ f, double idt2, const int *__restrict__ vert_pin,
@@ -177,10 +168,7 @@ __global__ __launch_bounds__(256) void k_stationarity(int nv, const double *__re
     const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
     double q[1] = {0.0};
     if (v < nv) {
-        bool pinned = false;
-        if (vert_pin) { const int pi = vert_pin[v]; pinned = pi >= 0 && pin_active[pi] != 0; }
-        if (pin_flag) pinned = pinned || pin_flag[v] != 0;
-        if (!pinned) {
+        if (!vertex_held(v, vert_pin, pin_active, pin_flag)) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const size_t i = 3 * (size_t)v + j;

@@ -8,11 +8,11 @@
 //             [kFrameTet][ldt] (one coalesced 512-byte wave access per component):  U (9), N = Binv V (9), vol {Hs (6), a (3), b (3)}.
 //             Per triangle [kFrameTri][ldr]: Q (6), Si (3), itr (with `psd` through tri_tangent_psd), w^2.
 //   k_tangent_frozen        per application.  A = U^T Ds(d) N, B from A and the coefficients (as tet_tangent_apply), corner contributions
-//             U B N^T -- neither V nor Binv is needed again -- reduced per chunk into the 32-byte records of k_forces / k_tangent
-//             (chunk_reduce_store, the same host plan).  Triangles: tri_tangent_apply on the stored frame; hinges as k_tangent.
+//             U B N^T -- neither V nor Binv is needed again -- leaving as those of k_forces / k_tangent do (elements.hpp: the write
+//             side).  Triangles: tri_tangent_apply on the stored frame; hinges as k_tangent.
 //   k_tangent_diag          the diagonal of the frozen operator: per tet and corner the three entries e_k . K_el e_k from twelve frozen
 //             applications to dF = e_k (x) grad N_a; they travel in the same records and corner buffers.
-//   k_newton_gather<DIAG>   lane = vertex, the incidence lists of k_gather_rhs in list order.  DIAG = false: out = K d + shift m o d, rows
+//   k_newton_gather<DIAG>   lane = vertex, gather_vertex.  DIAG = false: out = K d + shift m o d, rows
 //             of held vertices zero, and the block's partial of d . out; DIAG = true: out = 1 / (diag K + shift m), 0 on held vertices.
 // The PCG (y, r, p, Ap, D^-1; z = D^-1 r is not stored) per iteration: k_tangent_frozen on p, k_newton_gather, k_nw_cg_step (alpha; y, r;
 // partials of r.z and r.r), k_nw_cg_dir (beta; p; the stop decision).  The update of p needs the complete r.z of the SAME iteration, so
@@ -150,24 +150,14 @@ __device__ __forceinline__ void tangent_frozen_body(const FrozenArgs &fa, double
         LdsDk *sL = (LdsDk *)sLm;
         const ChunkLane ln = chunk_locate(v.kb, a.cb, blk, tid);
         const int t = ln.t;
-        LdsDk *sCf = sL + tid;
-        if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;                 // the padding column of the reduction lists
-        const int g0 = __builtin_amdgcn_readfirstlane(a.ch_group[blk]), g1 = __builtin_amdgcn_readfirstlane(a.ch_group[blk + 1]);
-        const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[blk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[blk + 1]) - r0;
-        const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
-        const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+        const ChunkOut co = chunk_out_begin(a.plan, blk, sL);
         double U[9], N[9], Hs[6], ca[3], cb[3], f[12];
         tet_frame_load(fa.t_fr, (size_t)v.ldt, t, U, N, Hs, ca, cb);
         if (!DIAG) {
             const int4 id = v.t_idx[t];
             const int vid[4] = {id.x, id.y, id.z, id.w};
-            double x[12], Ds[9];
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) x[3 * c + j] = fa.d[3 * (size_t)vid[c] + j];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
+            double Ds[9];
+            tet_edge_matrix(fa.d, vid, Ds);
             tet_frozen_apply(U, N, Hs, ca, cb, Ds, f);
         } else {
 #pragma unroll
@@ -185,10 +175,7 @@ __device__ __forceinline__ void tangent_frozen_body(const FrozenArgs &fa, double
                 for (int p = 0; p < 12; ++p) f[p] = p == q ? g[p] : f[p];
             }
         }
-#pragma unroll
-        for (int c = 0; c < 12; ++c) sCf[c * kChunkLdK] = f[c];
-        __syncthreads();
-        chunk_reduce_store(sL, re, e0, g0, g1, r0, nrec, a.rec);
+        chunk_out_store(co, sL, f, a.rec);
     } else if (blk < a.nb_r) {
         const int t = (blk - a.nb_t) * 256 + tid;
         if (t >= v.ntri) return;
@@ -226,17 +213,19 @@ __device__ __forceinline__ void tangent_frozen_body(const FrozenArgs &fa, double
     } else {
         const int t = (blk - a.nb_r) * 256 + tid;
         if (t >= v.nbend) return;
-        const int4 id = v.h_idx[t];
-        const int vid[4] = {id.x, id.y, id.z, id.w};
-        double c[4], Dx[3];
+        int vid[4];
+        double c[4], ks;
+        hinge_load(v, t, c, vid, ks);
+        if (!DIAG) {
+            double Dx[3];
+            hinge_Dx(c, vid, fa.d, Dx);
+            hinge_corner_store(c, ks, Dx, a.h_cf, v.ldb, t);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
-        const double ks = v.h_k[t];
-        if (!DIAG) hinge_Dx(c, vid, fa.d, Dx);
+            for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * v.ldb + t] = DIAG ? c[k] * (ks * c[k]) : c[k] * (ks * Dx[j]);
+                for (int j = 0; j < 3; ++j) a.h_cf[(size_t)(3 * k + j) * v.ldb + t] = c[k] * (ks * c[k]);
+        }
     }
 }
 __global__ __launch_bounds__(256) void k_tangent_frozen(FrozenArgs fa) {
@@ -267,12 +256,8 @@ __global__ __launch_bounds__(256) void k_newton_gather(NewtonGatherArgs na) {
     const int s = wave_slice();
     double q[1] = {0.0};
     if (s < a.n_slices) {
-        const int r = s * 64 + lane;
-        const int v = r < a.nv ? a.order[r] : a.nv;
         double acc[3] = {0.0, 0.0, 0.0};
-        if (a.t_inc) gather_records(a.t_inc + a.t_ptr[s] + lane, a.t_w[s], a.t_rec, acc);
-        if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf, a.r_ld, acc);
-        if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf, a.h_ld, acc);
+        const int v = gather_vertex(a, s, lane, acc);
         if (v < a.nv) {
             const bool held = na.pin && na.pin[v] != 0;
 #pragma unroll
@@ -310,15 +295,12 @@ __device__ __forceinline__ void nw_reduce(const double *__restrict__ part, int n
 }
 __device__ __forceinline__ bool nw_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (false for NaN)
 
-// pin[v] = 1 where k_stationarity skips a vertex: an active pin term (vert_pin / pin_active) or a pin of the GS sweeps (pin_flag)
+// pin[v] = 1 where k_stationarity skips a vertex (elements.hpp: vertex_held)
 __global__ __launch_bounds__(256) void k_nw_pin_mask(int nv, const int *__restrict__ vert_pin, const int *__restrict__ pin_active,
                                                      const int *__restrict__ pin_flag, int *__restrict__ pin) {
     const int v = blockIdx.x * 256 + (int)threadIdx.x;
     if (v >= nv) return;
-    bool held = false;
-    if (vert_pin) { const int pi = vert_pin[v]; held = pi >= 0 && pin_active[pi] != 0; }
-    if (pin_flag) held = held || pin_flag[v] != 0;
-    pin[v] = held ? 1 : 0;
+    pin[v] = vertex_held(v, vert_pin, pin_active, pin_flag) ? 1 : 0;
 }
 // out = in with the held vertices zeroed
 __global__ __launch_bounds__(256) void k_nw_mask(int nv, const int *__restrict__ pin, const double *__restrict__ in, double *__restrict__ out) {

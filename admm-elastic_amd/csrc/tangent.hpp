@@ -9,14 +9,12 @@
 //   tets      one block per 256-tet chunk, lane = tet.  The signed SVD of F = D_i x runs ONCE, the tangent's 12 coefficients
 //             (device_math.hpp: tet_tangent_coef -- Hs, al, be, collapsed to Hs, a = (al + be) / 2,
 //             b = (al - be) / 2) are formed once; per direction only dF = Ds(d) Binv, dP = U B V^T (tet_tangent_apply), the corner
-//             contributions vol dP Binv^T and the chunk's reduction into 32-byte records repeat.  U, V and the coefficients stay in
-//             registers, Binv in this thread's LDS column (rows 12..20); rows 0..11 are the chunk's corner contributions, reused between
-//             directions behind block barriers.
+//             contributions vol dP Binv^T and the chunk's way out repeat.  U, V and the coefficients stay in registers, Binv in this
+//             thread's LDS column (rows 12..20); rows 0..11 are reused between directions behind block barriers.
 //   triangles lane = triangle: dP = w^2 (dF - dQ) (device_math.hpp: tri_tangent_frame once, tri_tangent_apply per direction); strain
 //             limits ignored, as in energy() and forces().
 //   hinges    K = stiffness c c^T (x) I3, constant.
-// k_gather_tangent (lane = vertex, blockIdx.y = direction) sums records and corner contributions through the incidence lists of
-// k_gather_rhs in list order and adds shift m o d.
+// k_gather_tangent (lane = vertex, blockIdx.y = direction): gather_vertex on the direction's scratch, plus shift m o d.
 //
 // Limits: those of tet_tangent_coef and of the forces -- kinks at sigma_i = 0, the log barrier of the Neo-Hookean kinds at J -> 0, a
 // collapsed triangle: the outputs are what the arithmetic gives.  K is not projected to a positive semi-definite matrix.
@@ -32,7 +30,7 @@ struct TangentArgs {
     ForceArgs f;              // the scene at x and the chunk plan (stress, stop unused); rec, r_cf, h_cf: direction 0
     const double *d;          // [n_vec][3 nv]
     int n_vec;
-    size_t d_stride, rec_stride, rcf_stride, hcf_stride;      // doubles between two directions
+    DirStrides s;             // doubles between two directions
 };
 
 template <bool TABLE>
@@ -42,12 +40,8 @@ __device__ __forceinline__ void tangent_tets(const TangentArgs &ta, int chunk, L
     const int tid = (int)threadIdx.x;
     const ChunkLane ln = chunk_locate(v.kb, a.cb, chunk, tid);
     const int t = ln.t, grp = ln.grp;
-    LdsDk *sCf = sL + tid, *sBi = sL + 12 * kChunkLdK + tid;      // row c of this thread: [c * kChunkLdK]
-    if (tid < 3) sL[tid * kChunkLdK + 256] = 0.0;                 // the padding column of the reduction lists
-    const int g0 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk]), g1 = __builtin_amdgcn_readfirstlane(a.ch_group[chunk + 1]);
-    const int r0 = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk]), nrec = __builtin_amdgcn_readfirstlane(a.ch_rec[chunk + 1]) - r0;
-    const __amdgpu_buffer_rsrc_t re = soa_rsrc(a.ch_ent);
-    const bv4u e0 = __builtin_amdgcn_raw_buffer_load_b128(re, (g0 * 256 + tid) * 16, 0, kStreamLdAux);
+    LdsDk *sBi = sL + 12 * kChunkLdK + tid;      // row c of this thread: [c * kChunkLdK]
+    const ChunkOut co = chunk_out_begin(a.plan, chunk, sL);
     const double w2 = v.t_sc[t] / v.dt2;
     const Mat mt = v.mats[v.t_mat[t]];
     const int4 id = v.t_idx[t];
@@ -70,16 +64,10 @@ __device__ __forceinline__ void tangent_tets(const TangentArgs &ta, int chunk, L
     }
     const double vol = w2 / mt.k;      // w = sqrt(k vol), src/TetEnergyTerm.cpp:46-47
     for (int dir = 0; dir < ta.n_vec; ++dir) {
-        const double *dv = ta.d + (size_t)dir * ta.d_stride;
         double G[9], f[12];
         {
-            double x[12], Ds[9], dF[9];
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) x[3 * c + j] = dv[3 * (size_t)vid[c] + j];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { Ds[j] = x[3 + j] - x[j]; Ds[3 + j] = x[6 + j] - x[j]; Ds[6 + j] = x[9 + j] - x[j]; }
+            double Ds[9], dF[9];
+            tet_edge_matrix(ta.d + (size_t)dir * ta.s.d, vid, Ds);
 #pragma unroll
             for (int r = 0; r < 3; ++r) {      // dF = Ds(d) Binv, Binv from LDS
                 const double b0 = sBi[(r * 3 + 0) * kChunkLdK], b1 = sBi[(r * 3 + 1) * kChunkLdK], b2 = sBi[(r * 3 + 2) * kChunkLdK];
@@ -92,10 +80,7 @@ __device__ __forceinline__ void tangent_tets(const TangentArgs &ta, int chunk, L
         }
         tet_corner_forces(G, sBi, f);
         if (dir > 0) __syncthreads();      // the previous direction's reduction has read rows 0..11
-#pragma unroll
-        for (int c = 0; c < 12; ++c) sCf[c * kChunkLdK] = f[c];
-        __syncthreads();
-        chunk_reduce_store(sL, re, e0, g0, g1, r0, nrec, a.rec + (size_t)dir * ta.rec_stride);
+        chunk_out_store(co, sL, f, a.rec + (size_t)dir * ta.s.rec);
     }
 }
 
@@ -121,29 +106,22 @@ __global__ __launch_bounds__(256) void k_tangent(TangentArgs ta) {
         const double w2 = v.r_sc[t] / v.dt2;
         for (int dir = 0; dir < ta.n_vec; ++dir) {
             double dF[6], G[6];
-            tri_F(R, id, ta.d + (size_t)dir * ta.d_stride, dF);
+            tri_F(R, id, ta.d + (size_t)dir * ta.s.d, dF);
             tri_tangent_apply(Q, Si, itr, dF, G);
-            double *cf = a.r_cf + (size_t)dir * ta.rcf_stride;
+            double *cf = a.r_cf + (size_t)dir * ta.s.rcf;
 #pragma unroll
             for (int j = 0; j < 3; ++j) tri_corner_store(w2 * G[j], w2 * G[3 + j], R, cf + (size_t)j * v.ldr, v.ldr, t);
         }
     } else {
         const int t = (blk - a.nb_r) * 256 + tid;
         if (t >= v.nbend) return;
-        const int4 id = v.h_idx[t];
-        const int vid[4] = {id.x, id.y, id.z, id.w};
-        double c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = v.h_coef[(size_t)k * v.ldb + t];
-        const double ks = v.h_k[t];
+        int vid[4];
+        double c[4], ks;
+        hinge_load(v, t, c, vid, ks);
         for (int dir = 0; dir < ta.n_vec; ++dir) {
             double Dx[3];
-            hinge_Dx(c, vid, ta.d + (size_t)dir * ta.d_stride, Dx);
-            double *cf = a.h_cf + (size_t)dir * ta.hcf_stride;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) cf[(size_t)(3 * k + j) * v.ldb + t] = c[k] * (ks * Dx[j]);
+            hinge_Dx(c, vid, ta.d + (size_t)dir * ta.s.d, Dx);
+            hinge_corner_store(c, ks, Dx, a.h_cf + (size_t)dir * ta.s.hcf, v.ldb, t);
         }
     }
 }
@@ -154,7 +132,7 @@ struct TangentGatherArgs {
     ForceGatherArgs g;        // t_rec, r_cf, h_cf, f: direction 0
     const double *d, *m;      // [n_vec][3 nv], [3 nv]
     double shift;
-    size_t d_stride, rec_stride, rcf_stride, hcf_stride;
+    DirStrides s;
 };
 __global__ __launch_bounds__(256) void k_gather_tangent(TangentGatherArgs ta) {
     const ForceGatherArgs &a = ta.g;
@@ -162,15 +140,11 @@ __global__ __launch_bounds__(256) void k_gather_tangent(TangentGatherArgs ta) {
     const int s = wave_slice();
     if (s >= a.n_slices) return;
     const size_t dir = blockIdx.y;
-    const int r = s * 64 + lane;
-    const int v = r < a.nv ? a.order[r] : a.nv;
     double acc[3] = {0.0, 0.0, 0.0};
-    if (a.t_inc) gather_records(a.t_inc + a.t_ptr[s] + lane, a.t_w[s], a.t_rec + dir * ta.rec_stride, acc);
-    if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf + dir * ta.rcf_stride, a.r_ld, acc);
-    if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf + dir * ta.hcf_stride, a.h_ld, acc);
+    const int v = gather_vertex(a, s, lane, acc, dir, ta.s);
     if (v < a.nv) {
-        const double *dv = ta.d + dir * ta.d_stride;
-        double *out = a.f + dir * ta.d_stride;
+        const double *dv = ta.d + dir * ta.s.d;
+        double *out = a.f + dir * ta.s.d;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const size_t i = 3 * (size_t)v + j;
