@@ -87,6 +87,7 @@ SYMBOLS = [
     ("admm_hip_step", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.POINTER(Stats)]),
     ("admm_hip_local_step", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_global_solve", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int_p]),
+    ("admm_hip_regather_rhs", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p]),
     ("admm_hip_num_rows", C.c_int, [C.c_void_p]),
     ("admm_hip_solve_totals", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("admm_hip_energy", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),

@@ -884,6 +884,7 @@ int newton_args_ok(const char *who, double shift, int32_t flags) {
     return ADMM_HIP_OK;
 }
 
+template <bool REF = false>
 void launch_gather(admm_hip_ctx *c) {
     GatherArgs a{};
     a.nv = c->nv; a.n_slices = (c->nv + 63) / 64;
@@ -898,8 +899,8 @@ void launch_gather(admm_hip_ctx *c) {
     a.x = c->curr.p; a.Mxbar = c->Mxbar.p; a.b = c->b.p; a.add_mxbar = (c->rank == 0) ? 1 : 0;
     a.order = c->g_order.p; a.stop = c->stop_dev;
     const int grid = std::max(1, (a.n_slices + 3) / 4);
-    if (c->stop_dev) hipLaunchKernelGGL(k_gather_rhs<true>, dim3(grid), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_gather_rhs<false>, dim3(grid), dim3(256), 0, c->stream, a);
+    if (c->stop_dev) hipLaunchKernelGGL((k_gather_rhs<true, REF>), dim3(grid), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_gather_rhs<false, REF>), dim3(grid), dim3(256), 0, c->stream, a);
 }
 
 // in-place sum all-reduce of n doubles on the context's stream: RCCL, or the caller's transport staged through pinned host memory
@@ -3764,6 +3765,47 @@ int admm_hip_local_step(admm_hip_ctx *c, const double *x, double *u_inout, doubl
     HIP_TRY(hipStreamSynchronize(st));
     dev_to_rows(c, tu, ru, pu, hu, u_inout);
     dev_to_rows(c, tz, rz, pz, hz, z_out);
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_regather_rhs(admm_hip_ctx *c, const double *u_before, int32_t variant, double *b_out) {
+    if (!c || !b_out) return fail(ADMM_HIP_ERR_ARG, "regather_rhs: NULL argument");
+    if (c->cm.on) return fail(ADMM_HIP_ERR_STATE, "regather_rhs: kernel-level entry points work on the rows of the whole scene; this context holds only its rank's bodies (ADMM_HIP_PARTITION=elements)");
+    if (variant < 0 || variant > 3) return fail(ADMM_HIP_ERR_ARG, "regather_rhs: variant must be a combination of 1 (reference loop) and 2 (instantiation with the stop word)");
+    if (c->world > 1 || c->comm || c->ar_fn) return fail(ADMM_HIP_ERR_ARG, "regather_rhs: single-GPU contexts only");
+    if (c->npin_terms && !u_before) return fail(ADMM_HIP_ERR_ARG, "regather_rhs: a scene with pin terms needs u_before (the gather runs their local step)");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // the gather runs the local step of the pin terms: start it from the u the measured gather started from, and put back what that one left
+    const size_t np3 = 3 * (size_t)c->npin_terms;
+    std::vector<double> pu(np3), pu_keep(np3), pz_keep(np3), b_keep((size_t)c->n3);
+    if (np3) {
+        const double *r = u_before + 9 * (size_t)c->nt_total + 6 * (size_t)c->ntri_total + 3 * (size_t)c->nbend_total;
+        for (int p = 0; p < c->npin_terms; ++p)
+            for (int k = 0; k < 3; ++k) pu[3 * (size_t)p + k] = r[6 * (size_t)p + k];
+        HIP_TRY(hipMemcpyAsync(pu_keep.data(), c->pin_u.p, np3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(pz_keep.data(), c->pin_z.p, np3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->pin_u.p, pu.data(), np3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(b_keep.data(), c->b.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    {   // variant & 2: the instantiation a step with the early exit on the device launches, its stop word cleared as at the start of a step
+        struct StopDev { admm_hip_ctx *c; ~StopDev() { c->stop_dev = nullptr; } } stop_dev_guard{c};
+        if (variant & 2) {
+            HIP_TRY(hipMemsetAsync(c->counters.p + kCntAdmmStop, 0, sizeof(int), st));
+            c->stop_dev = c->counters.p + kCntAdmmStop;
+        }
+        if (variant & 1) launch_gather<true>(c);
+        else launch_gather<false>(c);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b_out, c->b.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));      // (the pageable copies above are staged: the host buffers are free to reuse)
+    HIP_TRY(hipMemcpyAsync(c->b.p, b_keep.data(), c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (np3) {
+        HIP_TRY(hipMemcpyAsync(c->pin_u.p, pu_keep.data(), np3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->pin_z.p, pz_keep.data(), np3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return ADMM_HIP_OK;
 }
 

@@ -704,6 +704,46 @@ __device__ __forceinline__ void gather_records(const int *__restrict__ inc, int 
     }
 }
 
+// The same sum with the whole list in flight (k_gather_rhs): gather_records waits one memory round trip per 4 records, and a
+// wave of the gather has nothing else to do meanwhile.  Here the indices of up to 32 records are issued at once
+// (gather_list_indices), and the records are then loaded 16 at a time (32 loads), so a list of width <= 16 costs one index
+// and one record round trip.  The adds are those of gather_records -- acc += rec[e_0], rec[e_1], ... in list order, padding
+// included -- hence the same bits.  w is wave-uniform: the guards are scalar branches, in steps of the width's granularity 4.
+constexpr int kGatherIdx = 32, kGatherBatch = 16;
+__device__ __forceinline__ void gather_list_indices(const int *__restrict__ inc, int w, int k0, int *e) {
+#pragma unroll
+    for (int g = 0; g < kGatherIdx; g += 4) {
+        if (k0 + g < w) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) e[g + i] = inc[64 * (k0 + g + i)];
+        }
+    }
+}
+__device__ __forceinline__ void gather_listed_records(const int *e, int w, int k0, __amdgpu_buffer_rsrc_t rr, double *acc) {
+#pragma unroll
+    for (int h = 0; h < kGatherIdx; h += kGatherBatch) {
+        if (k0 + h >= w) break;
+        union { double d[2]; bv4u v; } g0[kGatherBatch]; union { double d; bv2u v; } g1[kGatherBatch];
+#pragma unroll
+        for (int g = 0; g < kGatherBatch; g += 4) {
+            if (k0 + h + g < w) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    g0[g + i].v = __builtin_amdgcn_raw_buffer_load_b128(rr, e[h + g + i] * 32, 0, 0);
+                    g1[g + i].v = __builtin_amdgcn_raw_buffer_load_b64(rr, e[h + g + i] * 32 + 16, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < kGatherBatch; g += 4) {
+            if (k0 + h + g < w) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { acc[0] += g0[g + i].d[0]; acc[1] += g0[g + i].d[1]; acc[2] += g1[g + i].d; }
+            }
+        }
+    }
+}
+
 template <bool AOS>
 __device__ __forceinline__ void gather_corners(const int *__restrict__ inc, int w, const double *__restrict__ cf, int ld, double *acc) {
     constexpr int R = 8;
@@ -768,13 +808,53 @@ __device__ __forceinline__ void pin_term_update(const int *__restrict__ vert_pin
     }
 }
 
-template <bool STOP = false>
+// REF = the loop of gather_records, one round trip per 4 records: what the load schedule below is held to, bit for bit
+// (admm_hip_regather_rhs; tests only).
+template <bool STOP = false, bool REF = false>
 __global__ __launch_bounds__(256) void k_gather_rhs(GatherArgs a) {
     if (STOP && *a.stop) return;
     const int lane = threadIdx.x & 63;
     const int s = wave_slice();
     if (s >= a.n_slices) return;
-    {
+    if (!REF) {
+        // Everything whose address is known is issued before the first wait: the slice's offset and width together, then the
+        // record indices with order[r], then -- behind ONE wait -- the records with vert_pin[v] and M x_bar.
+        const int r = s * 64 + lane;
+        int tp = 0, tw = 0;
+        if (a.t_inc) { tp = a.t_ptr[s]; tw = a.t_w[s]; }
+        int e[kGatherIdx];
+        if (a.t_inc) gather_list_indices(a.t_inc + tp + lane, tw, 0, e);
+        const int v = r < a.nv ? a.order[r] : a.nv;
+        int pi = -1;
+        double mx[3] = {0.0, 0.0, 0.0};
+        if (v < a.nv) {
+            if (a.vert_pin) pi = a.vert_pin[v];
+            if (a.add_mxbar) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) mx[j] = a.Mxbar[3 * (size_t)v + j];
+            }
+        }
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (a.t_inc) {
+            const __amdgpu_buffer_rsrc_t rr = soa_rsrc(a.t_rec);
+            gather_listed_records(e, tw, 0, rr, acc);
+            for (int k0 = kGatherIdx; k0 < tw; k0 += kGatherIdx) {      // (a vertex in more than 32 records: further batches)
+                gather_list_indices(a.t_inc + tp + lane, tw, k0, e);
+                gather_listed_records(e, tw, k0, rr, acc);
+            }
+        }
+        if (a.r_inc) gather_corners<false>(a.r_inc + a.r_ptr[s] + lane, a.r_w[s], a.r_cf, a.r_ld, acc);
+        if (a.h_inc) gather_corners<false>(a.h_inc + a.h_ptr[s] + lane, a.h_w[s], a.h_cf, a.h_ld, acc);
+        if (v < a.nv) {
+            if (pi >= 0) pin_term_update(a.vert_pin, a.pin_xyz, a.pin_active, a.pin_u, a.pin_z, a.pin_sc, a.pin_nrm, a.x, v, a.add_mxbar != 0, acc);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double r = acc[j];
+                if (a.add_mxbar) r += mx[j];
+                a.b[3 * (size_t)v + j] = r;
+            }
+        }
+    } else {
         const int r = s * 64 + lane;
         const int v = r < a.nv ? a.order[r] : a.nv;
         double acc[3] = {0.0, 0.0, 0.0};

@@ -912,6 +912,17 @@ class Solver:
         check(lib().admm_hip_local_step(self._ctx, dptr(x), dptr(u), dptr(z), dptr(mx), dptr(b)))
         return (z, u, b) if Mxbar is not None else (z, u)
 
+    def regather_rhs(self, u_before=None, reference=False, stop_word=False):
+        """admm_hip_regather_rhs (tests): the right-hand side gathered again from what the last local_step left on the device -- by the
+        kernel the step launches, or by its reference instantiation (same sums, the loads of a list waited for four records at a time);
+        stop_word: the instantiations of a step with the early exit on the device.  u_before: the u handed to that local_step."""
+        self._need_ctx()
+        u = None if u_before is None else f64(u_before).ravel().copy()
+        assert u is None or u.size == self.num_rows()
+        b = np.zeros(self.m_x.size)
+        check(lib().admm_hip_regather_rhs(self._ctx, dptr(u), (1 if reference else 0) | (2 if stop_word else 0), dptr(b)))
+        return b
+
     def global_solve(self, b, x0):
         """LinearSolver::solve: returns (x, inner_iters)."""
         self._need_ctx()

@@ -275,6 +275,14 @@ int admm_hip_local_step(admm_hip_ctx *ctx, const double *x, double *u_inout, dou
 /* LinearSolver::solve (src/LinearSolver.hpp:46): x is in/out (warm start), returns inner iterations
  * through *iters.  Uses the context's linsolver, pins and obstacles. */
 int admm_hip_global_solve(admm_hip_ctx *ctx, const double *b, double *x_inout, int32_t *iters);
+/* Runs the gather of the right-hand side AGAIN on what the last admm_hip_local_step left on the device (no reference counterpart;
+ * tests): b = Mxbar + dt^2 D^T W^2 (z-u) into b_out [3 n_verts].  variant: 0 the kernel the step launches; | 1 its reference
+ * instantiation, which loads the records of a vertex four at a time and waits for each four -- the order of the sums is the same,
+ * so the two must agree bit for bit; | 2 the instantiations a step with the early exit on the device takes (they read the stop word
+ * of the ADMM loop, cleared here as at the start of a step).  The gather also runs the local step of the pin terms: u_before
+ * (the u handed to that admm_hip_local_step, reference row layout; may be NULL without pin terms) is where it starts from again.
+ * The context's own b, pin u and pin z are put back.  Single-GPU contexts only. */
+int admm_hip_regather_rhs(admm_hip_ctx *ctx, const double *u_before, int32_t variant, double *b_out);
 
 /* Totals of the on-chip PCG since admm_hip_create (no reference counterpart): solves launched, solves that met pcg_tol,
  * inner iterations.  Synchronises the context's stream.  Lets a caller run admm_hip_step WITHOUT per-step statistics
