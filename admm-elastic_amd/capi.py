@@ -96,6 +96,8 @@ SYMBOLS = [
     ("admm_hip_stiffness_apply", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.c_double, c_double_p]),
     ("admm_hip_stiffness_apply_ex", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.c_double, C.c_int32, c_double_p]),
     ("admm_hip_tangent_solve", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p]),
+    ("admm_hip_modes", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p,
+                                 c_double_p, c_double_p]),
     ("admm_hip_newton_polish", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_residuals", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_set_monitor", C.c_int, [C.c_void_p, C.c_int32]),

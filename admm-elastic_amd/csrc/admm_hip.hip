@@ -26,6 +26,7 @@
 #include "forces.hpp"
 #include "tangent.hpp"
 #include "newton.hpp"
+#include "modal.hpp"
 #include "anderson.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
@@ -426,6 +427,13 @@ struct admm_hip_ctx {
     int *nw_hstop = nullptr;      // pinned: the stop word as the host reads it between chunks
     hipEvent_t nw_ev[2] = {nullptr, nullptr};
     bool nw_ready = false;
+    // the frozen pass on a block of directions (newton.hpp: k_tangent_frozen_block; admm_hip_stiffness_apply_ex with ADMM_HIP_TANGENT_BLOCK,
+    // admm_hip_modes): the scratch of up to kModalNb directions and the columns of a blocked stiffness_apply_ex, allocated by the first call
+    ElemScratch bk_el; DevBuf<double> bk_d, bk_out;      // [n_vec][3 nv] each
+    // block eigensolver (modal.hpp; admm_hip_modes): buffers of their own, allocated by the first call
+    DevBuf<double> md_S, md_AS, md_theta, md_rpart, md_gpart, md_GA, md_GM, md_C;
+    DevBuf<ModalSt> md_st; int md_nbg = 0, md_tpb = 0;
+    bool md_ready = false;
     // Anderson acceleration of the ADMM loop (anderson.hpp; admm_hip_set_anderson): buffers of their own, allocated by the first step that
     // runs with a window, and again by a step with a larger one
     int aa_window = 0, aa_slots = 0, aa_n = 0;      // window in effect from the next step; ring slots allocated; records the last step wrote
@@ -878,9 +886,107 @@ int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int fl
     HIP_TRY(hipGetLastError());
     return ADMM_HIP_OK;
 }
-int newton_args_ok(const char *who, double shift, int32_t flags) {
+// ---- the frozen pass on a block of directions (newton.hpp), the block eigensolver (modal.hpp) ----
+DirStrides block_strides(const admm_hip_ctx *c) {      // (the sizes of ElemScratch::ensure)
+    return DirStrides{(size_t)c->n3, (size_t)4 * (c->n_rec + 1), (size_t)12 * c->ldr, (size_t)12 * c->ldb};
+}
+// out_j = K_frozen d_j + shift m o d_j (rows of held vertices zero), j < n_vec <= kModalNb; d, out: [n_vec][3 nv].  Column j has the bits
+// of launch_frozen on d_j.
+void launch_frozen_block(admm_hip_ctx *c, const double *d, double *out, int n_vec, double shift, const int *pin, const int *stop) {
+    FrozenBlockArgs b{};
+    b.fa = frozen_args(c, nullptr, d, 0, stop);
+    b.fa.f.rec = c->bk_el.rec.p; b.fa.f.r_cf = c->bk_el.rcf.p; b.fa.f.h_cf = c->bk_el.hcf.p;
+    b.n_vec = n_vec; b.s = block_strides(c);
+    const int nb = b.fa.f.nb_r + blocks_for(c->nbend);
+    if (nb > 0) hipLaunchKernelGGL(k_tangent_frozen_block, dim3(nb), dim3(256), 0, c->stream, b);
+    NewtonGatherBlockArgs q{};
+    q.n = newton_gather_args(c, b.fa, d, out, shift, pin, stop);
+    q.s = b.s;
+    hipLaunchKernelGGL(k_newton_gather_block, dim3(nw_blocks(c), n_vec), dim3(256), 0, c->stream, q);
+}
+hipError_t modal_ensure(admm_hip_ctx *c) {
+    if (c->md_ready) return hipSuccess;
+    hipError_t e;
+    hipStream_t st = c->stream;
+    if ((e = c->bk_el.ensure(c, kModalNb)) != hipSuccess) return e;
+    const size_t n = (size_t)std::max(1, c->n3), nbk = (size_t)nw_blocks(c);
+    const int tiles = (int)((n + kModalTile - 1) / kModalTile);
+    c->md_tpb = std::max(1, (tiles + 255) / 256);      // (at most 256 blocks of partials for k_modal_rr to sum)
+    c->md_nbg = (tiles + c->md_tpb - 1) / c->md_tpb;
+    if ((e = c->md_S.alloc_zeroed((size_t)kModalCols * n, st)) != hipSuccess) return e;
+    if ((e = c->md_AS.alloc_zeroed((size_t)kModalCols * n, st)) != hipSuccess) return e;
+    if ((e = c->md_theta.alloc_zeroed(kModalNb, st)) != hipSuccess) return e;
+    if ((e = c->md_rpart.alloc_zeroed((size_t)2 * kModalNb * nbk, st)) != hipSuccess) return e;
+    if ((e = c->md_gpart.alloc_zeroed((size_t)c->md_nbg * 2 * kModalPairs, st)) != hipSuccess) return e;
+    if ((e = c->md_GA.alloc_zeroed((size_t)kModalCols * kModalCols, st)) != hipSuccess) return e;
+    if ((e = c->md_GM.alloc_zeroed((size_t)kModalCols * kModalCols, st)) != hipSuccess) return e;
+    if ((e = c->md_C.alloc_zeroed((size_t)kModalCols * kModalNb, st)) != hipSuccess) return e;
+    if ((e = c->md_st.alloc(4)) != hipSuccess) return e;
+    c->md_ready = true;
+    return hipSuccess;
+}
+static_assert(kModalCols == admm_dev::kModalMax, "modal.hpp and device_math.hpp disagree on the widest block");
+ModalArgs modal_args(admm_hip_ctx *c, int k, int nb, double tol, int max_iters) {
+    ModalArgs a{};
+    a.nv = c->nv; a.n3 = c->n3; a.nb = nb; a.k = k;
+    a.nbk = nw_blocks(c); a.nbg = c->md_nbg; a.tpb = c->md_tpb;
+    a.S = c->md_S.p; a.AS = c->md_AS.p; a.m = c->m.p; a.dinv = c->nw_dinv.p;
+    a.theta = c->md_theta.p; a.rpart = c->md_rpart.p; a.gpart = c->md_gpart.p; a.GA = c->md_GA.p; a.GM = c->md_GM.p; a.C = c->md_C.p;
+    a.st = c->md_st.p; a.stop = c->nw_stop.p; a.tol = tol; a.max_iters = max_iters;
+    return a;
+}
+// the Rayleigh-Ritz on X alone: X becomes M-orthonormal, AX follows, Theta = the Ritz values
+void launch_modal_rr0(admm_hip_ctx *c, const ModalArgs &a, int init) {
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_modal_gram, dim3(a.nbg), dim3(256), 0, st, a, 0);
+    hipLaunchKernelGGL(k_modal_rr, dim3(1), dim3(256), 0, st, a, 0, 0, init);
+    hipLaunchKernelGGL(k_modal_update, dim3(std::max(1, blocks_for(a.n3))), dim3(256), 0, st, a, 0, 0);
+}
+// LOBPCG on the device; X (md_S) holds the start block on entry.  The host loop of tangent_solve_device: iterations in chunks of 8, one
+// chunk ahead of the device, one pinned word read per chunk.  Leaves X, Theta, the true residual partials (md_rpart) and the state st[2];
+// the caller synchronises.
+int modes_device(admm_hip_ctx *c, const double *xd, int k, int nb, double shift, int flags, double tol, int max_iters, const int *pin) {
+    hipStream_t st = c->stream;
+    const ModalArgs a = modal_args(c, k, nb, tol, max_iters);
+    const size_t n3 = (size_t)c->n3;
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(c->md_st.p, 0, 4 * sizeof(ModalSt), st));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    launch_frozen_block(c, a.S, a.AS, nb, shift, pin, nullptr);
+    launch_modal_rr0(c, a, 1);
+    const int nrow = std::max(1, blocks_for(a.n3));
+    constexpr int chunk = 8;
+    int launched = 0, chunks = 0;
+    while (launched < max_iters) {
+        const int n = std::min(chunk, max_iters - launched);
+        for (int it = launched; it < launched + n; ++it) {
+            hipLaunchKernelGGL(k_modal_resid, dim3(a.nbk), dim3(256), 0, st, a, 1);
+            launch_frozen_block(c, a.S + (size_t)nb * n3, a.AS + (size_t)nb * n3, nb, shift, pin, c->nw_stop.p);
+            hipLaunchKernelGGL(k_modal_gram, dim3(a.nbg), dim3(256), 0, st, a, 1);
+            hipLaunchKernelGGL(k_modal_rr, dim3(1), dim3(256), 0, st, a, it, 1, 0);
+            hipLaunchKernelGGL(k_modal_update, dim3(nrow), dim3(256), 0, st, a, it, 1);
+        }
+        launched += n;
+        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
+        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
+            if (c->nw_hstop[(chunks - 1) & 1]) break;
+        }
+        ++chunks;
+    }
+    // the returned X once more through the Rayleigh-Ritz (M-orthonormal to rounding) and the block pass: the TRUE residuals
+    launch_modal_rr0(c, a, 0);
+    launch_frozen_block(c, a.S, a.AS, nb, shift, pin, nullptr);
+    hipLaunchKernelGGL(k_modal_resid, dim3(a.nbk), dim3(256), 0, st, a, 2);
+    HIP_TRY(hipGetLastError());
+    return ADMM_HIP_OK;
+}
+int newton_args_ok(const char *who, double shift, int32_t flags, int32_t flag_max = 3) {
     if (!std::isfinite(shift)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": shift must be finite");
-    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
+    if (flag_max == 7 && (flags < 0 || flags > 7)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection), 2 (hold pinned vertices) and 4 (block pass)");
+    if (flags < 0 || flags > flag_max) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
     return ADMM_HIP_OK;
 }
 
@@ -3957,7 +4063,7 @@ int admm_hip_stiffness_apply(admm_hip_ctx *c, const double *x, int32_t n_vec, co
 // projected to their positive semi-definite part; bit 1: pinned vertices are held (their rows are zero, d is ignored there)
 int admm_hip_stiffness_apply_ex(admm_hip_ctx *c, const double *x, int32_t n_vec, const double *d, double shift, int32_t flags, double *out) {
     if (!c || !d || !out || n_vec < 1 || n_vec > 65535) return fail(ADMM_HIP_ERR_ARG, "stiffness_apply_ex: NULL argument, n_vec < 1 or n_vec > 65535");
-    if (int rc = newton_args_ok("stiffness_apply_ex", shift, flags)) return rc;
+    if (int rc = newton_args_ok("stiffness_apply_ex", shift, flags, 7)) return rc;
     const double *xd;
     if (int rc = eval_begin(c, "stiffness_apply_ex", x, &xd)) return rc;
     HIP_TRY(newton_ensure(c));
@@ -3965,6 +4071,20 @@ int admm_hip_stiffness_apply_ex(admm_hip_ctx *c, const double *x, int32_t n_vec,
     const int *pin = nullptr;
     if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
     launch_tangent_setup(c, xd, flags & 1);
+    if ((flags & 4) && c->n3) {      // all columns up in one copy, block passes in slabs of kModalNb directions, back in one copy
+        const size_t n = (size_t)n_vec * c->n3;
+        HIP_TRY(c->bk_el.ensure(c, std::min<int>(n_vec, kModalNb)));
+        if (c->bk_d.n < n) HIP_TRY(c->bk_d.alloc_zeroed(n, st));
+        if (c->bk_out.n < n) HIP_TRY(c->bk_out.alloc_zeroed(n, st));
+        HIP_TRY(hipMemcpyAsync(c->bk_d.p, d, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (pin) hipLaunchKernelGGL(k_nw_mask_block, dim3(nw_blocks(c), n_vec), dim3(256), 0, st, c->nv, (size_t)c->n3, pin, c->bk_d.p);
+        for (int j = 0; j < n_vec; j += kModalNb)
+            launch_frozen_block(c, c->bk_d.p + (size_t)j * c->n3, c->bk_out.p + (size_t)j * c->n3, std::min<int>(kModalNb, n_vec - j), shift, pin, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, c->bk_out.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return ADMM_HIP_OK;
+    }
     for (int j = 0; j < n_vec && c->n3; ++j) {
         HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, d + (size_t)j * c->n3, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_nw_mask, dim3(nw_blocks(c)), dim3(256), 0, st, c->nv, pin, c->nw_rhs.p, c->nw_p.p);
@@ -3996,6 +4116,58 @@ int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, 
     HIP_TRY(hipMemcpyAsync(&rr_true, c->nw_part.p + (size_t)3 * nw_blocks(c) + 2, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     info4[0] = h.it; info4[1] = h.conv; info4[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info4[3] = std::sqrt(h.bb);
+    return ADMM_HIP_OK;
+}
+
+// The k lowest eigenpairs of K_s phi = theta M phi on the free rows by LOBPCG on the device (modal.hpp); lambda = theta - shift
+int admm_hip_modes(admm_hip_ctx *c, const double *x, int32_t k, int32_t guard, double shift, int32_t flags, double tol, int32_t max_iters,
+                   const double *init, double *lambda, double *phi, double *info) {
+    if (!c || !lambda || !phi || !info) return fail(ADMM_HIP_ERR_ARG, "modes: NULL argument");
+    if (int rc = newton_args_ok("modes", shift, flags)) return rc;
+    if (k < 1 || guard < 0 || k + guard > kModalNb) return fail(ADMM_HIP_ERR_ARG, "modes: k >= 1, guard >= 0 and k + guard <= 16");
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "modes: tol must be finite and >= 0, max_iters >= 1");
+    const double *xd;
+    if (int rc = eval_begin(c, "modes", x, &xd)) return rc;
+    HIP_TRY(newton_ensure(c));
+    hipStream_t st = c->stream;
+    const int nb = k + guard;
+    const int *pin = nullptr;
+    long free_rows = c->n3;
+    if (flags & 2) {
+        launch_pin_mask(c); pin = c->nw_pin.p;
+        std::vector<int> hp((size_t)std::max(1, c->nv));
+        HIP_TRY(hipMemcpyAsync(hp.data(), c->nw_pin.p, (size_t)c->nv * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int v = 0; v < c->nv; ++v) free_rows -= hp[v] ? 3 : 0;
+    }
+    if ((long)3 * nb > free_rows) return fail(ADMM_HIP_ERR_ARG, "modes: 3 (k + guard) exceeds the number of free unknowns");
+    HIP_TRY(modal_ensure(c));
+    const size_t n3 = (size_t)c->n3;
+    HIP_TRY(hipMemsetAsync(c->md_S.p, 0, (size_t)kModalCols * n3 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(c->md_AS.p, 0, (size_t)kModalCols * n3 * sizeof(double), st));
+    if (init) HIP_TRY(hipMemcpyAsync(c->md_S.p, init, (size_t)nb * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    const ModalArgs a = modal_args(c, k, nb, tol, max_iters);
+    hipLaunchKernelGGL(k_modal_start, dim3(nw_blocks(c)), dim3(256), 0, st, a, pin, init ? 1 : 0);
+    if (int rc = modes_device(c, xd, k, nb, shift, flags, tol, max_iters, pin)) return rc;
+    ModalSt h;
+    const size_t nbk = (size_t)nw_blocks(c);
+    std::vector<double> part((size_t)2 * nb * nbk), th((size_t)nb);
+    HIP_TRY(hipMemcpyAsync(&h, c->md_st.p + 2, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(part.data(), c->md_rpart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(th.data(), c->md_theta.p, th.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(phi, c->md_S.p, (size_t)k * n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int met = 0;
+    for (int i = 0; i < k; ++i) {
+        double r2 = 0.0, mx2 = 0.0;
+        for (size_t b = 0; b < nbk; ++b) { r2 += part[(size_t)(2 * i) * nbk + b]; mx2 += part[(size_t)(2 * i + 1) * nbk + b]; }
+        const double den = std::fabs(th[i]) * std::sqrt(mx2);
+        info[4 + i] = den > 0.0 ? std::sqrt(r2) / den : std::sqrt(r2);
+        met += info[4 + i] <= tol ? 1 : 0;
+        lambda[i] = th[i] - shift;
+    }
+    const int ended = h.done ? h.ended : 1;
+    info[0] = h.it; info[1] = ended == 0 ? k : met; info[2] = h.restarts; info[3] = ended;
     return ADMM_HIP_OK;
 }
 

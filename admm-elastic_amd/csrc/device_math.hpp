@@ -1338,4 +1338,207 @@ __device__ __forceinline__ bool aa_small_solve(int n, const double *H, const dou
     return ok;
 }
 
+// ---- the dense Rayleigh-Ritz of the block eigensolver (modal.hpp: k_modal_rr) ----
+// G_A c = theta G_M c for symmetric G_A, G_M [n][n], n <= kModalMax, G_M positive definite: G_M is scaled to a unit diagonal and
+// factorised by Cholesky (right-looking), L^-1 G_A L^-T is diagonalised by a parallel cyclic Jacobi (round-robin pairing: n / 2 disjoint
+// rotations per stage, all row rotations of a stage, then all column rotations; sweeps until one rotates nothing, kModalSweeps at most),
+// the eigenvalues are sorted ascending
+// (ties by index) and C = D L^-T Q, so C^T G_M C = I and C^T G_A C = diag(ev).
+//
+// ONE text for the device and the host: the work is cut into PHASES of independent items; thread `tid` of `nt` takes the items tid,
+// tid + nt, ... of every phase and `sync` separates the phases.  The device passes its 256 threads and __syncthreads, the host replay
+// (tests/hostmath/modal_host.cpp) one thread and nothing: no item reads what another item of its phase writes, every entry sees the same
+// operations in the same order, so the serial replay IS the device's arithmetic.  Every operation is a single rounding (explicit fma).
+// Failure (false; ev and C zero): a diagonal of G_M or a Cholesky pivot that is not finite or below kModalPivot -- a multiple of eps
+// times the scaled diagonal, which is 1 -- or a non-finite result.
+constexpr int kModalMax = 48, kModalLd = 49;      // (an odd row stride: column accesses spread over the LDS banks)
+constexpr int kModalSweeps = 12;                          // at most; a sweep without a rotation ends the Jacobi iteration
+constexpr double kModalRotTol = 2.220446049250313e-16;      // |a_pq| <= eps sqrt(|a_pp a_qq|): no rotation
+constexpr double kModalPivot = 64.0 * 2.220446049250313e-16;
+struct ModalWork {            // the device keeps these in LDS
+    double *A, *M, *Q;        // [kModalMax][kModalLd]: G_A -> H -> C; G_M -> L (strict lower triangle); the rotations
+    double *ds, *dl, *ev, *cs;      // [kModalMax]: the scaling, L's diagonal, the eigenvalues; [kModalMax]: (c, s) of a stage's rotations
+    int *perm, *ok;           // [kModalMax]; [2]: the verdict, "this sweep rotated"
+};
+__device__ __forceinline__ bool modal_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (false for NaN)
+// the pair idx of stage `stage` of the round-robin over np (even) players; stage in [0, np - 1), idx in [0, np / 2)
+__device__ __forceinline__ void modal_pair(int np, int stage, int idx, int &p, int &q) {
+    const int r = np - 1;
+    if (idx == 0) { p = stage; q = r; }
+    else { p = stage + idx; p -= p >= r ? r : 0; q = stage - idx + r; q -= q >= r ? r : 0; }      // (both mod r)
+    if (p > q) { const int t = p; p = q; q = t; }
+}
+// the rotation that annihilates a_pq: (c, s) with a'_pj = c a_pj - s a_qj, a'_qj = s a_pj + c a_qj
+__device__ __forceinline__ bool modal_rotation(double app, double aqq, double apq, double &c, double &s) {
+    c = 1.0; s = 0.0;
+    if (fabs(apq) <= kModalRotTol * sqrt(fabs(app) * fabs(aqq))) return false;      // (a_pq = 0 included)
+    const double th = (aqq - app) / (2.0 * apq);
+    const double t = copysign(1.0, th) / (fabs(th) + sqrt(fma(th, th, 1.0)));
+    c = 1.0 / sqrt(fma(t, t, 1.0));
+    s = t * c;
+    return true;
+}
+template <class Sync>
+__device__ __forceinline__ bool modal_geneig(int n, const ModalWork &w, int tid, int nt, Sync sync) {
+    double *A = w.A, *M = w.M, *Q = w.Q;
+    const int ld = kModalLd;
+    // the scaling
+    for (int i = tid; i < n; i += nt) { const double d = M[i * ld + i]; w.ds[i] = 1.0 / sqrt(d); }
+    if (tid == 0) w.ok[0] = 1;
+    sync();
+    bool ok = true;
+    for (int i = 0; i < n; ++i) { const double d = M[i * ld + i]; ok = ok && d > 0.0 && modal_finite(d) && modal_finite(w.ds[i]); }
+    if (!ok) return false;
+    for (int e = tid; e < n * n; e += nt) {
+        const int i = e / n, j = e - i * n;
+        M[i * ld + j] = (M[i * ld + j] * w.ds[i]) * w.ds[j];
+        A[i * ld + j] = (A[i * ld + j] * w.ds[i]) * w.ds[j];
+        Q[i * ld + j] = i == j ? 1.0 : 0.0;
+    }
+    sync();
+    // Cholesky of M, right-looking: column j divided by its pivot, then the trailing lower triangle updated
+    for (int j = 0; j < n; ++j) {
+        const double d = M[j * ld + j];      // (every thread reads the same pivot: the verdict is uniform)
+        if (!(d >= kModalPivot) || !modal_finite(d)) return false;
+        const double l = sqrt(d);
+        for (int i = j + tid; i < n; i += nt) {
+            if (i == j) w.dl[j] = l;
+            else M[i * ld + j] = M[i * ld + j] / l;
+        }
+        sync();
+        const int r = n - 1 - j;
+        for (int e = tid; e < r * r; e += nt) {
+            const int i = j + 1 + e / r, k = j + 1 + e % r;
+            if (k <= i) M[i * ld + k] = fma(-M[i * ld + j], M[k * ld + j], M[i * ld + k]);
+        }
+        sync();
+    }
+    // Y = L^-1 A (a column per item), H = Y L^-T (a row per item)
+    for (int c = tid; c < n; c += nt)
+        for (int i = 0; i < n; ++i) {
+            double s = A[i * ld + c];
+            for (int k = 0; k < i; ++k) s = fma(-M[i * ld + k], A[k * ld + c], s);
+            A[i * ld + c] = s / w.dl[i];
+        }
+    sync();
+    for (int r = tid; r < n; r += nt)
+        for (int i = 0; i < n; ++i) {
+            double s = A[r * ld + i];
+            for (int k = 0; k < i; ++k) s = fma(-M[i * ld + k], A[r * ld + k], s);
+            A[r * ld + i] = s / w.dl[i];
+        }
+    sync();
+    for (int e = tid; e < n * n; e += nt) {
+        const int i = e / n, j = e - i * n;
+        if (i < j) { const double h = 0.5 * (A[i * ld + j] + A[j * ld + i]); A[i * ld + j] = h; A[j * ld + i] = h; }
+    }
+    sync();
+    // parallel cyclic Jacobi
+    const int np = (n + 1) & ~1, hp = np / 2;
+    for (int sweep = 0; sweep < kModalSweeps; ++sweep) {
+        if (tid == 0) w.ok[1] = 0;
+        sync();
+        for (int stage = 0; stage < np - 1; ++stage) {
+            for (int idx = tid; idx < hp; idx += nt) {
+                int p, q;
+                modal_pair(np, stage, idx, p, q);
+                double c = 1.0, s = 0.0;
+                if (q < n && modal_rotation(A[p * ld + p], A[q * ld + q], A[p * ld + q], c, s)) w.ok[1] = 1;      // (every writer stores 1)
+                w.cs[2 * idx] = c; w.cs[2 * idx + 1] = s;
+            }
+            sync();
+            for (int e = tid; e < hp * n; e += nt) {      // rows
+                const int idx = e / n, j = e - idx * n;
+                int p, q;
+                modal_pair(np, stage, idx, p, q);
+                if (q >= n) continue;
+                const double c = w.cs[2 * idx], s = w.cs[2 * idx + 1], x = A[p * ld + j], y = A[q * ld + j];
+                A[p * ld + j] = fma(c, x, -(s * y));
+                A[q * ld + j] = fma(s, x, c * y);
+            }
+            sync();
+            for (int e = tid; e < hp * n; e += nt) {      // columns, and the accumulated rotations
+                const int idx = e / n, i = e - idx * n;
+                int p, q;
+                modal_pair(np, stage, idx, p, q);
+                if (q >= n) continue;
+                const double c = w.cs[2 * idx], s = w.cs[2 * idx + 1];
+                double x = A[i * ld + p], y = A[i * ld + q];
+                A[i * ld + p] = fma(c, x, -(s * y));
+                A[i * ld + q] = fma(s, x, c * y);
+                x = Q[i * ld + p]; y = Q[i * ld + q];
+                Q[i * ld + p] = fma(c, x, -(s * y));
+                Q[i * ld + q] = fma(s, x, c * y);
+            }
+            sync();
+        }
+        const int rotated = w.ok[1];      // (read behind the stage's last barrier: uniform; the barrier below: before the next sweep clears it)
+        sync();
+        if (!rotated) break;
+    }
+    // ascending order (ties by index)
+    for (int i = tid; i < n; i += nt) w.ev[i] = A[i * ld + i];
+    sync();
+    for (int i = tid; i < n; i += nt) {
+        const double d = w.ev[i];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) { const double o = w.ev[j]; rank += (o < d || (o == d && j < i)) ? 1 : 0; }
+        w.perm[rank] = i;
+        if (!modal_finite(d)) w.ok[0] = 0;      // (a NaN ranks 0 in every item: the verdict below ends the call)
+    }
+    sync();
+    if (!w.ok[0]) return false;
+    // C = D L^-T Q[:, perm] into A (H is no longer needed; an item writes its own column and reads Q, L, ds, dl)
+    for (int r = tid; r < n; r += nt) {
+        const int src = w.perm[r];
+        bool fin = true;
+        for (int i = n - 1; i >= 0; --i) {
+            double s = Q[i * ld + src];
+            for (int k = i + 1; k < n; ++k) s = fma(-M[k * ld + i], A[k * ld + r], s);
+            A[i * ld + r] = s / w.dl[i];
+        }
+        for (int i = 0; i < n; ++i) { A[i * ld + r] *= w.ds[i]; fin = fin && modal_finite(A[i * ld + r]); }
+        if (!fin) w.ok[0] = 0;
+    }
+    sync();
+    return w.ok[0] != 0;
+}
+// The Rayleigh-Ritz of an iteration with its restart rule.  GA, GM [3 nb][3 nb] row-major (the upper triangle is read) for S = [X W P];
+// m = 3 nb with P, else 2 nb.  A failure on 3 nb columns is a RESTART: the leading 2 nb block ([X W], P dropped) is tried, *restarted = 1.
+// Returns the number of columns used (0: failure on [X W] as well); th [nb] ascending, Cout [3 nb][nb] row-major (rows >= the columns
+// used are zero), both zero on failure.
+template <class Sync>
+__device__ __forceinline__ int modal_rr(int nb, int m, const double *GA, const double *GM, const ModalWork &w, double *th, double *Cout,
+                                        int *restarted, int tid, int nt, Sync sync) {
+    const int m3 = 3 * nb, ld = kModalLd;
+    int used = 0;
+    if (tid == 0) *restarted = 0;
+    for (int attempt = 0; attempt < 2 && !used; ++attempt) {
+        const int n = attempt == 0 ? m : 2 * nb;
+        if (attempt == 1 && (m <= 2 * nb)) break;
+        for (int e = tid; e < n * n; e += nt) {
+            const int i = e / n, j = e - i * n, lo = i < j ? i : j, hi = i < j ? j : i;
+            w.A[i * ld + j] = GA[lo * m3 + hi];
+            w.M[i * ld + j] = GM[lo * m3 + hi];
+        }
+        sync();
+        if (modal_geneig(n, w, tid, nt, sync)) used = n;
+        else if (attempt == 0 && m > 2 * nb && tid == 0) *restarted = 1;
+        sync();
+    }
+    for (int e = tid; e < m3 * nb; e += nt) {
+        const int i = e / nb, j = e - i * nb;
+        Cout[e] = i < used ? w.A[i * ld + j] : 0.0;
+    }
+    for (int j = tid; j < nb; j += nt) th[j] = used ? w.ev[w.perm[j]] : 0.0;
+    sync();
+    return used;
+}
+// the default start block of the eigensolver: a fixed integer hash of (column, vertex, axis) mapped to (-1, 1)
+__device__ __forceinline__ double modal_start(unsigned col, unsigned vertex, unsigned axis) {
+    unsigned h = col * 0x9E3779B1u + vertex * 0x85EBCA77u + axis * 0xC2B2AE3Du;
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return ((double)h + 0.5) * 4.656612873077393e-10 - 1.0;      // (h + 1/2) 2^-31 - 1: exact in FP64
+}
+
 } // namespace admm_dev

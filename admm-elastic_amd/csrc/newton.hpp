@@ -280,6 +280,113 @@ __global__ __launch_bounds__(256) void k_newton_gather(NewtonGatherArgs na) {
     }
 }
 
+// ---- the frozen pass on a BLOCK of directions (admm_hip_stiffness_apply_ex with ADMM_HIP_TANGENT_BLOCK, modal.hpp) ----
+// k_tangent_frozen_block: the block ranges of k_tangent_frozen; an element's frame (tets: 30 doubles, triangles: 11, hinges: their
+// coefficients) is loaded ONCE and stays in registers across the loop over the directions, the way tangent_tets loops them: direction j
+// reads fa.d + j s.d and leaves its records / corner rows j strides further (ElemScratch::ensure(c, n_vec)); rows 0..11 of the LDS are
+// reused behind a block barrier.  Per direction the arithmetic and the summation orders are those of k_tangent_frozen, so column j has
+// the bits of the single pass on the same direction (tests/test_modes.py).
+struct FrozenBlockArgs {
+    FrozenArgs fa;            // fa.d: [n_vec][s.d]; f.rec, f.r_cf, f.h_cf: direction 0
+    int n_vec;
+    DirStrides s;
+};
+__global__ __launch_bounds__(256) void k_tangent_frozen_block(FrozenBlockArgs ba) {
+    __shared__ double sLm[12 * kChunkLdK];
+    const FrozenArgs &fa = ba.fa;
+    if (fa.stop && *fa.stop) return;
+    const ForceArgs &a = fa.f;
+    const ElemView &v = a.v;
+    const int blk = xcd_block(), tid = (int)threadIdx.x;
+    if (blk < a.nb_t) {
+        LdsDk *sL = (LdsDk *)sLm;
+        const ChunkLane ln = chunk_locate(v.kb, a.cb, blk, tid);
+        const int t = ln.t;
+        const ChunkOut co = chunk_out_begin(a.plan, blk, sL);
+        double U[9], N[9], Hs[6], ca[3], cb[3];
+        tet_frame_load(fa.t_fr, (size_t)v.ldt, t, U, N, Hs, ca, cb);
+        const int4 id = v.t_idx[t];
+        const int vid[4] = {id.x, id.y, id.z, id.w};
+#pragma unroll 1
+        for (int dir = 0; dir < ba.n_vec; ++dir) {
+            double Ds[9], f[12];
+            tet_edge_matrix(fa.d + (size_t)dir * ba.s.d, vid, Ds);
+            tet_frozen_apply(U, N, Hs, ca, cb, Ds, f);
+            if (dir > 0) __syncthreads();      // the previous direction's reduction has read rows 0..11
+            chunk_out_store(co, sL, f, a.rec + (size_t)dir * ba.s.rec);
+        }
+    } else if (blk < a.nb_r) {
+        const int t = (blk - a.nb_t) * 256 + tid;
+        if (t >= v.ntri) return;
+        const int4 id = v.r_idx[t];
+        double R[4], Q[6], Si[3];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) R[c] = v.r_rest[(size_t)c * v.ldr + t];
+        const double *fr = fa.r_fr + t;
+        const size_t ld = (size_t)v.ldr;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) Q[c] = fr[c * ld];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Si[c] = fr[(6 + c) * ld];
+        const double itr = fr[9 * ld], w2 = fr[10 * ld];
+#pragma unroll 1
+        for (int dir = 0; dir < ba.n_vec; ++dir) {
+            double dF[6], G[6];
+            tri_F(R, id, fa.d + (size_t)dir * ba.s.d, dF);
+            tri_tangent_apply(Q, Si, itr, dF, G);
+            double *cf = a.r_cf + (size_t)dir * ba.s.rcf;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) tri_corner_store(w2 * G[j], w2 * G[3 + j], R, cf + (size_t)j * v.ldr, v.ldr, t);
+        }
+    } else {
+        const int t = (blk - a.nb_r) * 256 + tid;
+        if (t >= v.nbend) return;
+        int vid[4];
+        double c[4], ks;
+        hinge_load(v, t, c, vid, ks);
+#pragma unroll 1
+        for (int dir = 0; dir < ba.n_vec; ++dir) {
+            double Dx[3];
+            hinge_Dx(c, vid, fa.d + (size_t)dir * ba.s.d, Dx);
+            hinge_corner_store(c, ks, Dx, a.h_cf + (size_t)dir * ba.s.hcf, v.ldb, t);
+        }
+    }
+}
+// k_newton_gather<false> on a block: blockIdx.y = direction; out_j = K d_j + shift m o d_j, rows of held vertices zero; no d . Kd partials
+struct NewtonGatherBlockArgs {
+    NewtonGatherArgs n;       // g.t_rec, g.r_cf, g.h_cf, g.f, d: direction 0 (part unused)
+    DirStrides s;
+};
+__global__ __launch_bounds__(256) void k_newton_gather_block(NewtonGatherBlockArgs ba) {
+    const NewtonGatherArgs &na = ba.n;
+    if (na.stop && *na.stop) return;
+    const ForceGatherArgs &a = na.g;
+    const int lane = threadIdx.x & 63;
+    const int s = wave_slice();
+    if (s >= a.n_slices) return;
+    const size_t dir = blockIdx.y;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int v = gather_vertex(a, s, lane, acc, dir, ba.s);
+    if (v < a.nv) {
+        const bool held = na.pin && na.pin[v] != 0;
+        const double *dv = na.d + dir * ba.s.d;
+        double *out = a.f + dir * ba.s.d;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            out[i] = held ? 0.0 : fma(na.shift * na.m[i], dv[i], acc[j]);
+        }
+    }
+}
+// d_j = 0 on the held vertices, in place; blockIdx.y = direction (k_nw_mask on a block)
+__global__ __launch_bounds__(256) void k_nw_mask_block(int nv, size_t stride, const int *__restrict__ pin, double *__restrict__ d) {
+    const int v = blockIdx.x * 256 + (int)threadIdx.x;
+    if (v >= nv || !pin || pin[v] == 0) return;
+    double *dj = d + (size_t)blockIdx.y * stride;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dj[3 * (size_t)v + j] = 0.0;
+}
+
 // ---- the vector kernels of the PCG: grid = blocks_for(nv), lane = vertex ----
 struct NwCg { double rz, rr, bb; int it, done, conv, pad_; };      // r . z, r . r, |rhs|^2 over the free rows; iterations done; ended; met its tolerance
 

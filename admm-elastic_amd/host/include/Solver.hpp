@@ -123,7 +123,14 @@ public:
     VecX stiffness_apply(const VecX &d, const VecX &x, double shift = 0.0);
     // The same from the tangent frozen at x (admm_hip_stiffness_apply_ex): psd projects every element tangent to its nearest positive
     // semi-definite one, hold_pins holds the pinned vertices (their rows are 0, d is ignored there)
-    VecX stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins);
+    // block: through the block pass (ADMM_HIP_TANGENT_BLOCK), the same bits
+    VecX stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins, bool block = false);
+    // The k lowest eigenpairs of (K(x) + shift M) phi = theta M phi on the free vertices by LOBPCG on the device (admm_hip_modes):
+    // returns phi, column i = mode i (three values per node, M-orthonormal, 0 on held vertices); info->lambda = theta - shift ascending.
+    // guard < 0 means min(4, 16 - k).  A body without held vertices needs shift > 0
+    struct ModesInfo { int iterations, converged_modes, restarts, ended_by; std::vector<double> lambda, residual; };
+    std::vector<VecX> modes(int k, const VecX &x, ModesInfo *info = nullptr, double shift = 0.0, bool psd = true, bool hold_pins = true,
+                            double tol = 1e-8, int max_iters = 2000, int guard = -1);
     // y with (K(x) + shift M) y = rhs on the free vertices: Jacobi-PCG on the device (admm_hip_tangent_solve); shift < 0 means 1 / dt^2
     struct SolveInfo { int iterations; bool converged; double residual, rhs_norm; };
     VecX tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info = nullptr, double shift = -1.0, bool psd = true, bool hold_pins = true,

@@ -673,12 +673,34 @@ VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift) {
     return out;
 }
 
-VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins) {
+VecX Solver::stiffness_apply(const VecX &d, const VecX &x, double shift, bool psd, bool hold_pins, bool block) {
     if (!initialized) throw std::runtime_error("Solver::stiffness_apply: initialize() first");
     if (x.rows() != m_x.rows() || d.rows() != m_x.rows()) throw std::runtime_error("Solver::stiffness_apply: x and d must hold three values per node");
     VecX out(m_x.rows());
-    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0);
+    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0) | (block ? ADMM_HIP_TANGENT_BLOCK : 0);
     check(admm_hip_stiffness_apply_ex((admm_hip_ctx *)m_ctx, x.data(), 1, d.data(), shift, flags, out.data()), "Solver::stiffness_apply");
+    return out;
+}
+
+std::vector<VecX> Solver::modes(int k, const VecX &x, ModesInfo *info, double shift, bool psd, bool hold_pins, double tol, int max_iters, int guard) {
+    if (!initialized) throw std::runtime_error("Solver::modes: initialize() first");
+    if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::modes: x must hold three values per node");
+    if (guard < 0) guard = std::max(0, std::min(4, 16 - k));
+    const size_t n = (size_t)m_x.rows(), kk = (size_t)std::max(1, k);
+    std::vector<double> lam(kk), phi(kk * n), inf(4 + kk, 0.0);
+    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0);
+    check(admm_hip_modes((admm_hip_ctx *)m_ctx, x.data(), (int32_t)k, (int32_t)guard, shift, flags, tol, (int32_t)max_iters, nullptr, lam.data(), phi.data(),
+                         inf.data()), "Solver::modes");
+    std::vector<VecX> out;
+    for (size_t i = 0; i < kk; ++i) {
+        VecX p(m_x.rows());
+        for (size_t r = 0; r < n; ++r) p[(int)r] = phi[i * n + r];
+        out.push_back(p);
+    }
+    if (info) {
+        info->iterations = (int)inf[0]; info->converged_modes = (int)inf[1]; info->restarts = (int)inf[2]; info->ended_by = (int)inf[3];
+        info->lambda = lam; info->residual.assign(inf.begin() + 4, inf.end());
+    }
     return out;
 }
 

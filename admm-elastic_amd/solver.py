@@ -642,12 +642,41 @@ class Solver:
         check(lib().admm_hip_stiffness_apply(self._ctx, dptr(xc), 1 if dc.ndim == 2 else dc.shape[0], dptr(dc), float(shift), dptr(out)))
         return out
 
-    def stiffness_apply_ex(self, d, x=None, shift=0.0, psd=False, hold_pins=False):
+    def modes(self, k, x=None, shift=0.0, psd=True, hold_pins=True, tol=1e-8, max_iters=2000, guard=None, init=None):
+        """admm_hip_modes: the k lowest eigenpairs of (K(x) + shift M) phi = theta M phi on the free vertices, K the tangent frozen at x
+        (default: the device-resident state), by LOBPCG with a Jacobi preconditioner on the device (csrc/modal.hpp); psd, hold_pins as
+        in stiffness_apply_ex.  Returns (lam [k] = theta - shift ascending, phi [k, n_verts, 3] M-orthonormal and 0 on held vertices,
+        info = dict(iterations, converged, converged_modes, restarts, ended_by in ("tol", "max_iters", "breakdown"), residual [k] =
+        |A phi_i - theta_i M phi_i| / (|theta_i| |M phi_i|) formed once more at the end, frequency_hz [k] = sqrt(max(lam, 0)) / 2 pi)).
+        guard=None means min(4, 16 - k) extra columns; k + guard <= 16.  init: None (a fixed start block) or [k + guard, n_verts, 3].
+        With psd=False the lowest modes of an indefinite state are the negative ones.  A body without held vertices needs shift > 0.
+        Bit-reproducible.  Single-GPU contexts."""
+        self._need_ctx()
+        xc = self._state_arg(x, "modes")
+        k = int(k)
+        if guard is None:
+            guard = max(0, min(4, 16 - k))
+        guard = int(guard)
+        ic = None
+        if init is not None:
+            ic = f64(init).copy()
+            if ic.shape != (k + guard, self.m_x.size // 3, 3):
+                raise ValueError("modes: init must be [k + guard, n_verts, 3]")
+        kk = max(k, 1)
+        lam = np.zeros(kk); phi = np.zeros((kk, self.m_x.size // 3, 3)); info = np.zeros(4 + kk)
+        check(lib().admm_hip_modes(self._ctx, dptr(xc), k, guard, float(shift), (1 if psd else 0) | (2 if hold_pins else 0), float(tol),
+                                   int(max_iters), dptr(ic), dptr(lam), dptr(phi), dptr(info)))
+        return lam, phi, dict(iterations=int(info[0]), converged=int(info[3]) == 0, converged_modes=int(info[1]), restarts=int(info[2]),
+                              ended_by=("tol", "max_iters", "breakdown")[int(info[3])], residual=info[4:].copy(),
+                              frequency_hz=np.sqrt(np.maximum(lam, 0.0)) / (2.0 * np.pi))
+
+    def stiffness_apply_ex(self, d, x=None, shift=0.0, psd=False, hold_pins=False, block=False):
         """admm_hip_stiffness_apply_ex: stiffness_apply from the tangent FROZEN at x (csrc/newton.hpp: one setup pass with the SVD, then
         one pass per direction).  psd replaces every element tangent by its nearest positive semi-definite one (an element that is
         positive semi-definite already keeps its bits); hold_pins holds the pinned vertices (the rule of `stationarity`): their rows of
         the result are 0 and d is ignored there.  With neither it is stiffness_apply in another summation order.  Shapes, sign, limits
-        and reproducibility as there.  Single-GPU contexts."""
+        and reproducibility as there.  block=True sends all directions through the block pass (one copy up, block passes of up to 16
+        directions, one copy back): the same bits.  Single-GPU contexts."""
         self._need_ctx()
         xc = self._state_arg(x, "stiffness_apply_ex")
         dc = f64(d).copy()
@@ -656,7 +685,7 @@ class Solver:
             raise ValueError("stiffness_apply_ex: d must be [n_verts, 3] or [k, n_verts, 3]")
         out = np.zeros(dc.shape)
         check(lib().admm_hip_stiffness_apply_ex(self._ctx, dptr(xc), 1 if dc.ndim == 2 else dc.shape[0], dptr(dc), float(shift),
-                                                (1 if psd else 0) | (2 if hold_pins else 0), dptr(out)))
+                                                (1 if psd else 0) | (2 if hold_pins else 0) | (4 if block else 0), dptr(out)))
         return out
 
     def tangent_solve(self, rhs, x=None, shift=None, psd=True, hold_pins=True, tol=1e-10, max_iters=1000):

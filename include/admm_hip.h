@@ -324,10 +324,35 @@ int admm_hip_stiffness_apply(admm_hip_ctx *ctx, const double *x, int32_t n_vec, 
  * modes of an element at rest).  ADMM_HIP_TANGENT_HOLD_PINS -- pinned vertices (the rule of `stationarity`: active pin terms, or the pins
  * of the sweeps under linsolver 1) are held: their rows of out are 0 and d is ignored there.  flags = 0 is admm_hip_stiffness_apply in
  * another summation order (measured: <= 2e-16 of its per-vertex scale).  Bit-reproducible; a column does not depend on the others.
- * Single-GPU contexts only.  Synchronises the stream. */
+ * Single-GPU contexts only.  Synchronises the stream.
+ * ADMM_HIP_TANGENT_BLOCK (this entry point only) -- all columns go up in one copy, through one setup and block passes of up to 16
+ * directions each (an element's frame is read once per pass, not once per direction), and come back in one copy.  Every column has the
+ * bits of the call without the flag. */
 #define ADMM_HIP_TANGENT_PSD 1
 #define ADMM_HIP_TANGENT_HOLD_PINS 2
+#define ADMM_HIP_TANGENT_BLOCK 4
 int admm_hip_stiffness_apply_ex(admm_hip_ctx *ctx, const double *x, int32_t n_vec, const double *d, double shift, int32_t flags, double *out);
+
+/* Modal analysis at a deformed state: the k lowest eigenpairs of K_s phi = theta M phi on the free rows, K_s = K_frozen(x) + shift M with
+ * the frozen tangent of admm_hip_stiffness_apply_ex (flags: ADMM_HIP_TANGENT_PSD, ADMM_HIP_TANGENT_HOLD_PINS), M = diag(m); held vertices
+ * are dropped as row and column.  lambda = theta - shift.  LOBPCG with the Jacobi preconditioner on a block of k + guard <= 16 columns
+ * (guard >= 0; a few guard columns speed up the k-th mode), all on the device (csrc/modal.hpp): per iteration a residual pass, ONE block
+ * frozen pass, the Gram matrices of [X W P] by per-block partials summed in a fixed order, a one-block dense Rayleigh-Ritz (Cholesky +
+ * parallel cyclic Jacobi) and the block update; iterations are enqueued in chunks of 8, the host reads one pinned word per chunk.  No
+ * floating-point atomics: bit-reproducible.  Stops when the columns 0 .. k-1 meet |A x_i - theta_i M x_i| <= tol |theta_i| |M x_i|, or
+ * after max_iters iterations.  A Cholesky pivot of the scaled Gram matrix that is not finite or below 64 eps is a restart (P dropped);
+ * a failure on [X W] as well ends the run (breakdown) with the last X.
+ * x: host positions, or NULL for the device-resident state.  init: NULL (a fixed integer hash of (column, vertex, axis): every caller
+ * starts identically) or [k + guard][3 n_verts].  lambda [k] ascending; phi [k][3 n_verts], M-orthonormal (the returned block passes a last
+ * Rayleigh-Ritz), 0 on held vertices; info [4 + k]: iterations, converged modes (k when the run ended by tol, else how many of the true
+ * residuals meet tol), restarts, ended-by (0 tol, 1 max_iters, 2 breakdown), then per mode the TRUE residual
+ * |A x_i - theta_i M x_i| / (|theta_i| |M x_i|) from one more block pass on the returned X.
+ * Without ADMM_HIP_TANGENT_PSD the operator may be indefinite (M is positive definite): the lowest eigenvalues are then the negative
+ * ones.  A body without held vertices needs shift > 0: its six rigid modes have theta = shift, and the relative stop test needs
+ * theta != 0.  Refused (ADMM_HIP_ERR_ARG): multi-GPU contexts, k < 1, guard < 0, k + guard > 16, 3 (k + guard) above the number of free
+ * unknowns, a non-finite shift or tol, tol < 0, max_iters < 1.  Synchronises the stream. */
+int admm_hip_modes(admm_hip_ctx *ctx, const double *x, int32_t k, int32_t guard, double shift, int32_t flags, double tol, int32_t max_iters,
+                   const double *init, double *lambda, double *phi, double *info);
 
 /* Solves (K(x) + shift M) y = rhs on the free vertices by Jacobi-preconditioned CG, matrix-free on the frozen tangent, on the context's
  * stream.  x as above; rhs and y [3 n_verts] host; flags as above (on held vertices y = 0 and rhs is ignored).  Stops at
