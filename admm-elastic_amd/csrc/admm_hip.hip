@@ -26,6 +26,7 @@
 #include "forces.hpp"
 #include "tangent.hpp"
 #include "newton.hpp"
+#include "adjoint.hpp"
 #include "modal.hpp"
 #include "anderson.hpp"
 #include "pcg_onchip2.hpp"
@@ -434,6 +435,9 @@ struct admm_hip_ctx {
     DevBuf<double> md_S, md_AS, md_theta, md_rpart, md_gpart, md_GA, md_GM, md_C;
     DevBuf<ModalSt> md_st; int md_nbg = 0, md_tpb = 0;
     bool md_ready = false;
+    // adjoint of a step (adjoint.hpp; admm_hip_param_sensitivity, admm_hip_step_adjoint): buffers of their own, allocated by the first call
+    DevBuf<double> adj_a, adj_ps, adj_l, adj_out;      // the stack [kSensCols][3 nv]; its sensitivities; Lx, Lv [2][3 nv]; the gradients [4][3 nv]
+    bool adj_ready = false;
     // Anderson acceleration of the ADMM loop (anderson.hpp; admm_hip_set_anderson): buffers of their own, allocated by the first step that
     // runs with a window, and again by a step with a larger one
     int aa_window = 0, aa_slots = 0, aa_n = 0;      // window in effect from the next step; ring slots allocated; records the last step wrote
@@ -990,6 +994,53 @@ int newton_args_ok(const char *who, double shift, int32_t flags, int32_t flag_ma
     return ADMM_HIP_OK;
 }
 
+// ---- adjoint of a step (adjoint.hpp) ----
+hipError_t adjoint_ensure(admm_hip_ctx *c) {
+    if (c->adj_ready) return hipSuccess;
+    hipError_t e;
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)std::max(1, c->n3);
+    if ((e = c->adj_a.alloc_zeroed((size_t)kSensCols * n, st)) != hipSuccess) return e;
+    if ((e = c->adj_ps.alloc_zeroed((size_t)kSensCols * ((size_t)4 * c->ldt + c->ldr + c->ldb) + 1, st)) != hipSuccess) return e;
+    if ((e = c->adj_l.alloc_zeroed(2 * n, st)) != hipSuccess) return e;
+    if ((e = c->adj_out.alloc_zeroed(4 * n, st)) != hipSuccess) return e;
+    c->adj_ready = true;
+    return hipSuccess;
+}
+// adj_ps = a_j^T df/dtheta per term at x (device) for the k <= kSensCols vectors a [k][stride] (device)
+void launch_param_sens(admm_hip_ctx *c, const double *x, const double *a, size_t stride, int k) {
+    SensArgs s{};
+    s.f = force_args(c, x, c->f_el);      // (the scene and the chunk plan only: the pass writes no records)
+    s.f.rec = nullptr; s.f.r_cf = nullptr; s.f.h_cf = nullptr;
+    s.a = a; s.sa = stride; s.k = k;
+    s.o_t = c->adj_ps.p; s.o_r = s.o_t + (size_t)kSensCols * 4 * c->ldt; s.o_h = s.o_r + (size_t)kSensCols * c->ldr;
+    const int nb = s.f.nb_r + blocks_for(c->nbend);
+    if (nb <= 0) return;
+    if (c->spl_tab.p) hipLaunchKernelGGL(k_param_sens<true>, dim3(nb), dim3(256), 0, c->stream, s);
+    else hipLaunchKernelGGL(k_param_sens<false>, dim3(nb), dim3(256), 0, c->stream, s);
+}
+// the first k columns of adj_ps into h (the layout of the device buffer), on the stream; the caller synchronises
+hipError_t param_sens_download(const admm_hip_ctx *c, std::vector<double> &h, int k) {
+    const size_t ot = 0, orr = (size_t)kSensCols * 4 * c->ldt, oh = orr + (size_t)kSensCols * c->ldr;
+    const size_t n[3] = {(size_t)k * 4 * c->ldt, (size_t)k * c->ldr, (size_t)k * c->ldb}, o[3] = {ot, orr, oh};
+    for (int q = 0; q < 3; ++q)
+        if (n[q])
+            if (hipError_t e = hipMemcpyAsync(h.data() + o[q], c->adj_ps.p + o[q], n[q] * sizeof(double), hipMemcpyDeviceToHost, c->stream)) return e;
+    return hipSuccess;
+}
+// the k columns of adj_ps (downloaded into h) in the caller's term order; any output may be NULL
+void param_sens_unpermute(const admm_hip_ctx *c, const std::vector<double> &h, int k, double *out_tets, double *out_tris, double *out_bends) {
+    const double *ht = h.data(), *hr = ht + (size_t)kSensCols * 4 * c->ldt, *hh = hr + (size_t)kSensCols * c->ldr;
+    for (int j = 0; j < k; ++j) {
+        if (out_tets)
+            for (int n = 0; n < c->nt; ++n)
+                for (int q = 0; q < 4; ++q) out_tets[((size_t)j * c->nt_total + c->tet_perm[n]) * 4 + q] = ht[((size_t)j * 4 + q) * c->ldt + n];
+        if (out_tris)
+            for (int t = 0; t < c->ntri; ++t) out_tris[(size_t)j * c->ntri_total + c->tri_perm[t]] = hr[(size_t)j * c->ldr + t];
+        if (out_bends)
+            for (int t = 0; t < c->nbend; ++t) out_bends[(size_t)j * c->nbend_total + c->bend_perm[t]] = hh[(size_t)j * c->ldb + t];
+    }
+}
 template <bool REF = false>
 void launch_gather(admm_hip_ctx *c) {
     GatherArgs a{};
@@ -4240,6 +4291,88 @@ int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol,
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
+
+// ---- adjoint of a step (adjoint.hpp) ----
+// a_j^T df/dtheta per energy term at x (host, or NULL = the device-resident state): one k_param_sens pass per kSensCols columns
+int admm_hip_param_sensitivity(admm_hip_ctx *c, const double *x, int32_t k, const double *a, double *out_tets, double *out_tris, double *out_bends) {
+    if (!c || !a || k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "param_sensitivity: NULL argument, k < 1 or k > 65535");
+    const double *xd;
+    if (int rc = eval_begin(c, "param_sensitivity", x, &xd)) return rc;
+    HIP_TRY(adjoint_ensure(c));
+    hipStream_t st = c->stream;
+    const size_t n3 = (size_t)c->n3;
+    std::vector<double> h(c->adj_ps.n);
+    for (int j0 = 0; j0 < k; j0 += kSensCols) {
+        const int kk = std::min<int>(kSensCols, k - j0);
+        if (n3) HIP_TRY(hipMemcpyAsync(c->adj_a.p, a + (size_t)j0 * n3, (size_t)kk * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        launch_param_sens(c, xd, c->adj_a.p, n3, kk);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(param_sens_download(c, h, kk));
+        HIP_TRY(hipStreamSynchronize(st));
+        param_sens_unpermute(c, h, kk, out_tets ? out_tets + (size_t)j0 * c->nt_total * 4 : nullptr, out_tris ? out_tris + (size_t)j0 * c->ntri_total : nullptr,
+                             out_bends ? out_bends + (size_t)j0 * c->nbend_total : nullptr);
+    }
+    return ADMM_HIP_OK;
+}
+
+// The adjoint of the last step at the device-resident state (the formulas: adjoint.hpp).  flags bit 0: the solve uses the projected
+// tangent; bit 1: the parameter sensitivities of lambda are wanted.  info6: iterations, converged, |g_x - A lambda| / |g_x| formed once
+// more at the end, |g_x|, |r_free| of the state, the shift 1 / dt^2.
+int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL_dv, int32_t flags, double tol, int32_t max_iters, double *out_lambda,
+                          double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass, double *out_tets, double *out_tris,
+                          double *out_bends, double *info6) {
+    if (!c || !dL_dx || !info6) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: NULL argument");
+    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: flags must be a combination of 1 (positive semi-definite projection) and 2 (parameter sensitivities)");
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: tol must be finite and >= 0, max_iters >= 1");
+    if (int rc = mon_refuse(c, "step_adjoint")) return rc;      // (the rules of newton_polish: the adjoint is of the problem the polish solves)
+    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has colliders; contact is not part of the problem the adjoint differentiates");
+    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has strain-limited triangles; the forces ignore the limits");
+    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has slide pins");
+    if (int rc = quiesce(c)) return rc;
+    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    HIP_TRY(newton_ensure(c));
+    HIP_TRY(force_ensure(c, false, 0));
+    HIP_TRY(adjoint_ensure(c));
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    const size_t n3 = (size_t)c->n3;
+    const double idt = 1.0 / c->dt, idt2 = 1.0 / (c->dt * c->dt);
+    const bool params = (flags & 2) != 0;
+    double *Lx = c->adj_l.p, *Lv = dL_dv ? c->adj_l.p + std::max<size_t>(1, n3) : nullptr;
+    double *sums = c->nw_part.p + (size_t)3 * nb;      // [0] |r_free|^2, [2] the true residual of the solve
+    if (n3) {
+        HIP_TRY(hipMemcpyAsync(Lx, dL_dx, n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (Lv) HIP_TRY(hipMemcpyAsync(Lv, dL_dv, n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    launch_pin_mask(c);
+    // |r_free| of the state: the polish's own figure (its kernels, its bits); k_nw_grad's vector goes to adj_out, overwritten below
+    launch_forces(c, c->x.p, false, nullptr);
+    hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->adj_out.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+    hipLaunchKernelGGL(k_adj_rhs, dim3(nb), dim3(256), 0, st, nv, Lx, Lv, idt, c->nw_pin.p, c->nw_rhs.p);
+    if (int rc = tangent_solve_device(c, c->x.p, idt2, (flags & 1) | 2, tol, max_iters)) return rc;
+    hipLaunchKernelGGL(k_adj_out, dim3(nb), dim3(256), 0, st, nv, n3, c->nw_y.p, c->m.p, c->Mxbar.p, c->x.p, Lv, idt, c->nw_pin.p, c->adj_out.p);
+    if (params) launch_param_sens(c, c->x.p, c->nw_y.p, n3, 1);
+    HIP_TRY(hipGetLastError());
+    NwCg h;
+    double g2 = 0.0, rr_true = 0.0;
+    std::vector<double> hp(params ? c->adj_ps.n : 0);
+    double *outs[4] = {out_xbar, out_xprev, out_vprev, out_mass};
+    if (n3) {
+        if (out_lambda) HIP_TRY(hipMemcpyAsync(out_lambda, c->nw_y.p, n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        for (int q = 0; q < 4; ++q)
+            if (outs[q]) HIP_TRY(hipMemcpyAsync(outs[q], c->adj_out.p + q * n3, n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (params) HIP_TRY(param_sens_download(c, hp, 1));
+    HIP_TRY(hipMemcpyAsync(&h, c->nw_st.p + 2, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&rr_true, sums + 2, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (params) param_sens_unpermute(c, hp, 1, out_tets, out_tris, out_bends);
+    info6[0] = h.it; info6[1] = h.conv; info6[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info6[3] = std::sqrt(h.bb);
+    info6[4] = std::sqrt(g2); info6[5] = idt2;
     return ADMM_HIP_OK;
 }
 

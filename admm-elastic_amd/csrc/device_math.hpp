@@ -1074,6 +1074,25 @@ __device__ __forceinline__ double tet_energy_grad(int grp, int type, double mu, 
     for (int i = 0; i < 3; ++i) sg[i] = (use_abs && S[i] < 0.0) ? -g[i] : g[i];
     return psi;
 }
+// The derivative of tet_energy_grad's sg with respect to the constants a tet's Mat stores (adjoint.hpp: k_param_sens;
+// tests/hostmath/param_sens_host.cpp): sg as tet_energy_grad returns it, and dsg[3 p + i] = d sg_i / d theta_p, theta = (mu, la, kappa).
+// Every density above has a stretch gradient LINEAR in its stored (mu, la, kappa) -- stable Neo-Hookean too: la_s (J - alpha) =
+// la_s (J - 1) - 3/4 mu_s -- so the derivative is the kind's own eval at the unit parameter vectors; no density is restated.  kappa
+// reaches the three xu:: splines only (grp 4, type 0..2); a kind is never evaluated at parameters its own formula divides by (stable
+// Neo-Hookean at mu = la = 0).  The linear tet (its k is the factor on the energy) and the tabulated spline have no (mu, la, kappa) on
+// the device: their columns are exactly 0.  TABLE = false: for callers that hold no tabulated spline, as tet_tangent_coef.
+template <bool TABLE = true>
+__device__ __forceinline__ void tet_param_grad(int grp, int type, double mu, double la, double k, double kappa, const double *tab,
+                                               const double *S, double *sg, double *dsg) {
+    if (!TABLE && grp == 4 && type == 3) type = 0;      // (cannot occur: compiles the table path out)
+    (void)tet_energy_grad(grp, type, mu, la, k, kappa, tab, S, sg);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) dsg[q] = 0.0;
+    if (grp == 0 || (grp == 4 && type == 3)) return;
+    (void)tet_energy_grad(grp, type, 1.0, 0.0, k, 0.0, tab, S, dsg);
+    (void)tet_energy_grad(grp, type, 0.0, 1.0, k, 0.0, tab, S, dsg + 3);
+    if (grp == 4 && type < 3) (void)tet_energy_grad(grp, type, 0.0, 0.0, k, 1.0, tab, S, dsg + 6);
+}
 // Hs = {h00, h01, h02, h11, h12, h22}, al and be for the pairs (0,1), (0,2), (1,2), all in the frame of the signed SVD.
 // grp: the tet's model group (0 linear, 1 Neo-Hookean, 2 StVK, 3 co-rotated, 4 the dense-Hessian models by `type`, kernels.hpp: Mat)
 // TABLE = false: for callers that hold no tabulated spline (type 3 cannot occur) -- the table path and its registers are compiled out

@@ -139,6 +139,20 @@ public:
     // updated (admm_hip_newton_polish).  One record per iterate, the first is the state the step left
     struct NewtonRecord { double objective, grad_norm, cg_iterations, step, energy; };
     std::vector<NewtonRecord> newton_polish(int max_iters = 10, double grad_tol = 1e-8, double cg_tol = 1e-8, int cg_max = 500);
+    // a^T d forces / d theta per energy term at x (admm_hip_param_sensitivity): tets [n_tets][4] = (d_mu, d_la, d_kappa, d_scale) in the
+    // order of energyterms, tris [n_tris], hinges [n_hinges]; d_scale, tris and hinges: the derivative in a factor on the term's energy
+    struct ParamSensitivity { std::vector<double> tets, tris, hinges; };
+    ParamSensitivity param_sensitivity(const VecX &a, const VecX &x);
+    // The adjoint of the last step() at its result (admm_hip_step_adjoint): for a loss L(x, v) with dL_dx, dL_dv (empty: 0) the
+    // multiplier lam of (K(x) + M / dt^2) lam = dL_dx + dL_dv / dt on the free rows and the gradients dL/dx_bar, dL/dx_prev, dL/dv_prev,
+    // dL/dm (per degree of freedom) and, with params, lam^T d forces / d theta.  x_prev and v_prev are the dL_dx and dL_dv
+    // contributions of the step before: several steps chain through them.  stationarity: |r_free| of the state
+    struct StepAdjoint {
+        VecX lam, xbar, x_prev, v_prev, masses; ParamSensitivity params;
+        int iterations; bool converged; double residual, rhs_norm, stationarity, shift;
+    };
+    StepAdjoint step_adjoint(const VecX &dL_dx, const VecX &dL_dv = VecX(), bool psd = false, double tol = 1e-10, int max_iters = 2000,
+                             bool params = true);
     // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)
@@ -154,6 +168,7 @@ protected:
     void *m_ctx;                                                  // admm_hip_ctx
     bool initialized;
     int m_n_tets;                                                 // tet terms handed to the context at initialize()
+    int m_n_tris = 0, m_n_bends = 0;                              // triangle and hinge terms
     Settings m_settings;
     RuntimeData m_runtime;
     std::vector<AdmmRecord> m_history;

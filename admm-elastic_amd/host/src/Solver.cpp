@@ -515,7 +515,7 @@ bool Solver::initialize(const Settings &settings_) { // src/Solver.cpp:167-261
     d.vert_xyz = m_x.data();      // smooth coordinates for the coarse space of the on-chip PCG (the solve does not depend on them)
     flat.tabulate();              // user-defined xu::Spline objects -> device tables
     flat.fill(d);
-    m_n_tets = d.n_tets;
+    m_n_tets = d.n_tets; m_n_tris = d.n_tris; m_n_bends = d.n_bends;
     // pins that are not energy terms (linsolver 1) go through the in-sweep pin list
     std::vector<int32_t> gs_v; std::vector<double> gs_p, gs_n;
     if (m_settings.linsolver == 1) {
@@ -726,6 +726,31 @@ std::vector<Solver::NewtonRecord> Solver::newton_polish(int max_iters, double gr
     rec.resize(std::min((size_t)std::max(0, (int)n), rec.size()));
     check(admm_hip_get_state(ctx, m_x.data(), m_v.data()), "Solver::newton_polish");
     return rec;
+}
+
+Solver::ParamSensitivity Solver::param_sensitivity(const VecX &a, const VecX &x) {
+    if (!initialized) throw std::runtime_error("Solver::param_sensitivity: initialize() first");
+    if (x.rows() != m_x.rows() || a.rows() != m_x.rows()) throw std::runtime_error("Solver::param_sensitivity: x and a must hold three values per node");
+    ParamSensitivity out;
+    out.tets.assign((size_t)4 * m_n_tets, 0.0); out.tris.assign((size_t)m_n_tris, 0.0); out.hinges.assign((size_t)m_n_bends, 0.0);
+    check(admm_hip_param_sensitivity((admm_hip_ctx *)m_ctx, x.data(), 1, a.data(), out.tets.data(), out.tris.data(), out.hinges.data()), "Solver::param_sensitivity");
+    return out;
+}
+
+Solver::StepAdjoint Solver::step_adjoint(const VecX &dL_dx, const VecX &dL_dv, bool psd, double tol, int max_iters, bool params) {
+    if (!initialized) throw std::runtime_error("Solver::step_adjoint: initialize() first");
+    if (dL_dx.rows() != m_x.rows() || (dL_dv.rows() != 0 && dL_dv.rows() != m_x.rows())) throw std::runtime_error("Solver::step_adjoint: dL_dx and dL_dv must hold three values per node");
+    StepAdjoint r;
+    const int n = (int)m_x.rows();
+    r.lam = VecX(n); r.xbar = VecX(n); r.x_prev = VecX(n); r.v_prev = VecX(n); r.masses = VecX(n);
+    if (params) { r.params.tets.assign((size_t)4 * m_n_tets, 0.0); r.params.tris.assign((size_t)m_n_tris, 0.0); r.params.hinges.assign((size_t)m_n_bends, 0.0); }
+    double i6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int32_t flags = (psd ? ADMM_HIP_ADJOINT_PSD : 0) | (params ? ADMM_HIP_ADJOINT_PARAMS : 0);
+    check(admm_hip_step_adjoint((admm_hip_ctx *)m_ctx, dL_dx.data(), dL_dv.rows() ? dL_dv.data() : nullptr, flags, tol, (int32_t)max_iters, r.lam.data(),
+                                r.xbar.data(), r.x_prev.data(), r.v_prev.data(), r.masses.data(), params ? r.params.tets.data() : nullptr,
+                                params ? r.params.tris.data() : nullptr, params ? r.params.hinges.data() : nullptr, i6), "Solver::step_adjoint");
+    r.iterations = (int)i6[0]; r.converged = i6[1] != 0.0; r.residual = i6[2]; r.rhs_norm = i6[3]; r.stationarity = i6[4]; r.shift = i6[5];
+    return r;
 }
 
 std::vector<Solver::TetStress> Solver::stress(const VecX &x) {

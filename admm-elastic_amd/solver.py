@@ -720,6 +720,68 @@ class Solver:
         self.download()
         return [dict(objective=r[0], grad_norm=r[1], cg_iterations=int(r[2]), step=r[3], energy=r[4]) for r in rec[:min(n.value, cap)]]
 
+    def param_sensitivity(self, a, x=None):
+        """admm_hip_param_sensitivity: a^T d forces / d theta per energy term at x (default: the device-resident state), theta what a
+        user tunes (csrc/adjoint.hpp: k_param_sens).  a is [n_verts, 3] or [k, n_verts, 3]; returns dict(tets [.., n_tets, 4] = (d_mu,
+        d_la, d_kappa, d_scale), tris [.., n_tris], hinges [.., n_bends]) in the order the terms were added, with the leading axis of a.
+        With F = U diag(sigma) V^T, sg_i = s_i dpsi/de_i and A^ = U^T Ds(a) Binv V:  d_scale = a . f_e = -vol sum_i sg_i A^_ii (the
+        derivative in a factor on the tet's energy) and d_theta = -vol sum_i (d sg_i / d theta) A^_ii for the tet's stored mu, lambda
+        and kappa; sg is linear in them, so mu d_mu + la d_la + kappa d_kappa = d_scale for the six kinds that have them.  The linear
+        tet and the tabulated spline have none on the device: their three columns are exactly 0 (linear tet: d/dk_bulk = d_scale / k).
+        tris and hinges: sum_c a_c . f_{e,c}, the derivative in a factor on the term's energy (w^2; the hinge stiffness).  Sums over
+        groups of terms, such as one mu per add_tets call, are the caller's np.bincount over the per-term output.  Every column of a
+        stack equals that column alone, bit for bit.  Limits as forces(): kinks of the |sigma| kinds at a stretch of 0, J -> 0,
+        strain limits ignored.  Single-GPU contexts."""
+        self._need_ctx()
+        xc = self._state_arg(x, "param_sensitivity")
+        ac = f64(a).copy()
+        nv = self.m_x.size // 3
+        if ac.ndim not in (2, 3) or ac.shape[-2:] != (nv, 3) or (ac.ndim == 3 and ac.shape[0] < 1):
+            raise ValueError("param_sensitivity: a must be [n_verts, 3] or [k, n_verts, 3]")
+        f = getattr(self, "_flat", None) or self.flatten()
+        lead = ac.shape[:-2]
+        tets = np.zeros(lead + (f["tet_idx"].shape[0], 4)); tris = np.zeros(lead + (f["tri_idx"].shape[0],))
+        hinges = np.zeros(lead + (f["bend_idx"].shape[0],))
+        check(lib().admm_hip_param_sensitivity(self._ctx, dptr(xc), 1 if ac.ndim == 2 else ac.shape[0], dptr(ac), dptr(tets), dptr(tris), dptr(hinges)))
+        return dict(tets=tets, tris=tris, hinges=hinges)
+
+    def step_adjoint(self, dL_dx, dL_dv=None, psd=False, tol=1e-10, max_iters=2000, params=True):
+        """admm_hip_step_adjoint: the adjoint of the last step at the device-resident state.  A converged step satisfies on the free rows
+        r = m o (x - x_bar) / dt^2 - f(x; theta) = 0 with x_bar = x_prev + dt v_prev + dt^2 a_ext and v = (x - x_prev) / dt.  For a loss
+        L(x, v) with dL_dx = dL/dx and dL_dv = dL/dv (None: 0), both [n_verts, 3]:
+            g_x = dL_dx + dL_dv / dt (held rows 0);  A lam = g_x,  A = K(x) + M / dt^2 on the free rows, lam = 0 on held rows
+            xbar = dL/dx_bar = m o lam / dt^2        x_prev = dL/dx_prev = m o lam / dt^2 - dL_dv / dt (held rows 0)
+            v_prev = dL/dv_prev = m o lam / dt       masses = dL/dm = -lam o (x - x_bar) / dt^2, per degree of freedom, x_bar held fixed
+            tets, tris, hinges = lam^T d forces / d theta, as param_sensitivity(lam) lays them out (params=True, else None)
+        Returns dict(lam, xbar, x_prev, v_prev, masses [n_verts, 3] each, tets, tris, hinges, info = dict(iterations, converged,
+        residual = |g_x - A lam| / |g_x| formed once more at the end, rhs_norm = |g_x|, stationarity = |r_free| of the state -- the
+        adjoint means something at a converged state only, see newton_polish -- and shift = 1 / dt^2)).  x_prev and v_prev of one call are
+        the dL_dx and dL_dv contributions of the step before it: that is how several steps chain (add the loss's own terms of that
+        frame).  Group sums, such as one mu per add_tets call, are the caller's np.bincount over the per-term output.  The solve is
+        tangent_solve's (Jacobi-PCG on the device, no host synchronisation inside).  psd=False is the exact tangent, the Jacobian,
+        positive definite on the free rows at a minimum; a CG breakdown ends with converged=False.  The state is not changed.  Limits
+        as forces(): kinks of the |sigma| kinds, J -> 0, strain limits ignored.  Refused for multi-GPU contexts, contexts with
+        colliders, strain-limited triangles or slide pins, and before the first step."""
+        self._need_ctx()
+        n3 = self.m_x.size
+        gx = f64(dL_dx).ravel().copy()
+        gv = None if dL_dv is None else f64(dL_dv).ravel().copy()
+        if gx.size != n3 or (gv is not None and gv.size != n3):
+            raise ValueError("step_adjoint: dL_dx and dL_dv must hold 3 values per node")
+        f = getattr(self, "_flat", None) or self.flatten()
+        vec = [np.zeros(n3) for _ in range(5)]
+        tets = np.zeros((f["tet_idx"].shape[0], 4)) if params else None
+        tris = np.zeros(f["tri_idx"].shape[0]) if params else None
+        hinges = np.zeros(f["bend_idx"].shape[0]) if params else None
+        info = np.zeros(6)
+        check(lib().admm_hip_step_adjoint(self._ctx, dptr(gx), dptr(gv), (1 if psd else 0) | (2 if params else 0), float(tol), int(max_iters),
+                                          dptr(vec[0]), dptr(vec[1]), dptr(vec[2]), dptr(vec[3]), dptr(vec[4]), dptr(tets), dptr(tris),
+                                          dptr(hinges), dptr(info)))
+        lam, xbar, xprev, vprev, mass = (q.reshape(-1, 3) for q in vec)
+        return dict(lam=lam, xbar=xbar, x_prev=xprev, v_prev=vprev, masses=mass, tets=tets, tris=tris, hinges=hinges,
+                    info=dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]),
+                              stationarity=float(info[4]), shift=float(info[5])))
+
     def residuals(self, x, z, z_prev):
         """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""
         self._need_ctx()

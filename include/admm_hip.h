@@ -378,6 +378,44 @@ int admm_hip_tangent_solve(admm_hip_ctx *ctx, const double *x, const double *rhs
 int admm_hip_newton_polish(admm_hip_ctx *ctx, int32_t max_newton, double grad_tol, double cg_tol, int32_t cg_max, int32_t cap, int32_t *n,
                            double *records);
 
+/* The derivative of the internal forces in what a user tunes, contracted with k vectors a [k][3 n_verts] (host): out = a_j^T df/dtheta
+ * per ENERGY TERM at x (host positions, or NULL for the device-resident state), in the order the terms were added (csrc/adjoint.hpp:
+ * k_param_sens; one pass per 16 columns, the SVD of a tet runs once per pass).
+ *   out_tets  [k][n_tets][4] = (d_mu, d_la, d_kappa, d_scale): the derivative in the tet's Lame constants and kappa AS THE LIBRARY STORES
+ *             THEM (tet_mu, tet_lambda, tet_kappa of the description) and in a factor on the tet's energy, d_scale = a . f_e.  With
+ *             F = U diag(sigma) V^T, sg_i = s_i dpsi/de_i and A^ = U^T Ds(a) Binv V:  d_scale = -vol sum_i sg_i A^_ii,
+ *             d_theta = -vol sum_i (d sg_i / d theta) A^_ii.  Every density's sg is linear in (mu, la, kappa), so for the six kinds with
+ *             such constants mu d_mu + la d_la + kappa d_kappa = d_scale.  The linear tet and the tabulated spline have none on the
+ *             device: their three columns are exactly 0 and d_scale carries everything (linear tet: d/dk_bulk = d_scale / k).
+ *   out_tris  [k][n_tris], out_bends [k][n_bends]: sum_c a_c . f_{e,c}, the derivative in a factor on the term's energy (w^2 of a
+ *             triangle, the stiffness of a hinge).
+ * Any output pointer may be NULL.  Sums over groups of terms (one mu per material) are the caller's.  Column j of a stack has the bits
+ * of a_j alone; no atomics: bit-reproducible.  Limits as admm_hip_forces (kinks of the |sigma| kinds, J -> 0, strain limits ignored).
+ * Single-GPU contexts only.  Synchronises the stream. */
+int admm_hip_param_sensitivity(admm_hip_ctx *ctx, const double *x, int32_t k, const double *a, double *out_tets, double *out_tris,
+                               double *out_bends);
+
+/* The adjoint of the LAST implicit-Euler step at the device-resident state x.  A converged step satisfies on the free rows (the rule of
+ * `stationarity`; held vertices do not move)  r = m o (x - x_bar) / dt^2 - f(x; theta) = 0,  x_bar = x_prev + dt v_prev + dt^2 a_ext,
+ * v = (x - x_prev) / dt.  For a scalar loss L(x, v) with dL_dx = dL/dx and dL_dv = dL/dv (NULL: 0), all [3 n_verts] host:
+ *     g_x = dL_dx + dL_dv / dt (held rows 0);   A lambda = g_x,  A = K(x) + M / dt^2 on the free rows, lambda = 0 on held rows
+ *     out_xbar  = dL/dx_bar  = m o lambda / dt^2            out_xprev = dL/dx_prev = m o lambda / dt^2 - dL_dv / dt (held rows 0)
+ *     out_vprev = dL/dv_prev = m o lambda / dt              out_mass  = dL/dm = -lambda o (x - x_bar) / dt^2 per degree of freedom (x_bar fixed)
+ *     out_tets, out_tris, out_bends = lambda^T df/dtheta as admm_hip_param_sensitivity lays them out (k = 1)
+ * out_xprev and out_vprev are the dL_dx and dL_dv contributions of the step BEFORE: several steps chain backwards through them.
+ * The solve is admm_hip_tangent_solve's (tol, max_iters; shift 1 / dt^2, pins held); flags: ADMM_HIP_ADJOINT_PSD -- the projected tangent
+ * (default off: the exact tangent is the Jacobian, positive definite on the free rows at a minimum; a CG breakdown ends with converged
+ * = 0); ADMM_HIP_ADJOINT_PARAMS -- the parameter outputs are computed (else untouched).  Any output pointer may be NULL.
+ * info6 = {iterations, converged, |g_x - A lambda| / |g_x| formed once more at the end, |g_x|, |r_free| of the state (the figure of
+ * `stationarity` and of the polish: an adjoint means something at a converged state only), the shift used}.  The state is not changed;
+ * one host synchronisation, at the end.  Refused like admm_hip_newton_polish (ADMM_HIP_ERR_ARG): multi-GPU contexts, contexts with
+ * colliders, with strain-limited triangles or with slide pins, and a state no step has run on. */
+#define ADMM_HIP_ADJOINT_PSD 1
+#define ADMM_HIP_ADJOINT_PARAMS 2
+int admm_hip_step_adjoint(admm_hip_ctx *ctx, const double *dL_dx, const double *dL_dv, int32_t flags, double tol, int32_t max_iters,
+                          double *out_lambda, double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass, double *out_tets,
+                          double *out_tris, double *out_bends, double *info6);
+
 /* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
  * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
 int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
