@@ -543,9 +543,17 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                     }
                 if (!true_residual(true, q, ri, bj)) { aborted = true; break; }      // (also hands back this row's b)
                 if (prof) a.prof[62 * 8 + 0] = wall_clock64();
+                // The copies of the entry x and r0 for the epilogue's pair.  The hot instances, with stored pairs, issue them under the grid barrier of
+                // the recycled sums below (six stores per row in front of the block sums sat in that barrier's drain).  The generic instances keep
+                // them here: <1024, generic> pays 30 more spilled VGPRs for the move, and <768, generic> gains nothing from it once the closing
+                // phase's pair is stored under its barrier (profiles/pcg2_closing_phase.txt).  Only this thread reads them back, in the epilogue.
+                // (written out at both places: as a shared lambda the stores cost <768, hot> two more spilled VGPRs)
+                constexpr bool kEntryCopiesUnderBarrier = HOT;
+                if (!kEntryCopiesUnderBarrier || cnt <= 0) {
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }      // (the entry x needs no copy: it stays in a.x until the epilogue has read it)
+                    for (int j = 0; j < 3; ++j) {
+                        if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }      // (the entry x needs no copy: it stays in a.x until the epilogue has read it)
+                    }
                 }
                 if (cnt > 0) {
                     __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void *)a.rc_part, 0, 72 * a.G * 8, 0x00020000);
@@ -571,11 +579,20 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         const double tot = block_sums24(q24);
                         if (tid < 24) oc_store_sc1(rs_r, ((24 * g24 + tid) * a.G + (int)blockIdx.x) * 8, tot);
                         if (g24 == 0) __syncthreads();      // red: the first round's totals are read before the second round's partials are written
-                                                            // (the second round's reads are followed by the block barrier of oc_barrier below)
+                                                            // (the second round's reads are followed by the block barrier of the grid barrier's arrival below)
                     }
                     if (prof) a.prof[62 * 8 + 1] = wall_clock64();
                     ++be;
-                    if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; }
+                    if (kEntryCopiesUnderBarrier) {
+                        // the arrival's drain orders this block's rc_part totals (write-through) in front of its arrival; the wait orders every
+                        // block's arrival before the loads of the totals below.  The entry copies in between wait for nobody.
+                        oc2_barrier_arrive(bar);
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) {
+                            if (live) { a.rc_xs[3 * (size_t)row + j] = rx[j]; a.rc_r0[3 * (size_t)row + j] = ri[j]; }
+                        }
+                        if (!oc_barrier_wait(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; }
+                    } else if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) { aborted = true; break; }
                     if (prof) a.prof[62 * 8 + 2] = wall_clock64();
                     double *sums = (double *)(smem + kOc2Scratch);   // [3 kRcS + 3 kRc] in the (idle) local vector
                     {   // every block adds the G partials of every sum in the same order; wave wv takes sums wv, wv + nw, ...:
@@ -1010,8 +1027,9 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     if (prof) a.prof[63 * 8 + 3] = wall_clock64();
 #undef OC2_STAMP
     // this solve's pair: e = x - x_entry, A e = r_entry - r_final (exact: u carries the true residual).  Formed BEFORE the end projection below,
-    // which moves x without updating r; STORED behind it: on this hardware a wave's loads return in order with its stores, so six stores per row
-    // in front of the projection's loads cost it 10 us (measured: ADMM_HIP_OC_PROF)
+    // which moves x without updating r; STORED behind the projection's loads: on this hardware a wave's loads return in order with its stores, so
+    // six stores per row in front of those loads cost it 10 us (measured: ADMM_HIP_OC_PROF).  With the projection they go out under its grid
+    // barrier, when those loads have been consumed (profiles/pcg2_closing_phase.txt); without it, as the kernel's last stores.
     // ALL global loads of the epilogue are issued here, before the first use of any (a wave's loads return in order): the pair's inputs, the
     // wave's modes for the dots (up to three of them), the row's own entries of every mode, G^-1.  As four dependent stages -- pair, G^-1 -> LDS,
     // first mode, second mode -- the same loads cost four round trips to HBM (ADMM_HIP_OC_PROF: 18.8 us for "pair stores + dots").
@@ -1096,7 +1114,20 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         // (this row's entries of Z for the update below stay in registers across the grid barrier)
         if (prof) a.prof[63 * 8 + 5] = wall_clock64();
         ++be;
-        if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) aborted = true;
+        // The closing grid barrier in its two halves.  The arrival's drain orders this block's defl_rec partials (write-through) in front of
+        // its arrival, hence in front of every block's reads of them behind the wait.
+        oc2_barrier_arrive(bar);
+        // THE PAIR'S STORES UNDER THE BARRIER'S LATENCY: the pair is complete, the projection never touches it, and every global load of the
+        // epilogue has been consumed (the drain above), so nothing of this phase queues behind the six stores per row.  Nothing of this
+        // launch reads the slots -- the next solve's recycled start does, ordered by the end of the kernel -- so no wait belongs to them.
+        // (the loads of the partials behind the wait return in order behind these stores: what that costs is the "reduce" stamp)
+        if (live && rc_on) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)row + j; a.rc_Eslot[i] = pe[j]; a.rc_Rslot[i] = pr[j]; }
+        }
+        // the wait orders every block's arrival (and the partials in front of it) before the loads of the partials below; a barrier given
+        // up leaves what it left before: the pair stored, x stored without the projection
+        if (!oc_barrier_wait(bar, be, a.G, ok_lds, a.sig)) aborted = true;
         else {
             if (prof) a.prof[63 * 8 + 6] = wall_clock64();
             // the blocks' sums, every block in the same order: wave w the quantities w, w + nw, ... (<= 8 of 96 with 12 waves), four blocks per lane
@@ -1149,7 +1180,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
             if (!HOT) a.u_out[3 * (size_t)vi + j] = ru[j];      // (D^-1 r_final: what k_rc_record and launch_deflation(have_resid) read after a launch-path solve.  Nothing reads it
                                                                 // after a solve that ran with the recycled start: it wrote its own pair and ends with its own projection)
         }
-        if (rc_on) {
+        if (rc_on && !proj) {      // (with the end projection: stored under its grid barrier, above)
 #pragma unroll
             for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)row + j; a.rc_Eslot[i] = pe[j]; a.rc_Rslot[i] = pr[j]; }
         }
