@@ -101,6 +101,8 @@ SYMBOLS = [
     ("admm_hip_newton_polish", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_param_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_step_adjoint", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_int32] + [c_double_p] * 9),
+    ("admm_hip_rest_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
+    ("admm_hip_adjoint_held", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_residuals", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_set_monitor", C.c_int, [C.c_void_p, C.c_int32]),
     ("admm_hip_get_monitor", C.c_int, [C.c_void_p, C.c_int32, c_int_p, c_double_p]),

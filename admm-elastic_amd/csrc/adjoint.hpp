@@ -24,6 +24,8 @@
 //             (amdgpu_waves_per_eu(4, 4) instead spilled 18 VGPRs; running the evaluations as one looped text hoisted every model's
 //             invariants out of the loop: 256 VGPRs.)  LDS is private to a thread here: no barrier.
 //   k_adj_rhs, k_adj_out the vector kernels around the solve (lane = vertex).
+//   k_rest_sens<TABLE>   a^T df/dX per REST vertex of the tets (the gradient in the rest shape), and
+//   k_adj_held           dL/dx of the held vertices, g - K lam on their rows: both described where they stand, below k_param_sens.
 //
 // REPRODUCIBLE to the bit: fixed summation orders, ordinary vector stores, no floating-point atomics.
 #pragma once
@@ -149,6 +151,92 @@ __global__ __launch_bounds__(256) void k_param_sens(SensArgs sa) {
             hinge_Dx(c, vid, sa.a + (size_t)j * sa.sa, Da);
             sa.o_h[(size_t)j * v.ldb + t] = -ks * fma(Dx[0], Da[0], fma(Dx[1], Da[1], Dx[2] * Da[2]));
         }
+    }
+}
+
+// a^T df/dX per rest vertex, X the rest positions behind the tets, for a stack of k <= kSensCols vectors a (masses and material
+// constants held fixed).  k_tangent's text with another 3x3 per column: the SVD, tet_energy_grad's sg and tet_tangent_coef run ONCE per
+// tet; per column A = Ds(a) Binv, Gs (device_math.hpp: tet_rest_grad), the corner contributions Gs Binv^T (tet_corner_forces) and the
+// chunk's way out into records, which k_gather_tangent (shift 0) sums per vertex in list order.  The whole block reaches every barrier:
+// a lane past its model's end redoes the last tet and parks zeros; the trip count sa.k is block-uniform.  Tets only: a context with
+// triangles or hinges is refused by the caller (their rest positions never reach the library).  No atomics; a column's arithmetic does
+// not depend on k.
+struct RestArgs {
+    ForceArgs f;              // the scene at x and the chunk plan; rec: column 0
+    const double *a;          // [k][sa] the multiplier vectors
+    size_t sa, srec;          // doubles between two of them, between two columns' records
+    int k;
+};
+template <bool TABLE>
+__global__ __launch_bounds__(256) void k_rest_sens(RestArgs ra) {
+    __shared__ double sLm[21 * kChunkLdK];      // rows 0..11: the chunk's corner contributions of one column; rows 12..20: Binv
+    const ForceArgs &a = ra.f;
+    const ElemView &v = a.v;
+    const int chunk = xcd_block(), tid = (int)threadIdx.x;
+    if (chunk >= a.nb_t) return;
+    LdsDk *sL = (LdsDk *)sLm;
+    const ChunkLane ln = chunk_locate(v.kb, a.cb, chunk, tid);
+    const int t = ln.t, grp = ln.grp;
+    LdsDk *sBi = sL + 12 * kChunkLdK + tid;      // row c of this thread: [c * kChunkLdK]
+    const ChunkOut co = chunk_out_begin(a.plan, chunk, sL);
+    const double w2 = v.t_sc[t] / v.dt2;
+    const Mat mt = v.mats[v.t_mat[t]];
+    const int4 id = v.t_idx[t];
+    const int vid[4] = {id.x, id.y, id.z, id.w};
+    double U[9], S[3], V[9];
+    {
+        double Bi[9], F[9];
+        tet_F_binv(v, id, t, F, Bi);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) sBi[c * kChunkLdK] = Bi[c];      // parked in this thread's LDS column for all the columns
+        signed_svd3(F, U, S, V);
+    }
+    const double *tab = v.spl + (size_t)(TABLE && grp == 4 && mt.type == 3 ? mt.table : 0) * kSplineTableDoubles;
+    double sg[3], Hs[6], ca[3], cb[3];
+    (void)tet_energy_grad(grp, (!TABLE && grp == 4 && mt.type == 3) ? 0 : mt.type, mt.mu, mt.la, mt.k, mt.kappa, tab, S, sg);
+    {
+        double al[3], be[3];
+        tet_tangent_coef<TABLE>(grp, mt.type, mt.mu, mt.la, mt.k, mt.kappa, tab, S, Hs, al, be);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { ca[q] = 0.5 * (al[q] + be[q]); cb[q] = 0.5 * (al[q] - be[q]); }
+    }
+    const double vol = w2 / mt.k;      // w = sqrt(k vol), src/TetEnergyTerm.cpp:46-47
+#pragma unroll 1
+    for (int j = 0; j < ra.k; ++j) {
+        double G[9], f[12];
+        {
+            double Ds[9], dF[9];
+            tet_edge_matrix(ra.a + (size_t)j * ra.sa, vid, Ds);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {      // A = Ds(a) Binv, Binv from LDS
+                const double b0 = sBi[(r * 3 + 0) * kChunkLdK], b1 = sBi[(r * 3 + 1) * kChunkLdK], b2 = sBi[(r * 3 + 2) * kChunkLdK];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) dF[r * 3 + i] = fma(Ds[i], b0, fma(Ds[3 + i], b1, Ds[6 + i] * b2));
+            }
+            tet_rest_grad(U, V, S, sg, Hs, ca, cb, dF, vol, G);
+        }
+        tet_corner_forces(G, sBi, f);
+        if (!ln.valid) {
+#pragma unroll
+            for (int c = 0; c < 12; ++c) f[c] = 0.0;
+        }
+        if (j > 0) __syncthreads();      // the previous column's reduction has read rows 0..11
+        chunk_out_store(co, sL, f, a.rec + (size_t)j * ra.srec);
+    }
+}
+
+// dL/dx of the held vertices: out = g - K lam on held rows with g = Lx + Lv / dt unmasked (Lv may be nullptr), 0 on free rows;
+// Kl = K(x) lam, the exact tangent without the mass shift
+__global__ __launch_bounds__(256) void k_adj_held(int nv, const double *__restrict__ Lx, const double *__restrict__ Lv, double idt, const int *__restrict__ pin,
+                                                  const double *__restrict__ Kl, double *__restrict__ out) {
+    const int v = blockIdx.x * 256 + (int)threadIdx.x;
+    if (v >= nv) return;
+    const bool held = pin[v] != 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const size_t i = 3 * (size_t)v + j;
+        const double g = Lv ? fma(idt, Lv[i], Lx[i]) : Lx[i];
+        out[i] = held ? g - Kl[i] : 0.0;
     }
 }
 

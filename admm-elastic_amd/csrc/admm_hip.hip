@@ -438,6 +438,9 @@ struct admm_hip_ctx {
     // adjoint of a step (adjoint.hpp; admm_hip_param_sensitivity, admm_hip_step_adjoint): buffers of their own, allocated by the first call
     DevBuf<double> adj_a, adj_ps, adj_l, adj_out;      // the stack [kSensCols][3 nv]; its sensitivities; Lx, Lv [2][3 nv]; the gradients [4][3 nv]
     bool adj_ready = false;
+    // gradients in the rest shape and in the held vertices (adjoint.hpp: k_rest_sens, k_adj_held; admm_hip_rest_sensitivity,
+    // admm_hip_adjoint_held): the records of up to kSensCols columns and their sums [rs_el.dirs][3 nv]; dL/dx of the held vertices [3 nv]
+    ElemScratch rs_el; DevBuf<double> rs_out, adj_h;
     // Anderson acceleration of the ADMM loop (anderson.hpp; admm_hip_set_anderson): buffers of their own, allocated by the first step that
     // runs with a window, and again by a step with a larger one
     int aa_window = 0, aa_slots = 0, aa_n = 0;      // window in effect from the next step; ring slots allocated; records the last step wrote
@@ -1018,6 +1021,32 @@ void launch_param_sens(admm_hip_ctx *c, const double *x, const double *a, size_t
     if (nb <= 0) return;
     if (c->spl_tab.p) hipLaunchKernelGGL(k_param_sens<true>, dim3(nb), dim3(256), 0, c->stream, s);
     else hipLaunchKernelGGL(k_param_sens<false>, dim3(nb), dim3(256), 0, c->stream, s);
+}
+// rs_out[j] = a_j^T df/dX per rest vertex at x (device) for the k <= kSensCols vectors a [k][3 nv] (device): tets only
+hipError_t rest_sens_ensure(admm_hip_ctx *c, int k) {
+    hipError_t e;
+    if ((e = c->rs_el.ensure(c, k)) != hipSuccess) return e;
+    const size_t n = (size_t)k * std::max(1, c->n3);
+    if (c->rs_out.n < n && (e = c->rs_out.alloc_zeroed(n, c->stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+void launch_rest_sens(admm_hip_ctx *c, const double *x, const double *a, int k) {
+    RestArgs r{};
+    r.f = force_args(c, x, c->rs_el);
+    r.a = a; r.sa = (size_t)c->n3; r.srec = (size_t)4 * (c->n_rec + 1); r.k = k;      // (the sizes of ElemScratch::ensure)
+    if (r.f.nb_t > 0) {
+        if (c->spl_tab.p) hipLaunchKernelGGL(k_rest_sens<true>, dim3(r.f.nb_t), dim3(256), 0, c->stream, r);
+        else hipLaunchKernelGGL(k_rest_sens<false>, dim3(r.f.nb_t), dim3(256), 0, c->stream, r);
+    }
+    TangentGatherArgs q{};
+    q.g = force_gather_args(c, r.f, c->rs_out.p);
+    q.d = a; q.m = c->m.p; q.shift = 0.0; q.s = DirStrides{r.sa, r.srec, 0, 0};
+    hipLaunchKernelGGL(k_gather_tangent, dim3(std::max(1, (q.g.n_slices + 3) / 4), k), dim3(256), 0, c->stream, q);
+}
+int rest_refuse(const admm_hip_ctx *c, const char *who) {
+    if (c->ntri_total > 0 || c->nbend_total > 0)
+        return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": the context has triangles or hinges; their rest positions do not reach the library, and a gradient of the tets alone would be partial");
+    return ADMM_HIP_OK;
 }
 // the first k columns of adj_ps into h (the layout of the device buffer), on the stream; the caller synchronises
 hipError_t param_sens_download(const admm_hip_ctx *c, std::vector<double> &h, int k) {
@@ -4373,6 +4402,59 @@ int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL
     if (params) param_sens_unpermute(c, hp, 1, out_tets, out_tris, out_bends);
     info6[0] = h.it; info6[1] = h.conv; info6[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info6[3] = std::sqrt(h.bb);
     info6[4] = std::sqrt(g2); info6[5] = idt2;
+    return ADMM_HIP_OK;
+}
+
+// a_j^T df/dX per rest vertex at x (host, or NULL = the device-resident state): one k_rest_sens pass per kSensCols columns
+int admm_hip_rest_sensitivity(admm_hip_ctx *c, const double *x, int32_t k, const double *a, double *out) {
+    if (!c || !a || !out || k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "rest_sensitivity: NULL argument, k < 1 or k > 65535");
+    if (int rc = mon_refuse(c, "rest_sensitivity")) return rc;
+    if (int rc = rest_refuse(c, "rest_sensitivity")) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, "rest_sensitivity", x, &xd)) return rc;
+    HIP_TRY(adjoint_ensure(c));
+    HIP_TRY(rest_sens_ensure(c, std::min<int>(k, kSensCols)));
+    hipStream_t st = c->stream;
+    const size_t n3 = (size_t)c->n3;
+    for (int j0 = 0; j0 < k; j0 += kSensCols) {
+        const int kk = std::min<int>(kSensCols, k - j0);
+        if (n3) HIP_TRY(hipMemcpyAsync(c->adj_a.p, a + (size_t)j0 * n3, (size_t)kk * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        launch_rest_sens(c, xd, c->adj_a.p, kk);
+        HIP_TRY(hipGetLastError());
+        if (n3) HIP_TRY(hipMemcpyAsync(out + (size_t)j0 * n3, c->rs_out.p, (size_t)kk * n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return ADMM_HIP_OK;
+}
+
+// dL/dx of the held vertices for the multiplier lam of admm_hip_step_adjoint, at the device-resident state: one k_tangent pass on lam
+// (the exact tangent, no mass shift, pins not masked), the pin mask, k_adj_held
+int admm_hip_adjoint_held(admm_hip_ctx *c, const double *lam, const double *dL_dx, const double *dL_dv, double *out_held) {
+    if (!c || !lam || !dL_dx || !out_held) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: NULL argument");
+    if (int rc = mon_refuse(c, "adjoint_held")) return rc;      // (the rules of step_adjoint: lam is its multiplier)
+    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has colliders; contact is not part of the problem the adjoint differentiates");
+    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has strain-limited triangles; the forces ignore the limits");
+    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has slide pins");
+    if (int rc = quiesce(c)) return rc;
+    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    HIP_TRY(newton_ensure(c));
+    HIP_TRY(adjoint_ensure(c));
+    HIP_TRY(tangent_ensure(c, 1));
+    hipStream_t st = c->stream;
+    const size_t n3 = (size_t)c->n3, ld = std::max<size_t>(1, n3);
+    if (!c->adj_h.p) HIP_TRY(c->adj_h.alloc_zeroed(ld, st));
+    double *Lx = c->adj_l.p, *Lv = dL_dv ? c->adj_l.p + ld : nullptr;
+    if (n3) {
+        HIP_TRY(hipMemcpyAsync(c->k_d.p, lam, n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(Lx, dL_dx, n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (Lv) HIP_TRY(hipMemcpyAsync(Lv, dL_dv, n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    launch_pin_mask(c);
+    launch_tangent(c, c->x.p, 1, 0.0);
+    hipLaunchKernelGGL(k_adj_held, dim3(nw_blocks(c)), dim3(256), 0, st, c->nv, Lx, Lv, 1.0 / c->dt, c->nw_pin.p, c->k_out.p, c->adj_h.p);
+    HIP_TRY(hipGetLastError());
+    if (n3) HIP_TRY(hipMemcpyAsync(out_held, c->adj_h.p, n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return ADMM_HIP_OK;
 }
 

@@ -1262,6 +1262,51 @@ __device__ __forceinline__ void tet_tangent_apply(const double *U, const double 
 #pragma unroll
         for (int r = 0; r < 3; ++r) ADMM_M3(dP, r, c) = fma(ADMM_M3(T, r, 0), ADMM_M3(V, c, 0), fma(ADMM_M3(T, r, 1), ADMM_M3(V, c, 1), ADMM_M3(T, r, 2) * ADMM_M3(V, c, 2)));
 }
+// The derivative of a tet's s = a . f_e = -vol P : A in its REST edge matrix Dm (Binv = Dm^-1; adjoint.hpp: k_rest_sens;
+// tests/hostmath/rest_sens_host.cpp), masses and material constants held fixed:  ds/dDm = Gs Binv^T with
+//     Gs = -vol [ (P : A) I - F^T T - A^T P ],    A = Ds(a) Binv (dF here),  T = H[A] the element tangent on A,
+// from dBinv = -Binv dDm Binv, dvol = vol tr(Binv dDm), dF = -F dDm Binv, dA = -A dDm Binv.  Formed in the frame of the signed SVD
+// F = U diag(S) V^T, where P = U diag(sg) V^T (tet_energy_grad) and T = U T^ V^T (the B of tet_tangent_apply on A^ = U^T A V):
+//     Gs = -vol V [ (sum_i sg_i A^_ii) I - diag(S) T^ - A^^T diag(sg) ] V^T
+// -- neither F nor P in full.  Hs, a, b: the coefficients as tet_tangent_apply takes them.  Gs column-major; the caller's
+// tet_corner_forces(Gs, Binv) gives rest corner m + 1 column m of Gs Binv^T and corner 0 minus their sum.
+__device__ __forceinline__ void tet_rest_grad(const double *U, const double *V, const double *S, const double *sg, const double *Hs, const double *a,
+                                              const double *b, const double *dF, double vol, double *Gs) {
+    double T[9], A[9], B[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(T, r, c) = fma(ADMM_M3(dF, r, 0), ADMM_M3(V, 0, c), fma(ADMM_M3(dF, r, 1), ADMM_M3(V, 1, c), ADMM_M3(dF, r, 2) * ADMM_M3(V, 2, c)));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(A, r, c) = fma(ADMM_M3(U, 0, r), ADMM_M3(T, 0, c), fma(ADMM_M3(U, 1, r), ADMM_M3(T, 1, c), ADMM_M3(U, 2, r) * ADMM_M3(T, 2, c)));
+    const double a0 = ADMM_M3(A, 0, 0), a1 = ADMM_M3(A, 1, 1), a2 = ADMM_M3(A, 2, 2);
+    ADMM_M3(B, 0, 0) = fma(Hs[0], a0, fma(Hs[1], a1, Hs[2] * a2));
+    ADMM_M3(B, 1, 1) = fma(Hs[1], a0, fma(Hs[3], a1, Hs[4] * a2));
+    ADMM_M3(B, 2, 2) = fma(Hs[2], a0, fma(Hs[4], a1, Hs[5] * a2));
+    ADMM_M3(B, 0, 1) = fma(a[0], ADMM_M3(A, 0, 1), b[0] * ADMM_M3(A, 1, 0)); ADMM_M3(B, 1, 0) = fma(a[0], ADMM_M3(A, 1, 0), b[0] * ADMM_M3(A, 0, 1));
+    ADMM_M3(B, 0, 2) = fma(a[1], ADMM_M3(A, 0, 2), b[1] * ADMM_M3(A, 2, 0)); ADMM_M3(B, 2, 0) = fma(a[1], ADMM_M3(A, 2, 0), b[1] * ADMM_M3(A, 0, 2));
+    ADMM_M3(B, 1, 2) = fma(a[2], ADMM_M3(A, 1, 2), b[2] * ADMM_M3(A, 2, 1)); ADMM_M3(B, 2, 1) = fma(a[2], ADMM_M3(A, 2, 1), b[2] * ADMM_M3(A, 1, 2));
+    const double pa = fma(sg[0], a0, fma(sg[1], a1, sg[2] * a2));      // P : A
+    // M = vol [ diag(S) T^ + A^^T diag(sg) - (P : A) I ]
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double m = fma(S[r], ADMM_M3(B, r, c), ADMM_M3(A, c, r) * sg[c]);
+            ADMM_M3(T, r, c) = vol * (r == c ? m - pa : m);
+        }
+    // Gs = V M V^T
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(B, r, c) = fma(ADMM_M3(V, r, 0), ADMM_M3(T, 0, c), fma(ADMM_M3(V, r, 1), ADMM_M3(T, 1, c), ADMM_M3(V, r, 2) * ADMM_M3(T, 2, c)));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ADMM_M3(Gs, r, c) = fma(ADMM_M3(B, r, 0), ADMM_M3(V, c, 0), fma(ADMM_M3(B, r, 1), ADMM_M3(V, c, 1), ADMM_M3(B, r, 2) * ADMM_M3(V, c, 2)));
+}
 
 // Triangle: E = w^2 / 2 sum (sigma_i - 1)^2 of the 3x2 F, P = w^2 (F - Q), Q = F C^(-1/2) the closest isometry (C = F^T F), so
 // dP = w^2 (dF - dQ).  With F = Q S (S = C^(1/2)):  dQ = om Q J + (dF - Q Q^T dF) S^-1,  J = [[0, -1], [1, 0]],

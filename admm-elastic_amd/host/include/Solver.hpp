@@ -153,6 +153,12 @@ public:
     };
     StepAdjoint step_adjoint(const VecX &dL_dx, const VecX &dL_dv = VecX(), bool psd = false, double tol = 1e-10, int max_iters = 2000,
                              bool params = true);
+    // d(a . forces)/dX per rest vertex at x, X the rest positions of the tets, masses and material constants held fixed
+    // (admm_hip_rest_sensitivity); three values per node.  Refused for scenes with triangles or hinges
+    VecX rest_sensitivity(const VecX &a, const VecX &x);
+    // dL/dx of the held vertices for the multiplier lam of step_adjoint with the same dL_dx, dL_dv (admm_hip_adjoint_held):
+    // (dL_dx + dL_dv / dt) - K(x) lam on the held rows, 0 on the free ones, at the result of the last step()
+    VecX adjoint_held(const VecX &lam, const VecX &dL_dx, const VecX &dL_dv = VecX());
     // the records of the last step(), one per EXECUTED ADMM iteration; empty with Settings::monitor = 0 and early exit off
     const std::vector<AdmmRecord> &admm_history() { return m_history; }
     // admm_hip_set_admm_stop after initialize(): in effect from the next step (tol = 0: off)

@@ -753,6 +753,23 @@ Solver::StepAdjoint Solver::step_adjoint(const VecX &dL_dx, const VecX &dL_dv, b
     return r;
 }
 
+VecX Solver::rest_sensitivity(const VecX &a, const VecX &x) {
+    if (!initialized) throw std::runtime_error("Solver::rest_sensitivity: initialize() first");
+    if (x.rows() != m_x.rows() || a.rows() != m_x.rows()) throw std::runtime_error("Solver::rest_sensitivity: x and a must hold three values per node");
+    VecX out(m_x.rows());
+    check(admm_hip_rest_sensitivity((admm_hip_ctx *)m_ctx, x.data(), 1, a.data(), out.data()), "Solver::rest_sensitivity");
+    return out;
+}
+
+VecX Solver::adjoint_held(const VecX &lam, const VecX &dL_dx, const VecX &dL_dv) {
+    if (!initialized) throw std::runtime_error("Solver::adjoint_held: initialize() first");
+    if (lam.rows() != m_x.rows() || dL_dx.rows() != m_x.rows() || (dL_dv.rows() != 0 && dL_dv.rows() != m_x.rows()))
+        throw std::runtime_error("Solver::adjoint_held: lam, dL_dx and dL_dv must hold three values per node");
+    VecX out(m_x.rows());
+    check(admm_hip_adjoint_held((admm_hip_ctx *)m_ctx, lam.data(), dL_dx.data(), dL_dv.rows() ? dL_dv.data() : nullptr, out.data()), "Solver::adjoint_held");
+    return out;
+}
+
 std::vector<Solver::TetStress> Solver::stress(const VecX &x) {
     if (!initialized) throw std::runtime_error("Solver::stress: initialize() first");
     if (x.rows() != m_x.rows()) throw std::runtime_error("Solver::stress: x must hold three values per node");

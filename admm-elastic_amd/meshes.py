@@ -95,6 +95,23 @@ def lumped_masses_tets(verts, tets, density=1522.0):
     return m
 
 
+def lumped_masses_tets_grad(verts, tets, dL_dm, density=1522.0):
+    """The chain rule of lumped_masses_tets: dL/dX [nv, 3] for a loss whose gradient in the nodal masses is dL_dm [nv] (step_adjoint's
+    `masses` summed over the three coordinates of a vertex).  m_v = rho / 4 sum_{e at v} vol_e with the signed volume of tet_volumes,
+    d vol / d v1 = (e2 x e3) / 6 and cyclic, d vol / d v0 = minus their sum."""
+    verts = np.asarray(verts, dtype=np.float64)
+    tets = np.asarray(tets)
+    dL_dm = np.asarray(dL_dm, dtype=np.float64).reshape(-1)
+    v0, v1, v2, v3 = (verts[tets[:, i]] for i in range(4))
+    e1, e2, e3 = v1 - v0, v2 - v0, v3 - v0
+    c = (density / 24.0) * dL_dm[tets].sum(axis=1)[:, None]      # dL/dvol_e / 6
+    g1, g2, g3 = c * np.cross(e2, e3), c * np.cross(e3, e1), c * np.cross(e1, e2)
+    out = np.zeros(verts.shape)
+    for i, g in enumerate((-(g1 + g2 + g3), g1, g2, g3)):
+        np.add.at(out, tets[:, i], g)
+    return out
+
+
 def lumped_masses_tris(verts, tris, density=1.0):
     v0, v1, v2 = (verts[tris[:, i]] for i in range(3))
     area = 0.5 * np.linalg.norm(np.cross(v1 - v0, v2 - v0), axis=1)

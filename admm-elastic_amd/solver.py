@@ -745,7 +745,27 @@ class Solver:
         check(lib().admm_hip_param_sensitivity(self._ctx, dptr(xc), 1 if ac.ndim == 2 else ac.shape[0], dptr(ac), dptr(tets), dptr(tris), dptr(hinges)))
         return dict(tets=tets, tris=tris, hinges=hinges)
 
-    def step_adjoint(self, dL_dx, dL_dv=None, psd=False, tol=1e-10, max_iters=2000, params=True):
+    def rest_sensitivity(self, a, x=None):
+        """admm_hip_rest_sensitivity: d(a . forces)/dX per rest vertex at x (default: the device-resident state), X the rest positions
+        behind add_tets(verts, ...), masses and material constants held fixed (csrc/adjoint.hpp: k_rest_sens).  a is [n_verts, 3] or
+        [k, n_verts, 3]; the result has the shape of a.  Per tet, with Binv = Dm^-1, F = Ds(x) Binv, P = dpsi/dF, A = Ds(a) Binv and
+        T = H[A] the exact element tangent on A:  d(a . f_e)/dDm = Gs Binv^T,  Gs = -vol [(P : A) I - F^T T - A^T P]; rest corner m + 1
+        gets column m, corner 0 minus their sum.  The columns sum to 0 over the vertices (a translation of the rest shape changes
+        nothing), and at x = X the result is stiffness_apply(a).  With a = lam of step_adjoint it is the rest-shape gradient of the
+        loss; masses lumped from the rest volumes chain through meshes.lumped_masses_tets_grad.  Every column of a stack equals that
+        column alone, bit for bit.  Limits as stiffness_apply().  Refused for multi-GPU contexts and for contexts that hold triangles
+        or hinges (their rest positions do not reach the library)."""
+        self._need_ctx()
+        xc = self._state_arg(x, "rest_sensitivity")
+        ac = f64(a).copy()
+        nv = self.m_x.size // 3
+        if ac.ndim not in (2, 3) or ac.shape[-2:] != (nv, 3) or (ac.ndim == 3 and ac.shape[0] < 1):
+            raise ValueError("rest_sensitivity: a must be [n_verts, 3] or [k, n_verts, 3]")
+        out = np.zeros(ac.shape)
+        check(lib().admm_hip_rest_sensitivity(self._ctx, dptr(xc), 1 if ac.ndim == 2 else ac.shape[0], dptr(ac), dptr(out)))
+        return out
+
+    def step_adjoint(self, dL_dx, dL_dv=None, psd=False, tol=1e-10, max_iters=2000, params=True, rest=False, held=False):
         """admm_hip_step_adjoint: the adjoint of the last step at the device-resident state.  A converged step satisfies on the free rows
         r = m o (x - x_bar) / dt^2 - f(x; theta) = 0 with x_bar = x_prev + dt v_prev + dt^2 a_ext and v = (x - x_prev) / dt.  For a loss
         L(x, v) with dL_dx = dL/dx and dL_dv = dL/dv (None: 0), both [n_verts, 3]:
@@ -761,7 +781,11 @@ class Solver:
         tangent_solve's (Jacobi-PCG on the device, no host synchronisation inside).  psd=False is the exact tangent, the Jacobian,
         positive definite on the free rows at a minimum; a CG breakdown ends with converged=False.  The state is not changed.  Limits
         as forces(): kinks of the |sigma| kinds, J -> 0, strain limits ignored.  Refused for multi-GPU contexts, contexts with
-        colliders, strain-limited triangles or slide pins, and before the first step."""
+        colliders, strain-limited triangles or slide pins, and before the first step.
+        rest=True adds rest = rest_sensitivity(lam) at the device state, dL/dX of the tets' rest positions [n_verts, 3] (refused as
+        rest_sensitivity is); held=True adds held = dL/dx of the held vertices, (dL_dx + dL_dv / dt) - K(x) lam on the held rows and 0
+        on the free ones (admm_hip_adjoint_held: K the exact tangent without the mass shift; any terms).  With both off the call and
+        its result are what they were."""
         self._need_ctx()
         n3 = self.m_x.size
         gx = f64(dL_dx).ravel().copy()
@@ -778,9 +802,16 @@ class Solver:
                                           dptr(vec[0]), dptr(vec[1]), dptr(vec[2]), dptr(vec[3]), dptr(vec[4]), dptr(tets), dptr(tris),
                                           dptr(hinges), dptr(info)))
         lam, xbar, xprev, vprev, mass = (q.reshape(-1, 3) for q in vec)
-        return dict(lam=lam, xbar=xbar, x_prev=xprev, v_prev=vprev, masses=mass, tets=tets, tris=tris, hinges=hinges,
-                    info=dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]),
-                              stationarity=float(info[4]), shift=float(info[5])))
+        out = dict(lam=lam, xbar=xbar, x_prev=xprev, v_prev=vprev, masses=mass, tets=tets, tris=tris, hinges=hinges,
+                   info=dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]),
+                             stationarity=float(info[4]), shift=float(info[5])))
+        if rest:
+            out["rest"] = self.rest_sensitivity(lam)
+        if held:
+            h = np.zeros(n3)
+            check(lib().admm_hip_adjoint_held(self._ctx, dptr(vec[0]), dptr(gx), dptr(gv), dptr(h)))
+            out["held"] = h.reshape(-1, 3)
+        return out
 
     def residuals(self, x, z, z_prev):
         """admm_hip_residuals: (|W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|) with z, z_prev in the reference's row layout (num_rows())."""

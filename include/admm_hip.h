@@ -416,6 +416,25 @@ int admm_hip_step_adjoint(admm_hip_ctx *ctx, const double *dL_dx, const double *
                           double *out_lambda, double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass, double *out_tets,
                           double *out_tris, double *out_bends, double *info6);
 
+/* The derivative of the internal forces in the REST positions X of the tets (the verts behind add_tets), contracted with k vectors
+ * a [k][3 n_verts] (host): out [k][3 n_verts] = d(a_j . f)/dX per rest vertex at x (host positions, or NULL for the device-resident
+ * state), masses and material constants held fixed (csrc/adjoint.hpp: k_rest_sens; one pass per 16 columns, the SVD of a tet runs once
+ * per pass).  Per tet, with Binv = Dm^-1, vol, F = Ds(x) Binv, P = dpsi/dF, A = Ds(a) Binv and T = H[A] (the exact element tangent):
+ *     d(a . f_e)/dDm = Gs Binv^T,   Gs = -vol [ (P : A) I - F^T T - A^T P ];   rest corner m + 1 gets column m, corner 0 minus their sum.
+ * With a = lambda of admm_hip_step_adjoint this is dL/dX, the gradient of inverse design.  A caller whose masses are lumped from the
+ * rest volumes adds the chain through out_mass.  Column j of a stack has the bits of a_j alone; no atomics: bit-reproducible.  Limits as
+ * admm_hip_stiffness_apply.  Refused (ADMM_HIP_ERR_ARG): multi-GPU contexts, and contexts that hold triangles or hinges -- the library is
+ * handed a triangle's rest matrix and a hinge's stencil, not the rest positions behind them, and a partial gradient is not returned.
+ * Synchronises the stream. */
+int admm_hip_rest_sensitivity(admm_hip_ctx *ctx, const double *x, int32_t k, const double *a, double *out);
+
+/* The gradient of admm_hip_step_adjoint's loss in the positions of the HELD vertices (where the pins hold them), at the device-resident
+ * state: with lam = out_lambda of admm_hip_step_adjoint for the same dL_dx, dL_dv (NULL: 0),
+ *     out_held = (dL_dx + dL_dv / dt) - K(x) lam   on the held rows,  0 on the free rows    ([3 n_verts], host)
+ * K the exact tangent of all terms without the mass shift (one admm_hip_stiffness_apply pass).  Refused exactly where
+ * admm_hip_step_adjoint is.  The state is not changed.  Synchronises the stream. */
+int admm_hip_adjoint_held(admm_hip_ctx *ctx, const double *lam, const double *dL_dx, const double *dL_dv, double *out_held);
+
 /* Kernel-level entry point (parity tests): x [3*n_verts], z and z_prev [admm_hip_num_rows] in the reference row layout (host).
  * out4 = |W(Dx - z)|, |W(z - z_prev)|, |W z|, |W D x|   (2-norms over all rows, pins included).  Single-GPU contexts only. */
 int admm_hip_residuals(admm_hip_ctx *ctx, const double *x, const double *z, const double *z_prev, double *out4);
