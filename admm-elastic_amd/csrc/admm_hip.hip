@@ -267,7 +267,7 @@ struct admm_hip_ctx {
     // general-mesh plan of the on-chip PCG (oc_plan.cpp): internal row order, its SELL, slab shares, two-level data
     double oc_sm_ab = 0.0, oc_sm_b = 0.0, oc_lam_bb = 0.0;   // block-local smoother of k_pcg2 (pcg_onchip2.hpp: smooth)
     bool oc_plan = false, oc_coarse = false; int oc_rows = 0, oc_bcols = 0, oc_nc = 0, oc_ncp = 0, oc_veclen = 0;
-    SellDev oc_A; DevBuf<int> oc_orig, oc_ldsoff, oc_wls, oc_haloptr, oc_halosrc; DevBuf<unsigned short> oc_col16;
+    SellDev oc_A; DevBuf<int> oc_orig, oc_ldsoff, oc_wls, oc_haloptr, oc_halosrc, oc_halovert; DevBuf<unsigned short> oc_col16;
     DevBuf<double> oc_mdiag, oc_ainv, oc_cbuf; DevBuf<float> oc_cwt; bool oc_affine = false;
     const double *create_xyz = nullptr;   // desc.vert_xyz, valid during admm_hip_create only (coarse space of the plan)
     int64_t oc_stat[6] = {0, 0, 0, 0, 0, 0};   // nnz, stored, on chip, block-local, max neighbour blocks, coarse unknowns
@@ -1191,7 +1191,7 @@ int launch_pcg2(admm_hip_ctx *c, const double *b, double *x, int max_iters, cons
     a.n_rows = c->oc_rows; a.n_slices = c->oc_A.n_slices;
     a.ptr = c->oc_A.ptr.p; a.w = c->oc_A.w.p; a.val = c->oc_A.val.p; a.col16 = c->oc_col16.p;
     a.lds_off = c->oc_ldsoff.p; a.wl_s = c->oc_wls.p; a.bcols = c->oc_bcols;
-    a.orig = c->oc_orig.p; a.halo_ptr = c->oc_haloptr.p; a.halo_src = c->oc_halosrc.p; a.vec_len = c->oc_veclen;
+    a.orig = c->oc_orig.p; a.halo_ptr = c->oc_haloptr.p; a.halo_src = c->oc_halosrc.p; a.halo_vert = c->oc_halovert.p; a.vec_len = c->oc_veclen;
     a.mdiag = c->oc_mdiag.p; a.dinv = c->dinv.p; a.b = b; a.x = x; a.u_out = c->cg_u.p;
     a.ubuf = c->oc_ubuf.p; a.part = c->oc_part.p; a.bar = c->oc_bar.p;
     a.nbr = c->oc_nbr.p; a.flags = c->oc_flags.p;
@@ -1293,6 +1293,9 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
                 {   // never empty: the kernel reads two entries per thread unconditionally guarded by nh
                     std::vector<int> hs(plan.halo_src); if (hs.empty()) hs.push_back(0);
                     if ((e = c->oc_halosrc.upload(hs)) != hipSuccess) return e;
+                    std::vector<int> hv(plan.halo_vert); hv.push_back(0);      // (the vertex of every entry: the entry residual's halo of x; one entry of
+                                                                               // padding: the kernel's two loads per thread are unconditional, at a clamped index)
+                    if ((e = c->oc_halovert.upload(hv)) != hipSuccess) return e;
                 }
                 if ((e = c->oc_mdiag.upload(plan.mdiag)) != hipSuccess) return e;
                 c->oc_coarse = plan.coarse_ok && plan.nc <= 2 * T;
@@ -5035,8 +5038,8 @@ int admm_host_assemble_matrix(const admm_hip_desc *d, int32_t *rowptr, int32_t *
     if (val) std::copy(A.val.begin(), A.val.end(), val);
     return ADMM_HIP_OK;
 }
-int admm_host_oc_plan(const admm_hip_desc *d, int32_t n_blocks, int32_t spb, int32_t lds_bytes, int32_t *row_vertex,
-                      int32_t *row_aggregate, double *coarse_inv, int64_t *stats, float *row_weights) {
+// the plan admm_hip_create would make for this description (admm_host_oc_plan, admm_host_oc_plan_halo)
+static int host_oc_plan_of(const admm_hip_desc *d, int32_t n_blocks, int32_t spb, int32_t lds_bytes, bool want_coarse, admm_host::OcPlan &P) {
     int rc = validate(d);
     if (rc) return rc;
     if (n_blocks < 1 || spb < 1 || spb > 16 || (int64_t)n_blocks * spb * 64 < d->n_verts) return fail(ADMM_HIP_ERR_ARG, "oc_plan: blocks x slices do not hold the vertices");
@@ -5048,8 +5051,25 @@ int admm_host_oc_plan(const admm_hip_desc *d, int32_t n_blocks, int32_t spb, int
     admm_host::Csr A = admm_host::assemble_Ahat(d->n_verts, dt, d->n_tets, d->tet_idx, d->tet_Binv, d->tet_weight, d->n_tris,
                                                       d->tri_idx, d->tri_rest, d->tri_weight, pins_as_terms ? d->n_pins : 0, d->pin_vert, pw);
     if (d->n_bends > 0) A = admm_host::add_stencil_terms(A, dt, d->n_bends, d->bend_idx, d->bend_coef, d->bend_weight);      // (the matrix admm_hip_create plans for)
-    const admm_host::OcPlan P = admm_host::build_oc_plan(A, d->masses, n_blocks, spb, lds_bytes, coarse_inv != nullptr, d->vert_xyz);
+    P = admm_host::build_oc_plan(A, d->masses, n_blocks, spb, lds_bytes, want_coarse, d->vert_xyz);
     if (!P.ok) return fail(ADMM_HIP_ERR_ARG, "oc_plan: a block does not fit its slots");
+    return ADMM_HIP_OK;
+}
+int admm_host_oc_plan_halo(const admm_hip_desc *d, int32_t n_blocks, int32_t spb, int32_t lds_bytes, int32_t *halo_ptr, int32_t *halo_src, int32_t *halo_vert) {
+    if (!halo_ptr) return fail(ADMM_HIP_ERR_ARG, "oc_plan_halo: halo_ptr is NULL");
+    admm_host::OcPlan P;
+    const int rc = host_oc_plan_of(d, n_blocks, spb, lds_bytes, false, P);
+    if (rc) return rc;
+    std::copy(P.halo_ptr.begin(), P.halo_ptr.end(), halo_ptr);
+    if (halo_src) std::copy(P.halo_src.begin(), P.halo_src.end(), halo_src);
+    if (halo_vert) std::copy(P.halo_vert.begin(), P.halo_vert.end(), halo_vert);
+    return ADMM_HIP_OK;
+}
+int admm_host_oc_plan(const admm_hip_desc *d, int32_t n_blocks, int32_t spb, int32_t lds_bytes, int32_t *row_vertex,
+                      int32_t *row_aggregate, double *coarse_inv, int64_t *stats, float *row_weights) {
+    admm_host::OcPlan P;
+    const int rc = host_oc_plan_of(d, n_blocks, spb, lds_bytes, coarse_inv != nullptr, P);
+    if (rc) return rc;
     if (row_vertex) std::copy(P.orig.begin(), P.orig.end(), row_vertex);
     if (row_weights) std::copy(P.cwt.begin(), P.cwt.end(), row_weights);
     if (row_aggregate)

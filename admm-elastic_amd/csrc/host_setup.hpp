@@ -129,6 +129,7 @@ struct OcPlan {
     std::vector<uint16_t> col16;        // local column of entry (slice s, column k, lane l) at slice_ptr[s] + ((k / 4) 64 + l) 4 + k % 4
     std::vector<double> mdiag;          // [3 n_rows] mass + diagonal of Ahat (0 for dummy rows)
     std::vector<int32_t> halo_ptr, halo_src;   // [G + 1], internal rows of the halo entries of every block (sorted)
+    std::vector<int32_t> halo_vert;     // the vertex of every halo entry, orig[halo_src[h]]: the entry x of a solve is read through it (k_pcg2)
     int32_t nh_max = 0, nh_cap = 0, vec_len = 0;   // largest halo, rounded up to 64, entries per axis of the local vector
     std::vector<int32_t> wl_s, lds_off; // [n_slices] columns of the slice kept in LDS, their offset (columns) in the block's slab
     int bcols = 0;                      // slab columns of the fullest block

@@ -258,6 +258,15 @@ OcPlan build_oc_plan(const Csr &A, const double *mass3, int G, int spb, int lds_
     }
     P.halo_src.reserve(P.halo_ptr[G]);
     for (int b = 0; b < G; ++b) P.halo_src.insert(P.halo_src.end(), halo[b].begin(), halo[b].end());
+    // ... and the vertex behind every entry: the x a solve starts from lies complete in global memory, by vertex, so the kernel reads the halo of
+    // its entry residual through this list instead of exchanging it.  A halo entry exists because a non-zero references it, and dummy rows have
+    // none: every source row is live (no plan otherwise: the kernel would index x with -1).
+    P.halo_vert.resize(P.halo_src.size());
+    for (size_t h = 0; h < P.halo_src.size(); ++h) {
+        const int32_t v = P.orig[P.halo_src[h]];
+        if (v < 0 || v >= nv) { P.ok = false; return P; }
+        P.halo_vert[h] = v;
+    }
     P.nh_cap = (P.nh_max + 63) / 64 * 64;
     if (T + P.nh_cap > 65535) { P.ok = false; return P; }
     // ---- SELL of the off-diagonal non-zeros: values + 16-bit local columns (own row = internal row - block base, halo

@@ -59,6 +59,7 @@ struct Oc2Args {
     int bcols;                       // slab columns per block
     const int *orig;                 // [n_rows] vertex | aggregate << 28 (-1 = dummy row)
     const int *halo_ptr, *halo_src;  // [G + 1]; internal rows of the halo entries (sorted per block)
+    const int *halo_vert;            // the vertex of every halo entry (orig[halo_src[h]] & 0x0fffffff): the halo of the ENTRY x is read from a.x
     int vec_len;                     // entries per axis of the local vector: 64 spb own + halo capacity
     const double *mdiag, *dinv, *b;  // mass + diag(Ahat) by internal row; dinv, b by vertex
     double *x, *u_out;               // by vertex
@@ -142,6 +143,16 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     const bool live = oa >= 0;
     const int vi = live ? (oa & 0x0fffffff) : 0;       // the vertex this row belongs to
     const int myagg = live ? (oa >> 28) & 3 : 0;
+    // The halo of the ENTRY x needs no exchange: x0 is a.x, complete in global memory before the launch and written by nobody before the
+    // epilogue (behind at least one grid barrier), so halo entry h is a.x[3 halo_vert[h] + j] -- the very double the neighbour would publish.
+    // Its indices are asked for here, its values between the two halves of the slab fill, and they land in the halo part of the local vector
+    // (which the fill does not touch) right behind the fill: the launch's first residual finds them there (entry_residual, below).
+    const int hp0 = a.halo_ptr[blockIdx.x], nh = a.halo_ptr[blockIdx.x + 1] - hp0;
+    // (unconditional loads at a clamped index -- the list carries one entry of padding, so a block without a halo has one to read: guarded by
+    // tid < nh each became a branch that waited for its load, two round trips in a row in front of the slab fill; the lanes without an entry
+    // read some entry's vertex, a valid index of x, and write nothing)
+    const int hlast = nh > 0 ? nh - 1 : 0;
+    const int hv0 = a.halo_vert[hp0 + (tid < hlast ? tid : hlast)], hv1 = a.halo_vert[hp0 + (tid + T < hlast ? tid + T : hlast)];
     // (cvt_here: the float -> double conversion as a volatile instruction.  Left to the compiler it is hoisted out of the
     // iteration loop, single-precision constants then occupy twice the registers in a loop that has none to spare, and most of
     // them are spilled and come back from scratch memory every iteration.)
@@ -169,12 +180,24 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         const double *vpg = vpg_w + lane;
         for (int k = 0; k < wl_s; ++k) lvw[64 * k] = vpg[64 * k];
     }
+    double xh[2][3];      // entry x of the halo entries tid and tid + T: in flight under the columns' half of the fill only
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { xh[0][j] = a.x[3 * (size_t)hv0 + j]; xh[1][j] = a.x[3 * (size_t)hv1 + j]; }
     {   // ... and its columns
         LdsU64 *lcw = lc_w + lane;
         const unsigned long long *cpg = cpg_w + lane;
         for (int k = 0; k < (wl_s >> 2); ++k) lcw[64 * k] = cpg[64 * k];
     }
-    const int hp0 = a.halo_ptr[blockIdx.x], nh = a.halo_ptr[blockIdx.x + 1] - hp0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (tid < nh) vec[j * NV + T + tid] = xh[0][j];
+        if (tid + T < nh) vec[j * NV + 2 * T + tid] = xh[1][j];
+    }
+    for (int h = tid + 2 * T; h < nh; h += T) {      // (small blocks with long halos: the further entries, from the list)
+        const int hv = a.halo_vert[hp0 + h];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vec[j * NV + T + h] = a.x[3 * (size_t)hv + j];
+    }
     // the halo entries this thread fetches (two per thread cover nh <= 2 T; more are read from the list every time)
     const int hs0 = tid < nh ? a.halo_src[hp0 + tid] : 0, hs1 = tid + T < nh ? a.halo_src[hp0 + tid + T] : 0;
     if (prof) a.prof[63 * 8 + 1] = wall_clock64();
@@ -503,7 +526,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
     auto action = [&]() -> int { __syncthreads(); return __builtin_amdgcn_readfirstlane(ictl[2]); };
     // u = D^-1 (b - A x) from the x held in registers (x goes through the published copy: the columns are local indices);
     // leaves r . D^-1 r (and optionally b . D^-1 b) in q[0..5]
-    auto true_residual = [&](bool with_bnorm, double *q, double *ri_out, double *b_out = nullptr) -> bool {
+    auto true_residual = [&](double *q) -> bool {
         double ax[3];
         ++ph; publish(rx);
         if (handoff) { if (!oc_announce_and_wait_neighbours<false>(bar, a.flags, a.nbr, (unsigned)a.seq, ph, ok_lds, a.sig)) return false; }
@@ -513,20 +536,50 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         for (int j = 0; j < 3; ++j) {
             const double bj = live ? a.b[3 * (size_t)vi + j] : 0.0;
             const double ri = bj - ax[j];
+            ru[j] = rd[j] * ri;
+            q[j] = ru[j] * ri;
+            q[3 + j] = 0.0;
+        }
+        __syncthreads();   // the local vector is rewritten by the next publish
+        return true;
+    };
+    // THE FIRST RESIDUAL OF A LAUNCH, r0 = b - A x0, WITHOUT AN EXCHANGE: the halo of x0 already lies in the local vector (read from a.x through
+    // halo_vert at the top of the kernel), the own entries go into LDS only, one block barrier, then the same row loop and the same
+    // fma(rm, self, acc) as true_residual -- the same doubles in the same order, bit for bit.  Also leaves b . D^-1 b in q[3..5] and hands
+    // back r0 and this row's b.  The start phase below runs once per launch (do { } while (false)), so its two calls are the launch's first
+    // residual in every block, and every later one (verification, restart from the entry x) is true_residual with its exchange: the path
+    // is chosen at compile time, all blocks take the same one.
+    // PHASE COUNTERS: ph (and be on the path without hand-off lists) is not advanced here, so the first exchange of a launch, that of u, is
+    // phase 1.  The two-parity ubuf and the (seq, ph) flag tags stay safe: a block writes parity p again two exchanges later, and every two
+    // consecutive exchanges of a launch are still separated by a grid barrier (an exchange is followed by the barrier of a record before the
+    // next publish), which a neighbour passes only after its halo loads of the earlier phase have been consumed; the flags only ever compare
+    // tags of one launch with each other or with smaller ones -- tags of different launches differ in seq, the upper half -- and (seq, 1),
+    // which the entry exchange used to announce, is now announced by the exchange of u.
+    auto entry_residual = [&](double *q, double *ri_out, double *b_out) {
+        {
+            const int tid = otid();
+            vec[OC2_VX(tid, 0)] = rx[0]; vec[OC2_VX(tid, 1)] = rx[1]; vec[OC2_VX(tid, 2)] = rx[2];
+        }
+        __syncthreads();   // own entries and the halo written behind the slab fill -> every thread
+        double acc[3] = {0.0, 0.0, 0.0};
+        row_times_local_vector(acc);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double bj = live ? a.b[3 * (size_t)vi + j] : 0.0;
+            const double ri = bj - fma(rm[j], rx[j], acc[j]);
             if (ri_out) ri_out[j] = ri;
             if (b_out) b_out[j] = bj;
             ru[j] = rd[j] * ri;
             q[j] = ru[j] * ri;
-            q[3 + j] = with_bnorm ? bj * rd[j] * bj : 0.0;
+            q[3 + j] = bj * rd[j] * bj;
         }
         __syncthreads();   // the local vector is rewritten by the next publish
-        return true;
     };
     do {
         // ---- start: TRUE residual of the warm start (after the recycled projection), stop test, w = A u ---------------
         {
             double q[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            if (!rc_on) { if (!true_residual(true, q, nullptr)) { aborted = true; break; } }
+            if (!rc_on) entry_residual(q, nullptr, nullptr);
             else {
                 // recycled warm start (see k_rc_* in kernels.hpp): A-orthogonal projection of the initial
                 // error on the stored exact pairs (E_j, R_j = A E_j): per axis G c = g, x += E c, r0 -= R c
@@ -541,7 +594,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
                         e[jj][ax] = on ? a.rc.E[jj][3 * (size_t)row + ax] : 0.0;
                         r[jj][ax] = on ? a.rc.R[jj][3 * (size_t)row + ax] : 0.0;
                     }
-                if (!true_residual(true, q, ri, bj)) { aborted = true; break; }      // (also hands back this row's b)
+                entry_residual(q, ri, bj);      // (also hands back this row's b)
                 if (prof) a.prof[62 * 8 + 0] = wall_clock64();
                 // The copies of the entry x and r0 for the epilogue's pair.  The hot instances, with stored pairs, issue them under the grid barrier of
                 // the recycled sums below (six stores per row in front of the block sums sat in that barrier's drain).  The generic instances keep
@@ -731,7 +784,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
         // verification that did not improve on the previous one by 4x); 0: it does not -- CG restarts from it; -1: aborted
         auto verify = [&]() -> int {
             double q[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            if (!true_residual(false, q, nullptr)) return -1;
+            if (!true_residual(q)) return -1;
             ++be;
             publish_record(q, zero3, false, (int)(be & 1u));
             if (!oc_barrier(bar, be, a.G, ok_lds, a.sig)) return -1;
@@ -958,7 +1011,7 @@ __global__ __launch_bounds__(MAXT) void k_pcg2(Oc2Args a) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) rx[j] = live ? a.x[3 * (size_t)vi + j] : 0.0;
                 double q[7];
-                if (!true_residual(false, q, nullptr)) { aborted = true; break; }
+                if (!true_residual(q)) { aborted = true; break; }
                 if (tid == 0) { ctl[0] = 1e300; ictl[0] = 0; }
                 if (++restarts > 1) break;
                 fresh = true;

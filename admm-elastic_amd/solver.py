@@ -452,6 +452,16 @@ class Solver:
         stats.update(lambda_bb=st[8] * 1e-9, bank_load_by_index=st[9] * 1e-6, bank_load_placed=st[10] * 1e-6)
         return dict(row_vertex=rv, row_aggregate=ra, coarse_inv=ci, stats=stats, row_weights=wt)
 
+    def host_oc_plan_halo(self, n_blocks, slices_per_block, lds_bytes=159744, settings=None):
+        """The halo lists of the same plan (admm_host_oc_plan_halo, no GPU): dict(halo_ptr [n_blocks + 1], halo_src, halo_vert) -- the
+        internal row of every halo entry and its vertex."""
+        d = self.make_desc(settings if settings is not None else self._settings)
+        hp = np.zeros(n_blocks + 1, np.int32)
+        check(lib().admm_host_oc_plan_halo(C.byref(d), n_blocks, slices_per_block, lds_bytes, iptr(hp), None, None))
+        hs = np.zeros(max(int(hp[-1]), 1), np.int32); hv = np.zeros(max(int(hp[-1]), 1), np.int32)
+        check(lib().admm_host_oc_plan_halo(C.byref(d), n_blocks, slices_per_block, lds_bytes, iptr(hp), iptr(hs), iptr(hv)))
+        return dict(halo_ptr=hp, halo_src=hs[:int(hp[-1])], halo_vert=hv[:int(hp[-1])])
+
     def host_big_plan(self, max_aggregates=0, settings=None):
         """The plan of the launch-path two-level PCG of this scene (admm_host_big_plan, no GPU): dict(G, ra, rows, nc, ncp, slices, row_vertex,
         row_weights [rows, 4], coarse_inv [nc, nc])."""

@@ -727,6 +727,11 @@ void admm_host_locality_order(int32_t n_verts, int32_t n_elems, int32_t corners,
  * entries in index order / as placed.  lds_bytes = LDS a block may spend on its local vector and matrix slab. */
 int admm_host_oc_plan(const admm_hip_desc *desc, int32_t n_blocks, int32_t slices_per_block, int32_t lds_bytes,
                       int32_t *row_vertex, int32_t *row_aggregate, double *coarse_inv, int64_t *stats, float *row_weights);
+/* The halo lists of the same plan (same arguments), no GPU -- tests.  halo_ptr [n_blocks + 1]: offsets of the blocks' lists; halo_src and
+ * halo_vert [halo_ptr[n_blocks]] (either may be NULL: call once for halo_ptr, the sizes): the internal row of every halo entry, and its
+ * vertex -- what the on-chip kernel reads the halo of a solve's entry x through. */
+int admm_host_oc_plan_halo(const admm_hip_desc *desc, int32_t n_blocks, int32_t slices_per_block, int32_t lds_bytes,
+                           int32_t *halo_ptr, int32_t *halo_src, int32_t *halo_vert);
 
 /* The plan of the LAUNCH-PATH two-level PCG (csrc/pcg_big.hpp; csrc/oc_plan.cpp: build_big_plan) for this scene, no GPU -- bodies beyond the
  * chip's LDS and the fall-back of the on-chip solver; replaces the same prefactored solve, src/LinearSolver.hpp:87-90.  The vertices are
