@@ -98,6 +98,9 @@ SYMBOLS = [
     ("admm_hip_tangent_solve", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p]),
     ("admm_hip_modes", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p,
                                  c_double_p, c_double_p]),
+    ("admm_hip_set_tangent_precond", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    ("admm_hip_get_tangent_precond", C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    ("admm_hip_tangent_precond_apply", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p]),
     ("admm_hip_newton_polish", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_param_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_step_adjoint", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_int32] + [c_double_p] * 9),
@@ -151,6 +154,7 @@ SYMBOLS = [
     ("admm_host_chunk_reduce", C.c_int, [C.c_int32, C.c_int32, c_int_p, c_int_p, c_double_p, c_double_p, C.POINTER(C.c_int64)]),
     ("admm_host_gs_plan_sweeps", C.c_int, [C.POINTER(Desc), C.c_int32, c_int_p, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_double, c_int_p]),
     ("admm_host_big_plan", C.c_int, [C.POINTER(Desc), C.c_int32, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_float)]),
+    ("admm_host_tangent_plan", C.c_int, [C.c_int32, c_double_p, C.c_int32, c_int_p, c_int_p]),
     ("admm_host_oc_plan", C.c_int, [C.POINTER(Desc), C.c_int32, C.c_int32, C.c_int32, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
     ("admm_host_oc_plan_halo", C.c_int, [C.POINTER(Desc), C.c_int32, C.c_int32, C.c_int32, c_int_p, c_int_p, c_int_p]),
 ]

@@ -28,6 +28,7 @@
 #include "newton.hpp"
 #include "adjoint.hpp"
 #include "modal.hpp"
+#include "tangent_precond.hpp"
 #include "anderson.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
@@ -435,6 +436,14 @@ struct admm_hip_ctx {
     DevBuf<double> md_S, md_AS, md_theta, md_rpart, md_gpart, md_GA, md_GM, md_C;
     DevBuf<ModalSt> md_st; int md_nbg = 0, md_tpb = 0;
     bool md_ready = false;
+    // two-level preconditioner of the tangent solves (tangent_precond.hpp; admm_hip_set_tangent_precond): buffers of their own, allocated
+    // by the first solve that runs with it (and again when the number of aggregates changes)
+    int tc_kind = 0, tc_aggregates = 0;      // in effect from the next solve: 0 Jacobi, 1 two-level; aggregates wanted (0: n_verts / 256 in 1 .. 64)
+    int tc_G = 0, tc_nc = 0, tc_ncb = 0;     // of the buffers: aggregates planned, 12 G, blocks of k_tc_coarse
+    int tc_last_nc = 0, tc_last_passes = 0;  // the last solve: coarse dimension (0: Jacobi), block passes of its setup
+    std::vector<double> tc_xyz_h;            // desc.vert_xyz (the aggregates are cut in the rest positions)
+    DevBuf<int> tc_agg_ptr, tc_agg_vert, tc_agg_of, tc_keep, tc_info;      // [G + 1], [nv], [nv]; tc_invert's columns kept [nc]; {flag, coarse_ok, dropped}
+    DevBuf<double> tc_phi, tc_d, tc_ad, tc_Ac, tc_As, tc_Ainv, tc_ds, tc_dl, tc_col, tc_c, tc_yc, tc_cpart;      // [nv][4]; [16][3 nv] twice; [nc][nc] three times; [nc] five times; [ncb]
     // adjoint of a step (adjoint.hpp; admm_hip_param_sensitivity, admm_hip_step_adjoint): buffers of their own, allocated by the first call
     DevBuf<double> adj_a, adj_ps, adj_l, adj_out;      // the stack [kSensCols][3 nv]; its sensitivities; Lx, Lv [2][3 nv]; the gradients [4][3 nv]
     bool adj_ready = false;
@@ -854,7 +863,10 @@ void launch_pin_mask(admm_hip_ctx *c) {
 // Jacobi-PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device; leaves y in nw_y and the verdict in nw_st[2].
 // Iterations are enqueued in chunks, one chunk ahead of the device; the host reads the stop word of the chunk before (pinned, behind an
 // event) and stops enqueueing.  The caller synchronises.
+int tangent_solve_two_level(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters);
 int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
+    if (c->tc_kind == 1) return tangent_solve_two_level(c, xd, shift, flags, tol, max_iters);      // (tangent_precond.hpp; below)
+    c->tc_last_nc = 0; c->tc_last_passes = 0;
     hipStream_t st = c->stream;
     const int nv = c->nv, nb = nw_blocks(c);
     const int *pin = nullptr;
@@ -987,6 +999,101 @@ int modes_device(admm_hip_ctx *c, const double *xd, int k, int nb, double shift,
     launch_modal_rr0(c, a, 0);
     launch_frozen_block(c, a.S, a.AS, nb, shift, pin, nullptr);
     hipLaunchKernelGGL(k_modal_resid, dim3(a.nbk), dim3(256), 0, st, a, 2);
+    HIP_TRY(hipGetLastError());
+    return ADMM_HIP_OK;
+}
+// ---- the two-level preconditioner of the tangent solves (tangent_precond.hpp) ----
+// the aggregates (planned in the rest positions, uploaded once per number of aggregates) and every tc_ buffer
+int tc_ensure(admm_hip_ctx *c) {
+    const int nv = c->nv;
+    const int G = c->tc_aggregates > 0 ? c->tc_aggregates : std::min(kTcMaxAgg, std::max(1, nv / 256));
+    if (c->tc_G == G) return ADMM_HIP_OK;
+    if (c->tc_xyz_h.size() != (size_t)c->n3) return fail(ADMM_HIP_ERR_ARG, "tangent_precond: the two-level preconditioner needs desc.vert_xyz (the aggregates are cut in the rest positions)");
+    std::vector<int32_t> ptr, vert;
+    if (!admm_host::tangent_plan(nv, c->tc_xyz_h.data(), G, ptr, vert)) return fail(ADMM_HIP_ERR_ARG, "tangent_precond: more aggregates than vertices");
+    hipStream_t st = c->stream;
+    c->tc_G = 0;
+    HIP_TRY(c->bk_el.ensure(c, kModalNb));
+    const size_t nc = (size_t)kTcPer * G, n = (size_t)std::max(1, c->n3), nvv = (size_t)std::max(1, nv), ncb = (nc + 3) / 4;
+    if (vert.empty()) vert.push_back(0);
+    HIP_TRY(c->tc_agg_ptr.alloc(ptr.size())); HIP_TRY(c->tc_agg_vert.alloc(vert.size()));
+    HIP_TRY(hipMemcpyAsync(c->tc_agg_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->tc_agg_vert.p, vert.data(), vert.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(c->tc_agg_of.alloc_zeroed(nvv, st)); HIP_TRY(c->tc_keep.alloc_zeroed(nc, st)); HIP_TRY(c->tc_info.alloc_zeroed(3, st));
+    HIP_TRY(c->tc_phi.alloc_zeroed(4 * nvv, st));
+    HIP_TRY(c->tc_d.alloc_zeroed((size_t)kModalNb * n, st)); HIP_TRY(c->tc_ad.alloc_zeroed((size_t)kModalNb * n, st));
+    for (DevBuf<double> *b : {&c->tc_Ac, &c->tc_As, &c->tc_Ainv}) HIP_TRY(b->alloc_zeroed(nc * nc, st));
+    for (DevBuf<double> *b : {&c->tc_ds, &c->tc_dl, &c->tc_col, &c->tc_c, &c->tc_yc}) HIP_TRY(b->alloc_zeroed(nc, st));
+    HIP_TRY(c->tc_cpart.alloc_zeroed(ncb, st));
+    HIP_TRY(hipStreamSynchronize(st));      // (ptr and vert leave scope)
+    c->tc_G = G; c->tc_nc = (int)nc; c->tc_ncb = (int)ncb;
+    return ADMM_HIP_OK;
+}
+// A_c^-1 of the tangent frozen at xd (frames and nw_dinv are in place): the basis, A P in block passes of kModalNb columns, P^T (A P), the inverse
+void launch_tc_setup(admm_hip_ctx *c, const double *xd, double shift, const int *pin) {
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c), G = c->tc_G, nc = c->tc_nc;
+    const size_t n3 = (size_t)c->n3;
+    hipLaunchKernelGGL(k_tc_basis, dim3(G), dim3(256), 0, st, c->tc_agg_ptr.p, c->tc_agg_vert.p, xd, pin, c->tc_phi.p, c->tc_agg_of.p);
+    c->tc_last_passes = 0;
+    for (int col0 = 0; col0 < nc; col0 += kModalNb, ++c->tc_last_passes) {
+        const int n = std::min<int>(kModalNb, nc - col0);
+        hipLaunchKernelGGL(k_tc_fill, dim3(nb, n), dim3(256), 0, st, nv, col0, n3, c->tc_agg_of.p, c->tc_phi.p, c->tc_d.p);
+        launch_frozen_block(c, c->tc_d.p, c->tc_ad.p, n, shift, pin, nullptr);
+        hipLaunchKernelGGL(k_tc_restrict_block, dim3(G, n), dim3(256), 0, st, nc, col0, n3, c->tc_agg_ptr.p, c->tc_agg_vert.p, c->tc_phi.p, c->tc_ad.p, c->tc_Ac.p);
+    }
+    hipLaunchKernelGGL(k_tc_sym, dim3(blocks_for(nc * nc)), dim3(256), 0, st, nc, c->tc_Ac.p, c->tc_As.p);
+    hipLaunchKernelGGL(k_tc_invert, dim3(1), dim3(1024), 0, st, nc, c->tc_As.p, c->tc_Ainv.p, c->tc_ds.p, c->tc_dl.p, c->tc_col.p, c->tc_keep.p, c->tc_info.p, c->tc_info.p + 1);
+    c->tc_last_nc = nc;
+}
+// r = nw_rhs on the free rows, y = 0, p = z = M^-1 r and the scalars of iteration 0 (the stop word is 0 on entry)
+void launch_tc_start(admm_hip_ctx *c, const int *pin) {
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    hipLaunchKernelGGL(k_tc_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_tc_restrict, dim3(c->tc_G), dim3(256), 0, st, c->nw_stop.p, c->tc_agg_ptr.p, c->tc_agg_vert.p, c->tc_phi.p, c->nw_r.p, c->tc_c.p);
+    hipLaunchKernelGGL(k_tc_coarse, dim3(c->tc_ncb), dim3(256), 0, st, c->nw_stop.p, c->tc_nc, c->tc_Ainv.p, c->tc_c.p, c->tc_yc.p, c->tc_cpart.p);
+    hipLaunchKernelGGL(k_tc_cg_init2, dim3(nb), dim3(256), 0, st, nv, nb, c->tc_ncb, c->nw_part.p, c->tc_cpart.p, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_r.p,
+                       c->tc_phi.p, c->tc_agg_of.p, c->tc_yc.p, c->nw_p.p);
+}
+// tangent_solve_device with the two-level preconditioner: the same chunks, the same stop protocol, the same true-residual tail; six
+// launches per iteration
+int tangent_solve_two_level(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
+    if (int rc = tc_ensure(c)) return rc;
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    launch_tc_setup(c, xd, shift, pin);
+    launch_tc_start(c, pin);
+    constexpr int chunk = 8;
+    int launched = 0, chunks = 0;
+    while (launched < max_iters) {
+        const int n = std::min(chunk, max_iters - launched);
+        for (int it = launched; it < launched + n; ++it) {
+            launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
+            hipLaunchKernelGGL(k_tc_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
+                               c->nw_y.p, c->nw_r.p, c->nw_part.p);
+            hipLaunchKernelGGL(k_tc_restrict, dim3(c->tc_G), dim3(256), 0, st, c->nw_stop.p, c->tc_agg_ptr.p, c->tc_agg_vert.p, c->tc_phi.p, c->nw_r.p, c->tc_c.p);
+            hipLaunchKernelGGL(k_tc_coarse, dim3(c->tc_ncb), dim3(256), 0, st, c->nw_stop.p, c->tc_nc, c->tc_Ainv.p, c->tc_c.p, c->tc_yc.p, c->tc_cpart.p);
+            hipLaunchKernelGGL(k_tc_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->tc_ncb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
+                               c->nw_r.p, c->nw_p.p, c->nw_part.p, c->tc_cpart.p, c->tc_phi.p, c->tc_agg_of.p, c->tc_yc.p);
+        }
+        launched += n;
+        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
+        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
+            if (c->nw_hstop[(chunks - 1) & 1]) break;
+        }
+        ++chunks;
+    }
+    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);      // the TRUE residual of the returned iterate (tangent_solve_device)
+    hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
     HIP_TRY(hipGetLastError());
     return ADMM_HIP_OK;
 }
@@ -3041,6 +3148,7 @@ static int create_impl(const admm_hip_desc *d, admm_hip_ctx **out) {
     c->defl_use_resid = env_flag("ADMM_HIP_DEFL_RESID", true);
     c->kernel_clock = env_flag("ADMM_HIP_KERNEL_CLOCK", false);
     c->uz_lanes_debug = env_flag("ADMM_HIP_UZ_LANES_DEBUG", false);
+    if (d->vert_xyz) c->tc_xyz_h.assign(d->vert_xyz, d->vert_xyz + c->n3);
     if (d->vert_xyz && d->linsolver != 1) c->xyz_h.assign(d->vert_xyz, d->vert_xyz + c->n3);      // (the launch-path two-level PCG plans lazily)
     {   // distributed solve of ONE body (ADMM_HIP_DIST_SOLVE=1, element-block partition): contiguous vertex rows per rank, 64-aligned
         const bool force_comm = env_flag("ADMM_HIP_FORCE_COMM", false);     // (tests: a world of ONE with a communicator runs the same collectives through RCCL)
@@ -4199,6 +4307,66 @@ int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, 
     HIP_TRY(hipMemcpyAsync(&rr_true, c->nw_part.p + (size_t)3 * nw_blocks(c) + 2, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     info4[0] = h.it; info4[1] = h.conv; info4[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info4[3] = std::sqrt(h.bb);
+    return ADMM_HIP_OK;
+}
+
+// The preconditioner of admm_hip_tangent_solve, admm_hip_newton_polish and admm_hip_step_adjoint
+int admm_hip_set_tangent_precond(admm_hip_ctx *c, int32_t kind, int32_t aggregates) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: NULL context");
+    if (kind < 0 || kind > 1) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: kind is 0 (Jacobi) or 1 (two-level)");
+    if (aggregates < 0 || aggregates > kTcMaxAgg) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: aggregates in 0 .. 64 (0: the default)");
+    if (int rc = mon_refuse(c, "set_tangent_precond")) return rc;
+    if (aggregates > std::max(1, c->nv)) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: more aggregates than vertices");
+    if (kind == 1 && c->tc_xyz_h.size() != (size_t)c->n3) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: the two-level preconditioner needs desc.vert_xyz");
+    c->tc_kind = kind; c->tc_aggregates = aggregates;
+    return ADMM_HIP_OK;
+}
+int admm_hip_get_tangent_precond(admm_hip_ctx *c, int32_t *kind, int32_t *aggregates, int32_t *coarse_dim, int32_t *coarse_dropped, int32_t *coarse_ok,
+                                 int32_t *setup_passes) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "get_tangent_precond: NULL context");
+    int h[3] = {0, 0, 0};
+    if (c->tc_last_nc > 0) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(h, c->tc_info.p, sizeof(h), hipMemcpyDeviceToHost));
+    }
+    if (kind) *kind = c->tc_kind;
+    if (aggregates) *aggregates = c->tc_aggregates;
+    if (coarse_dim) *coarse_dim = c->tc_last_nc;
+    if (coarse_dropped) *coarse_dropped = h[2];
+    if (coarse_ok) *coarse_ok = h[1];
+    if (setup_passes) *setup_passes = c->tc_last_passes;
+    return ADMM_HIP_OK;
+}
+// z = M^-1 r of the two-level preconditioner of the tangent frozen at x (tests): the setup of a solve, then its start -- p of iteration 0
+int admm_hip_tangent_precond_apply(admm_hip_ctx *c, const double *x, const double *r, double shift, int32_t flags, double *z_out) {
+    if (!c || !r || !z_out) return fail(ADMM_HIP_ERR_ARG, "tangent_precond_apply: NULL argument");
+    if (int rc = newton_args_ok("tangent_precond_apply", shift, flags)) return rc;
+    const double *xd;
+    if (int rc = eval_begin(c, "tangent_precond_apply", x, &xd)) return rc;
+    HIP_TRY(newton_ensure(c));
+    if (int rc = tc_ensure(c)) return rc;
+    hipStream_t st = c->stream;
+    if (c->n3) HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, r, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    launch_tc_setup(c, xd, shift, pin);
+    launch_tc_start(c, pin);
+    HIP_TRY(hipGetLastError());
+    if (c->n3) HIP_TRY(hipMemcpyAsync(z_out, c->nw_p.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
+int admm_host_tangent_plan(int32_t n_verts, const double *xyz, int32_t G, int32_t *agg_ptr, int32_t *agg_vert) {
+    if (n_verts < 0 || !agg_ptr || (n_verts > 0 && (!xyz || !agg_vert))) return fail(ADMM_HIP_ERR_ARG, "tangent_plan: NULL argument");
+    if (G < 1 || G > kTcMaxAgg || G > std::max(1, n_verts)) return fail(ADMM_HIP_ERR_ARG, "tangent_plan: G in 1 .. min(64, n_verts)");
+    std::vector<int32_t> ptr, vert;
+    if (!admm_host::tangent_plan(n_verts, xyz, G, ptr, vert)) return fail(ADMM_HIP_ERR_ARG, "tangent_plan: no plan");
+    std::copy(ptr.begin(), ptr.end(), agg_ptr);
+    std::copy(vert.begin(), vert.end(), agg_vert);
     return ADMM_HIP_OK;
 }
 

@@ -1605,4 +1605,97 @@ __device__ __forceinline__ double modal_start(unsigned col, unsigned vertex, uns
     return ((double)h + 0.5) * 4.656612873077393e-10 - 1.0;      // (h + 1/2) 2^-31 - 1: exact in FP64
 }
 
+// ---- the dense inverse of the two-level tangent preconditioner (tangent_precond.hpp: k_tc_invert) ----
+// X = A^-1 for a symmetric A [n][n] (row-major; destroyed), by Cholesky of the diagonally scaled matrix (right-looking, as modal_geneig)
+// and the two triangular solves against the identity; X is symmetrised at the end, so applying it is a symmetric operator to the bit.
+// ONE text for the device and the host, cut into phases as modal_geneig is (tid, nt, sync).  The three sweeps are ROW-ORIENTED: step k
+// finishes row k and then takes its share out of the other rows, (rows) x (columns) independent items between two barriers -- the
+// threads form a grid of nt / 64 row groups by 64 columns, so a wave walks a row with unit stride and the loads of an item do not wait
+// for the item before (a column per thread, the first form, was one dependent chain of n^2 loads per thread: 229 ms at n = 768).  Every
+// entry sees the same operations in the same order whatever nt is.
+//   DROPPED columns: |a_ii| <= kTcDrop max_k a_kk.  Row and column i of X are zero, the rest of X is the inverse of the rest of A.
+//          Counted in *dropped.  (An aggregate whose vertices are all held; a flat cloth, where one affine function vanishes.)
+//   VERDICT 0, X all zero: a diagonal that is not finite or below -kTcDrop max_k a_kk; a pivot of the scaled matrix (unit diagonal) that
+//          is not finite or below 16 n eps -- the rounding of a pivot is up to n eps, a pivot of that size carries no digit: this is how
+//          a singular A ends, P containing a null space of the operator or dependent columns --; a non-finite entry of X.
+// Work: ds, dl, col [n], keep [n], flag [1].
+constexpr double kTcDrop = 9.094947017729282e-13;      // 2^-40
+template <class Sync>
+__device__ __forceinline__ int tc_invert(int n, double *A, double *X, double *ds, double *dl, double *col, int *keep, int *flag, int *dropped,
+                                         int tid, int nt, Sync sync) {
+    const size_t ld = (size_t)n;
+    const int W = nt >= 64 ? 64 : 1, tx = tid % W, ty = tid / W, ny = nt / W;      // (threads beyond ny W take no item of the sweeps)
+    bool ok = true;
+    double dmax = 0.0;
+    for (int i = 0; i < n; ++i) { const double d = A[i * ld + i]; ok = ok && modal_finite(d); dmax = d > dmax ? d : dmax; }      // (every thread: uniform)
+    const double thr = kTcDrop * dmax;
+    int nd = 0;
+    for (int i = 0; i < n; ++i) { const double d = A[i * ld + i]; nd += d <= thr ? 1 : 0; ok = ok && d >= -thr; }
+    if (tid == 0) { *dropped = nd; *flag = 1; }
+    for (int i = tid; i < n; i += nt) { const double d = A[i * ld + i]; keep[i] = d > thr ? 1 : 0; ds[i] = d > thr ? 1.0 / sqrt(d) : 0.0; }
+    sync();
+    if (ok) {
+        for (size_t e = (size_t)tid; e < ld * ld; e += (size_t)nt) {
+            const int i = (int)(e / ld), j = (int)(e - i * ld);
+            A[e] = keep[i] && keep[j] ? (A[e] * ds[i]) * ds[j] : (i == j ? 1.0 : 0.0);      // (a dropped column: the identity's, so the factorisation runs through)
+            X[e] = i == j ? 1.0 : 0.0;
+        }
+        sync();
+        const double pivot_min = 16.0 * n * 2.220446049250313e-16;
+        for (int j = 0; j < n; ++j) {
+            const double d = A[j * ld + j];      // (no item of this step writes a pivot: every thread reads the same one)
+            if (!(d >= pivot_min) || !modal_finite(d)) { ok = false; break; }
+            const double l = sqrt(d);
+            for (int i = j + tid; i < n; i += nt) {
+                if (i == j) dl[j] = l;
+                else { const double v = A[i * ld + j] / l; A[i * ld + j] = v; col[i] = v; }      // (col: column j of L with unit stride)
+            }
+            sync();
+            for (int i = j + 1 + ty; i < n && ty < ny; i += ny) {      // the trailing lower triangle
+                const double lij = col[i];
+                for (int k = j + 1 + tx; k <= i; k += W) A[i * ld + k] = fma(-lij, col[k], A[i * ld + k]);
+            }
+            sync();
+        }
+    }
+    if (ok) {
+        // L Y = I in place in X (Y is lower triangular: row k ends at column k)
+        for (int k = 0; k < n; ++k) {
+            for (int c = tid; c <= k; c += nt) X[k * ld + c] = X[k * ld + c] / dl[k];
+            sync();
+            for (int i = k + 1 + ty; i < n && ty < ny; i += ny) {
+                const double lik = A[i * ld + k];
+                for (int c = tx; c <= k; c += W) X[i * ld + c] = fma(-lik, X[k * ld + c], X[i * ld + c]);
+            }
+            sync();
+        }
+        // L^T X = Y in place
+        for (int k = n - 1; k >= 0; --k) {
+            for (int c = tid; c < n; c += nt) X[k * ld + c] = X[k * ld + c] / dl[k];
+            sync();
+            for (int i = ty; i < k && ty < ny; i += ny) {
+                const double lki = A[k * ld + i];
+                for (int c = tx; c < n; c += W) X[i * ld + c] = fma(-lki, X[k * ld + c], X[i * ld + c]);
+            }
+            sync();
+        }
+        for (size_t e = (size_t)tid; e < ld * ld; e += (size_t)nt) {
+            const int i = (int)(e / ld), j = (int)(e - i * ld);
+            if (i > j) continue;
+            const double h = keep[i] && keep[j] ? (0.5 * (X[i * ld + j] + X[j * ld + i]) * ds[i]) * ds[j] : 0.0;
+            if (!modal_finite(h)) *flag = 0;      // (every writer stores 0)
+            X[i * ld + j] = h; X[j * ld + i] = h;
+        }
+        sync();
+        ok = *flag != 0;
+        sync();
+    }
+    if (!ok) {
+        for (size_t e = (size_t)tid; e < ld * ld; e += (size_t)nt) X[e] = 0.0;
+        if (tid == 0) *flag = 0;
+        sync();
+    }
+    return ok ? 1 : 0;
+}
+
 } // namespace admm_dev

@@ -166,6 +166,11 @@ struct BigPlan {
 };
 BigPlan build_big_plan(const Csr &A, const double *mass3, const double *xyz, int max_aggregates);
 
+// Aggregates of the two-level tangent preconditioner (oc_plan.cpp: tangent_plan; kernels: tangent_precond.hpp): all vertices in G compact
+// parts by recursive coordinate bisection of the rest positions xyz [3 n]; agg_ptr [G + 1], agg_vert [n] grouped by aggregate, ascending
+// within one.  false: G outside 1 .. max(1, n), or no positions.
+bool tangent_plan(int32_t nv, const double *xyz, int G, std::vector<int32_t> &agg_ptr, std::vector<int32_t> &agg_vert);
+
 // Plan of the PERSISTENT multi-colour Gauss-Seidel kernel (oc_plan.cpp: build_gs_plan; kernels: gs_persist.hpp).  The vertices are
 // split into G compact blocks (one per CU, the recursive bisection of the on-chip PCG); a block keeps its rows' matrix entries,
 // its part of x and the values of the rows of other blocks it references (its halo) in LDS for the whole solve, and a colour phase

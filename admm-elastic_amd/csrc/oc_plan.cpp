@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <numeric>
 
 namespace admm_host {
@@ -915,6 +916,44 @@ GsPlan build_gs_plan(const Csr &A, int n_colors, const int32_t *color, int max_b
     if (P.halo_box.empty()) { P.halo_box.push_back(0); P.halo_orig.push_back(0); }
     P.ok = P.lds_bytes <= lds_limit;
     return P;
+}
+
+// ---- aggregates of the two-level tangent preconditioner (tangent_precond.hpp) -------------------------------------------------------
+// Recursive coordinate bisection of ALL vertices: a part of n vertices that is to hold g aggregates goes to its g / 2 and g - g / 2
+// halves with n (g / 2) / g and the remaining vertices -- along the axis of its longest extent (ties: the lowest axis), in the order of
+// that coordinate, equal coordinates by vertex number (a stable sort of ascending numbers).  A power-of-two G therefore splits at the
+// median: siblings differ by at most one vertex.  Deterministic; needs 1 <= G <= max(1, n_verts).
+bool tangent_plan(int32_t nv, const double *xyz, int G, std::vector<int32_t> &agg_ptr, std::vector<int32_t> &agg_vert) {
+    agg_ptr.assign(1, 0); agg_vert.clear();
+    if (G < 1 || G > std::max<int32_t>(1, nv) || nv < 0 || (nv > 0 && !xyz)) return false;
+    agg_vert.reserve((size_t)nv);
+    std::vector<int32_t> all((size_t)nv);
+    std::iota(all.begin(), all.end(), 0);
+    std::function<void(std::vector<int32_t> &, int)> split = [&](std::vector<int32_t> &part, int g) {
+        if (g == 1) {
+            std::sort(part.begin(), part.end());
+            agg_vert.insert(agg_vert.end(), part.begin(), part.end());
+            agg_ptr.push_back((int32_t)agg_vert.size());
+            return;
+        }
+        double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+        for (int32_t v : part)
+            for (int j = 0; j < 3; ++j) { lo[j] = std::min(lo[j], xyz[3 * (size_t)v + j]); hi[j] = std::max(hi[j], xyz[3 * (size_t)v + j]); }
+        int ax = 0;
+        for (int j = 1; j < 3; ++j) if (hi[j] - lo[j] > hi[ax] - lo[ax]) ax = j;
+        std::sort(part.begin(), part.end());
+        std::stable_sort(part.begin(), part.end(), [&](int32_t a, int32_t b) { return xyz[3 * (size_t)a + ax] < xyz[3 * (size_t)b + ax]; });
+        const int gl = g / 2;
+        size_t nl = (size_t)((int64_t)part.size() * gl / g);
+        nl = std::min(std::max(nl, (size_t)gl), part.size() - (size_t)(g - gl));      // (every aggregate keeps a vertex)
+        std::vector<int32_t> left(part.begin(), part.begin() + nl), right(part.begin() + nl, part.end());
+        std::vector<int32_t>().swap(part);
+        split(left, gl);
+        split(right, g - gl);
+    };
+    if (nv == 0) { agg_ptr.push_back(0); return true; }
+    split(all, G);
+    return true;
 }
 
 } // namespace admm_host

@@ -135,6 +135,12 @@ public:
     struct SolveInfo { int iterations; bool converged; double residual, rhs_norm; };
     VecX tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info = nullptr, double shift = -1.0, bool psd = true, bool hold_pins = true,
                        double tol = 1e-10, int max_iters = 1000);
+    // The preconditioner of the CG behind tangent_solve, newton_polish and step_adjoint (admm_hip_set_tangent_precond): Jacobi (the
+    // default), or two-level with the affine displacements of `aggregates` compact aggregates (0: n_verts / 256 in 1 .. 64) as coarse space
+    enum class TangentPrecond { Jacobi = 0, TwoLevel = 1 };
+    struct TangentPrecondInfo { TangentPrecond kind; int aggregates, coarse_dim, coarse_dropped; bool coarse_ok; int setup_passes; };      // the last four: of the last solve
+    void set_tangent_precond(TangentPrecond kind, int aggregates = 0);
+    TangentPrecondInfo tangent_precond();
     // Projected Newton with a backtracking line search on the objective of the last step(), applied to its result; m_x and m_v are
     // updated (admm_hip_newton_polish).  One record per iterate, the first is the state the step left
     struct NewtonRecord { double objective, grad_norm, cg_iterations, step, energy; };

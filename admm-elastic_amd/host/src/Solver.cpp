@@ -716,6 +716,18 @@ VecX Solver::tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info, doub
     return y;
 }
 
+void Solver::set_tangent_precond(TangentPrecond kind, int aggregates) {
+    if (!initialized) throw std::runtime_error("Solver::set_tangent_precond: initialize() first");
+    check(admm_hip_set_tangent_precond((admm_hip_ctx *)m_ctx, (int32_t)kind, (int32_t)aggregates), "Solver::set_tangent_precond");
+}
+
+Solver::TangentPrecondInfo Solver::tangent_precond() {
+    if (!initialized) throw std::runtime_error("Solver::tangent_precond: initialize() first");
+    int32_t v[6] = {0, 0, 0, 0, 0, 0};
+    check(admm_hip_get_tangent_precond((admm_hip_ctx *)m_ctx, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]), "Solver::tangent_precond");
+    return TangentPrecondInfo{v[0] == 1 ? TangentPrecond::TwoLevel : TangentPrecond::Jacobi, (int)v[1], (int)v[2], (int)v[3], v[4] != 0, (int)v[5]};
+}
+
 std::vector<Solver::NewtonRecord> Solver::newton_polish(int max_iters, double grad_tol, double cg_tol, int cg_max) {
     if (!initialized) throw std::runtime_error("Solver::newton_polish: initialize() first");
     admm_hip_ctx *ctx = (admm_hip_ctx *)m_ctx;

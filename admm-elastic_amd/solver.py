@@ -717,6 +717,52 @@ class Solver:
                                            int(max_iters), dptr(y), dptr(info)))
         return y.reshape(-1, 3), dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]))
 
+    def set_tangent_precond(self, kind="jacobi", aggregates=None):
+        """admm_hip_set_tangent_precond: the preconditioner of the CG behind tangent_solve, newton_polish and step_adjoint, from the next
+        solve on.  "jacobi" (the default) or "two_level": D^-1 + P (P^T A P)^-1 P^T with the affine displacements of `aggregates` compact
+        aggregates of vertices (1 .. 64; None: n_verts / 256 clamped to that range) as the coarse space, rebuilt at the x of every solve.
+        Fewer iterations of six launches instead of four, plus a setup of ceil(12 aggregates / 16) block passes and a dense inverse per
+        solve.  Single-GPU contexts."""
+        self._need_ctx()
+        kinds = {"jacobi": 0, "two_level": 1}
+        if kind not in kinds:
+            raise ValueError("set_tangent_precond: kind is 'jacobi' or 'two_level'")
+        check(lib().admm_hip_set_tangent_precond(self._ctx, kinds[kind], 0 if aggregates is None else int(aggregates)))
+
+    def tangent_precond(self):
+        """admm_hip_get_tangent_precond: dict(kind, aggregates (0: the default)) and, of the last solve, coarse_dim (0: Jacobi),
+        coarse_dropped (columns of the coarse space left out: held aggregates, a flat cloth), coarse_ok (False: the coarse matrix was not
+        positive definite and the solve ran as Jacobi-PCG), setup_passes."""
+        self._need_ctx()
+        v = [C.c_int32(0) for _ in range(6)]
+        check(lib().admm_hip_get_tangent_precond(self._ctx, *[C.byref(q) for q in v]))
+        return dict(kind=("jacobi", "two_level")[v[0].value], aggregates=v[1].value, coarse_dim=v[2].value, coarse_dropped=v[3].value,
+                    coarse_ok=bool(v[4].value), setup_passes=v[5].value)
+
+    def tangent_precond_apply(self, r, x=None, shift=None, psd=True, hold_pins=True):
+        """admm_hip_tangent_precond_apply (tests): z = M^-1 r of the two-level preconditioner of the tangent frozen at x, with the
+        aggregates set by set_tangent_precond; arguments as tangent_solve."""
+        self._need_ctx()
+        xc = self._state_arg(x, "tangent_precond_apply")
+        rc = f64(r).ravel().copy()
+        if rc.size != self.m_x.size:
+            raise ValueError("tangent_precond_apply: r must hold 3 values per node")
+        if shift is None:
+            shift = 1.0 / (self._settings.timestep_s ** 2)
+        z = np.zeros(rc.size)
+        check(lib().admm_hip_tangent_precond_apply(self._ctx, dptr(xc), dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0), dptr(z)))
+        return z.reshape(-1, 3)
+
+    @staticmethod
+    def tangent_plan(xyz, aggregates):
+        """admm_host_tangent_plan (no GPU): the aggregates of the two-level tangent preconditioner for the rest positions xyz
+        [n_verts, 3] -> (agg_ptr [G + 1], agg_vert [n_verts])."""
+        xc = f64(xyz).reshape(-1, 3).copy()
+        G = int(aggregates)
+        ptr = np.zeros(max(G, 0) + 1, np.int32); vert = np.zeros(max(len(xc), 1), np.int32)
+        check(lib().admm_host_tangent_plan(len(xc), dptr(xc), G, iptr(ptr), iptr(vert)))
+        return ptr, vert[:len(xc)]
+
     def newton_polish(self, max_iters=10, grad_tol=1e-8, cg_tol=1e-8, cg_max=500):
         """admm_hip_newton_polish: projected Newton with a backtracking line search on the objective of the last step, applied to the
         device-resident state; m_x and m_v are downloaded afterwards.  Returns one dict per iterate (the first is the state the step left):

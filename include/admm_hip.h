@@ -366,6 +366,27 @@ int admm_hip_modes(admm_hip_ctx *ctx, const double *x, int32_t k, int32_t guard,
 int admm_hip_tangent_solve(admm_hip_ctx *ctx, const double *x, const double *rhs, double shift, int32_t flags, double tol, int32_t max_iters,
                            double *y, double *info4);
 
+/* The preconditioner of the CG behind admm_hip_tangent_solve, admm_hip_newton_polish and admm_hip_step_adjoint, in effect from the next
+ * solve.  kind 0 (the default): Jacobi, D^-1 with D the diagonal of A = K(x) + shift M.  kind 1: two-level, M^-1 = D^-1 + P (P^T A P)^-1 P^T
+ * with P the affine displacements {1, (x - mean) / h} (x) {e_x, e_y, e_z} of `aggregates` compact aggregates of vertices (12 columns each;
+ * zero on held vertices), the aggregates cut once by recursive coordinate bisection of desc.vert_xyz, the functions taken at the x the
+ * tangent is frozen at.  P^T A P is formed matrix-free at the start of every solve (ceil(12 aggregates / 16) block passes of the frozen
+ * tangent) and inverted on the device.  A column whose diagonal is <= 2^-40 of the largest is DROPPED (an aggregate held entirely; a flat
+ * cloth); a coarse matrix that is otherwise not positive definite (no ADMM_HIP_TANGENT_PSD at a compressed state; shift 0 with nothing
+ * held) switches the coarse term off for that solve, on the device: the solve is then Jacobi-PCG.  Six launches per iteration instead of
+ * four; bit-reproducible.  aggregates 0 means clamp(n_verts / 256, 1, 64).  With kind 0 every call returns the bits it returned before
+ * this entry point existed.  Refused (ADMM_HIP_ERR_ARG): kind outside 0 .. 1, aggregates outside 0 .. 64 or above n_verts, kind 1 on a
+ * context created without desc.vert_xyz, multi-GPU contexts. */
+int admm_hip_set_tangent_precond(admm_hip_ctx *ctx, int32_t kind, int32_t aggregates);
+/* The setting, and of the LAST solve: coarse_dim = 12 aggregates (0: it ran with Jacobi), the columns dropped, coarse_ok (1: the coarse
+ * term was used; 0: switched off), the block passes of its setup.  Any pointer may be NULL.  Synchronises the stream. */
+int admm_hip_get_tangent_precond(admm_hip_ctx *ctx, int32_t *kind, int32_t *aggregates, int32_t *coarse_dim, int32_t *coarse_dropped, int32_t *coarse_ok,
+                                 int32_t *setup_passes);
+/* Tests: z = M^-1 r of the two-level preconditioner (whatever kind is set; the aggregates as set) of the tangent frozen at x -- the setup
+ * of a solve, then one application.  x, shift, flags as admm_hip_tangent_solve; r, z_out [3 n_verts] host (r is ignored and z is 0 on
+ * held vertices).  admm_hip_get_tangent_precond then describes this setup. */
+int admm_hip_tangent_precond_apply(admm_hip_ctx *ctx, const double *x, const double *r, double shift, int32_t flags, double *z_out);
+
 /* Projected Newton on the objective of the LAST step, Phi(x) = |x - x_bar|_M^2 / (2 dt^2) + E(x) (what monitor mode 2 sums), applied to
  * the device-resident state: per iteration g = (m o x - M x_bar) / dt^2 - f(x) with the pinned rows zeroed; stop at |g| <= grad_tol;
  * else (K_psd(x) + M / dt^2) delta = -g by admm_hip_tangent_solve (both flags, cg_tol, cg_max), Armijo backtracking on Phi (c = 1e-4,
@@ -739,6 +760,10 @@ int admm_host_oc_plan_halo(const admm_hip_desc *desc, int32_t n_blocks, int32_t 
  * = 4 G, their padded count, SELL slices.  row_vertex [rows] (-1 = unused slot), row_weights [4 rows] (row r of P, energy-orthonormal per
  * aggregate), coarse_inv [nc nc] = (P^T A P)^-1 in single precision; any of the three may be NULL (call once for the sizes). */
 int admm_host_big_plan(const admm_hip_desc *desc, int32_t max_aggregates, int32_t *stats, int32_t *row_vertex, double *row_weights, float *coarse_inv);
+/* The aggregates of the two-level tangent preconditioner (admm_hip_set_tangent_precond), no GPU: the n_verts vertices at xyz [3 n_verts]
+ * in G parts (1 .. min(64, n_verts)) by recursive coordinate bisection -- the longest extent, cut at the median in a stable order.
+ * agg_ptr [G + 1], agg_vert [n_verts]: the vertices grouped by aggregate, ascending within one. */
+int admm_host_tangent_plan(int32_t n_verts, const double *xyz, int32_t G, int32_t *agg_ptr, int32_t *agg_vert);
 
 /* The plan of the PERSISTENT multi-colour Gauss-Seidel kernel (csrc/gs_persist.hpp; csrc/oc_plan.cpp: build_gs_plan) run ON THE HOST, no
  * GPU (tests): `sweeps` plain SOR sweeps (src/NodalMultiColorGS.hpp:180-216, no pins, no obstacles) over the plan's own data -- blocks, the ELL of
