@@ -123,6 +123,7 @@ SYMBOLS = [
     ("admm_hip_persistent_launches", C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
     ("admm_hip_pcg_findings", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("admm_hip_pcg_instances", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("admm_hip_pcg_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("admm_hip_device_buffers", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("admm_hip_probe_sync", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64)]),
     ("admm_hip_time_local_launches", C.c_int, [C.c_void_p, C.c_int32]),

@@ -272,6 +272,7 @@ struct admm_hip_ctx {
     DevBuf<double> oc_mdiag, oc_ainv, oc_cbuf; DevBuf<float> oc_cwt; bool oc_affine = false;
     const double *create_xyz = nullptr;   // desc.vert_xyz, valid during admm_hip_create only (coarse space of the plan)
     int64_t oc_stat[6] = {0, 0, 0, 0, 0, 0};   // nnz, stored, on chip, block-local, max neighbour blocks, coarse unknowns
+    int oc_nbr_max = 0;   // most neighbour blocks of a block of the plan, -1: a block has more than 64 (no hand-off lists; admm_hip_pcg_plan_info)
     // Recovery from a grid barrier that cannot complete (the persistent PCG kernel needs all its blocks resident at once:
     // another persistent kernel, a second context or CU masking can break that).  The state at the last point known to be
     // good is kept, with the steps issued since; a timed-out barrier (detected at the next synchronisation) switches the
@@ -1461,7 +1462,10 @@ hipError_t plan_pcg_onchip(admm_hip_ctx *c) {
     c->oc_prof_block = env_int("ADMM_HIP_OC_PROF_BLOCK", 0);
     c->oc_force_generic = env_flag("ADMM_HIP_OC_GENERIC", false);     // A/B, tests: the generic instance of k_pcg2 for every launch
     if (env_flag("ADMM_HIP_OC_PROF", false)) { if ((e = c->oc_prof.alloc(64 * 8)) != hipSuccess) return e; if ((e = c->oc_prof.zero()) != hipSuccess) return e; }
-    if (plan.nbr_ok) {      // which blocks does every block gather from?
+    c->oc_nbr_max = plan.nbr_ok ? plan.nbr_max : -1;
+    // tests (ADMM_HIP_OC_HANDOFF=0): no hand-off lists although the plan has them -- k_pcg2 orders its vector exchanges with grid barriers,
+    // as it does for a plan with more than 64 neighbour blocks of a block (same arithmetic, same bits; generic instance only)
+    if (plan.nbr_ok && env_flag("ADMM_HIP_OC_HANDOFF", true)) {      // which blocks does every block gather from?
         if ((e = c->oc_nbr.upload(plan.nbr)) != hipSuccess) return e;
         if ((e = c->oc_flags.alloc((size_t)8 * G)) != hipSuccess) return e;
         if ((e = c->oc_flags.zero()) != hipSuccess) return e;
@@ -5015,6 +5019,18 @@ int admm_hip_persistent_launches(const admm_hip_ctx *c, int64_t *pcg, int64_t *g
     if (pcg) *pcg = c->oc_launches;
     if (gs) *gs = c->gsp_launches;
     if (schur) *schur = c->uzp_launches;
+    return ADMM_HIP_OK;
+}
+
+int admm_hip_pcg_plan_info(const admm_hip_ctx *c, int64_t *out) {
+    if (!c || !out) return fail(ADMM_HIP_ERR_ARG, "pcg_plan_info: NULL argument");
+    const bool planned = c->oc_plan && c->oc_G > 0;      // (a plan the device accepted: oc_G is set behind the occupancy check)
+    out[0] = c->oc_enabled ? 1 : 0;
+    out[1] = planned ? c->oc_G : 0; out[2] = planned ? c->oc_spb : 0; out[3] = planned ? c->oc_T : 0;
+    out[4] = planned && c->oc_coarse ? 1 : 0;
+    out[5] = c->oc_nbr.p ? 1 : 0;
+    out[6] = planned ? c->oc_nbr_max : 0;
+    out[7] = c->oc_gave_up ? 1 : 0;
     return ADMM_HIP_OK;
 }
 

@@ -1027,6 +1027,16 @@ class Solver:
         check(lib().admm_hip_pcg_instances(self._ctx, C.byref(last), n, C.byref(v)))
         return dict(last=("none", "generic", "hot")[last.value], hot=n[0], generic=n[1], lane_hot=n[2], lane_generic=n[3], last_verifications=v.value)
 
+    def pcg_plan(self):
+        """admm_hip_pcg_plan_info: dict(enabled, G, spb, T, two_level, handoff, nbr_max, gave_up) -- the plan of the on-chip PCG this context
+        runs on: whether it serves the solves, its grid and block shape, the two-level preconditioner, whether the vector exchanges go by
+        the neighbour hand-off lists (False: by grid barriers), the most neighbour blocks of a block (-1: more than 64), and whether the
+        context gave the persistent kernels up after a time-out."""
+        self._need_ctx()
+        o = (C.c_int64 * 8)()
+        check(lib().admm_hip_pcg_plan_info(self._ctx, o))
+        return dict(enabled=bool(o[0]), G=o[1], spb=o[2], T=o[3], two_level=bool(o[4]), handoff=bool(o[5]), nbr_max=o[6], gave_up=bool(o[7]))
+
     def probe_sync(self, n=200):
         """admm_hip_probe_sync: (us per all-to-all, us per vector exchange, plan statistics dict) of the on-chip PCG."""
         self._need_ctx()

@@ -580,6 +580,15 @@ int admm_hip_pcg_findings(admm_hip_ctx *ctx, int32_t *smoother_given_up, int32_t
  * stream).  Any pointer may be NULL. */
 int admm_hip_pcg_instances(admm_hip_ctx *ctx, int32_t *last, int64_t *launches, int32_t *last_verifications);
 
+/* What the on-chip PCG (k_pcg2) of this context runs on, as admm_hip_create planned it (no reference counterpart; diagnostics, tests).  out[8]:
+ * [0] the on-chip solver serves the context's solves (0: no plan, the launch path was asked for, or the context gave it up); [1] blocks G,
+ * [2] waves per block, [3] threads per block T of the plan (0 without one; kept after a give-up); [4] 1 the two-level preconditioner, 0 the
+ * block smoother alone; [5] 1 the vector exchanges are ordered by the neighbour hand-off lists, 0 by grid barriers -- a plan in which a block
+ * has more than 64 neighbour blocks has no lists, and ADMM_HIP_OC_HANDOFF=0 at create leaves them out of any plan (a test switch: same
+ * arithmetic, same bits, generic instance only); [6] most neighbour blocks of a block of the plan, -1 when one has more than 64; [7] 1 after a
+ * grid barrier or hand-off timed out and the context gave the persistent kernels up for good (seen at the synchronisation behind it). */
+int admm_hip_pcg_plan_info(const admm_hip_ctx *ctx, int64_t *out);
+
 /* Device memory the library holds in this process (no reference counterpart; diagnostics, tests): the number of live device buffers of all
  * contexts and their total size in bytes.  A destroyed context leaves none of its own behind.  Any pointer may be NULL. */
 int admm_hip_device_buffers(int64_t *buffers, int64_t *bytes);

@@ -11,7 +11,7 @@ make_solve_entry_parent_bits.py (whose helpers are used), on the cases the earli
     launch takes the new path and the later ones the exchange, within one launch;
   * a cap of three iterations: solves that end unconverged, from a cold first frame on.
 No plan of these scenes has a block with more than 64 neighbour blocks (at most 22, tests/test_halo_vert_plan.py prints them), so none
-reaches the kernel's path without hand-off lists.
+reaches the kernel's path without hand-off lists by itself; tests/test_pcg2_no_handoff.py runs these cases on it with ADMM_HIP_OC_HANDOFF=0.
 
 Run ONCE, on the GPU, with the library of the commit the fixture is named after, in a checkout of that commit (this file copied into its
 tests/golden; the generators it imports are there):

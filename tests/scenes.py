@@ -199,6 +199,35 @@ def bodies_scene(cells, kinds=None, gap=1.6, **settings):
     return sc
 
 
+def hub_scene(n_rim=4300, radius=0.5, **settings):
+    """One vertex of very high valence: a hub at the origin (vertex 0), a Fibonacci sphere of `n_rim` points around it (vertices 1 ..
+    n_rim, from the top down), the sphere triangulated by its convex hull, one tet (hub, a, b, c) per hull triangle -- 2 n_rim - 4 tets,
+    the hub's matrix row has n_rim off-diagonal entries.  Neo-Hookean soft rubber, the eight highest rim vertices pinned.  Whatever the
+    on-chip PCG's partition does with the rim, the hub's block neighbours every other block: at one wave per block (n_rim = 4300: 68
+    blocks) that is more than the 64 neighbour blocks a hand-off list holds (csrc/oc_plan.cpp).  numpy and scipy only, deterministic."""
+    from scipy.spatial import ConvexHull
+    i = np.arange(n_rim)
+    y = 1.0 - (2.0 * i + 1.0) / n_rim
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    rho = np.sqrt(1.0 - y * y)
+    rim = radius * np.stack([rho * np.cos(phi), y, rho * np.sin(phi)], axis=1)
+    tri = np.sort(ConvexHull(rim).simplices, axis=1)
+    tri = tri[np.lexsort((tri[:, 2], tri[:, 1], tri[:, 0]))]      # (an order of our own, not the hull code's)
+    assert len(tri) == 2 * n_rim - 4 and len(np.unique(tri)) == n_rim
+    verts = np.concatenate([np.zeros((1, 3)), rim])
+    tets = np.concatenate([np.zeros((len(tri), 1), np.int64), tri + 1], axis=1)
+    flip = meshes.tet_volumes(verts, tets) < 0.0
+    tets[flip] = tets[flip][:, [0, 2, 1, 3]]
+    tets = tets.astype(np.int32)
+    assert (meshes.tet_volumes(verts, tets) > 0.0).all()
+    sc = Scene()
+    sc.add_tet_mesh(verts, tets, Lame.soft_rubber(), pkg.TET_NEOHOOKEAN)
+    for v in np.argsort(-verts[:, 1], kind="stable")[:8]:
+        sc.pins[int(v)] = verts[v].copy()
+    sc.settings.update(settings)
+    return sc
+
+
 def blob_scene(n, jitter=0.15, seed=0, order="rcm", **settings):
     """BASELINE configs[2] on an UNSTRUCTURED body: meshes.unstructured_blob (valences 3..26, not 2-colourable, no exact
     zeros in Ahat), numbered randomly like a mesh file and renumbered for locality as the samples do; Neo-Hookean / StVK

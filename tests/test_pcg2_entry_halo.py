@@ -10,7 +10,8 @@ from an x0 with -0.0, denormals, 1e-100 and 1e100 at halo vertices and with b = 
 instance serves a case it is repeated on the forced generic instance; both must agree with each other and with the fixture.
 
 No plan of a small scene reaches the kernel's path without hand-off lists (a block with more than 64 neighbour blocks): blob_scene(30) at
-one wave per block has at most 22, mixed_cube_scene(12) at most 19 (tests/test_halo_vert_plan.py prints them).  That path is not run here."""
+one wave per block has at most 22, mixed_cube_scene(12) at most 19 (tests/test_halo_vert_plan.py prints them).  That path is run by
+tests/test_pcg2_no_handoff.py: on these cases with ADMM_HIP_OC_HANDOFF=0, held to this fixture as well, and on scenes.hub_scene(), whose plan has it."""
 import importlib.util
 import json
 import os
