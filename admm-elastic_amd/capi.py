@@ -101,6 +101,9 @@ SYMBOLS = [
     ("admm_hip_set_tangent_precond", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("admm_hip_get_tangent_precond", C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]),
     ("admm_hip_tangent_precond_apply", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p]),
+    ("admm_hip_set_tangent_coarse", C.c_int, [C.c_void_p, C.c_int32]),
+    ("admm_hip_get_tangent_coarse", C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p]),
+    ("admm_hip_tangent_coarse_invert", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_int_p, c_int_p]),
     ("admm_hip_newton_polish", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_param_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_step_adjoint", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_int32] + [c_double_p] * 9),

@@ -29,6 +29,7 @@
 #include "adjoint.hpp"
 #include "modal.hpp"
 #include "tangent_precond.hpp"
+#include "tangent_coarse.hpp"
 #include "anderson.hpp"
 #include "pcg_onchip2.hpp"
 #include "pcg_big.hpp"
@@ -442,6 +443,10 @@ struct admm_hip_ctx {
     int tc_kind = 0, tc_aggregates = 0;      // in effect from the next solve: 0 Jacobi, 1 two-level; aggregates wanted (0: n_verts / 256 in 1 .. 64)
     int tc_G = 0, tc_nc = 0, tc_ncb = 0;     // of the buffers: aggregates planned, 12 G, blocks of k_tc_coarse
     int tc_last_nc = 0, tc_last_passes = 0;  // the last solve: coarse dimension (0: Jacobi), block passes of its setup
+    // the dense inverse behind it (admm_hip_set_tangent_coarse): 0 one block (k_tc_invert), 1 blocked over the chip (tangent_coarse.hpp), in
+    // effect from the next solve; the launches of the last inverse; the blocked chain's scratch, allocated only when it is selected
+    int tc_coarse_solver = 0, tc_last_launches = 0;
+    DevBuf<double> tcb_W, tcb_Linv;          // [nc][nc]: L^-1; [ceil(nc / 64)][64][64]: the inverted diagonal tiles
     std::vector<double> tc_xyz_h;            // desc.vert_xyz (the aggregates are cut in the rest positions)
     DevBuf<int> tc_agg_ptr, tc_agg_vert, tc_agg_of, tc_keep, tc_info;      // [G + 1], [nv], [nv]; tc_invert's columns kept [nc]; {flag, coarse_ok, dropped}
     DevBuf<double> tc_phi, tc_d, tc_ad, tc_Ac, tc_As, tc_Ainv, tc_ds, tc_dl, tc_col, tc_c, tc_yc, tc_cpart;      // [nv][4]; [16][3 nv] twice; [nc][nc] three times; [nc] five times; [ncb]
@@ -1008,7 +1013,13 @@ int modes_device(admm_hip_ctx *c, const double *xd, int k, int nb, double shift,
 int tc_ensure(admm_hip_ctx *c) {
     const int nv = c->nv;
     const int G = c->tc_aggregates > 0 ? c->tc_aggregates : std::min(kTcMaxAgg, std::max(1, nv / 256));
-    if (c->tc_G == G) return ADMM_HIP_OK;
+    if (c->tc_G == G && (c->tc_coarse_solver == 0 || c->tcb_W.p)) return ADMM_HIP_OK;
+    if (c->tc_G == G) {      // the blocked inverse was selected after the buffers were made: its scratch alone
+        const size_t nc = (size_t)c->tc_nc, ntile = (size_t)admm_dev::tcb_tiles(c->tc_nc);
+        HIP_TRY(c->tcb_W.alloc_zeroed(nc * nc, c->stream));
+        HIP_TRY(c->tcb_Linv.alloc_zeroed(ntile * admm_dev::kTcbT * admm_dev::kTcbT, c->stream));
+        return ADMM_HIP_OK;
+    }
     if (c->tc_xyz_h.size() != (size_t)c->n3) return fail(ADMM_HIP_ERR_ARG, "tangent_precond: the two-level preconditioner needs desc.vert_xyz (the aggregates are cut in the rest positions)");
     std::vector<int32_t> ptr, vert;
     if (!admm_host::tangent_plan(nv, c->tc_xyz_h.data(), G, ptr, vert)) return fail(ADMM_HIP_ERR_ARG, "tangent_precond: more aggregates than vertices");
@@ -1026,9 +1037,35 @@ int tc_ensure(admm_hip_ctx *c) {
     for (DevBuf<double> *b : {&c->tc_Ac, &c->tc_As, &c->tc_Ainv}) HIP_TRY(b->alloc_zeroed(nc * nc, st));
     for (DevBuf<double> *b : {&c->tc_ds, &c->tc_dl, &c->tc_col, &c->tc_c, &c->tc_yc}) HIP_TRY(b->alloc_zeroed(nc, st));
     HIP_TRY(c->tc_cpart.alloc_zeroed(ncb, st));
+    c->tcb_W.release(); c->tcb_Linv.release();
+    if (c->tc_coarse_solver == 1) {
+        HIP_TRY(c->tcb_W.alloc_zeroed(nc * nc, st));
+        HIP_TRY(c->tcb_Linv.alloc_zeroed((size_t)admm_dev::tcb_tiles((int)nc) * admm_dev::kTcbT * admm_dev::kTcbT, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));      // (ptr and vert leave scope)
     c->tc_G = G; c->tc_nc = (int)nc; c->tc_ncb = (int)ncb;
     return ADMM_HIP_OK;
+}
+// The blocked inverse (tangent_coarse.hpp): X = A^-1 by the chain of k_tcb_ launches; A [n][n] is destroyed.  info = {flag, ok, dropped} as
+// k_tc_invert's.  Returns the launches.
+int launch_tcb_invert(hipStream_t st, int n, double *A, double *X, double *ds, int *keep, int *info, double *Linv, double *Wm) {
+    const int ntile = admm_dev::tcb_tiles(n), grid = std::min(1024, blocks_for(n * n));
+    int *flag = info;
+    int launches = 0;
+    hipLaunchKernelGGL(k_tcb_scan, dim3(1), dim3(256), 0, st, n, A, ds, keep, flag, info + 1); ++launches;
+    hipLaunchKernelGGL(k_tcb_scale, dim3(grid), dim3(256), 0, st, n, A, ds, keep, flag); ++launches;
+    for (int k = 0; k < ntile; ++k) {
+        const int m = ntile - k - 1;      // tile rows below the diagonal tile
+        hipLaunchKernelGGL(k_tcb_potrf, dim3(1), dim3(256), 0, st, n, k, A, Linv, flag); ++launches;
+        if (!m) break;
+        hipLaunchKernelGGL(k_tcb_panel, dim3(m), dim3(256), 0, st, n, k, A, Linv, flag); ++launches;
+        hipLaunchKernelGGL(k_tcb_update, dim3(m * (m + 1) / 2), dim3(256), 0, st, n, k, A, flag); ++launches;
+    }
+    hipLaunchKernelGGL(k_tcb_winv, dim3(ntile, admm_dev::kTcbT / admm_dev::kTcbStrip), dim3(256), 0, st, n, A, Linv, Wm, flag); ++launches;
+    hipLaunchKernelGGL(k_tcb_wtw, dim3(ntile * (ntile + 1) / 2), dim3(256), 0, st, n, Wm, X, flag); ++launches;
+    hipLaunchKernelGGL(k_tcb_unscale, dim3(grid), dim3(256), 0, st, n, X, ds, keep, flag); ++launches;
+    hipLaunchKernelGGL(k_tcb_final, dim3(grid), dim3(256), 0, st, n, X, flag, info + 1); ++launches;
+    return launches;
 }
 // A_c^-1 of the tangent frozen at xd (frames and nw_dinv are in place): the basis, A P in block passes of kModalNb columns, P^T (A P), the inverse
 void launch_tc_setup(admm_hip_ctx *c, const double *xd, double shift, const int *pin) {
@@ -1044,7 +1081,11 @@ void launch_tc_setup(admm_hip_ctx *c, const double *xd, double shift, const int 
         hipLaunchKernelGGL(k_tc_restrict_block, dim3(G, n), dim3(256), 0, st, nc, col0, n3, c->tc_agg_ptr.p, c->tc_agg_vert.p, c->tc_phi.p, c->tc_ad.p, c->tc_Ac.p);
     }
     hipLaunchKernelGGL(k_tc_sym, dim3(blocks_for(nc * nc)), dim3(256), 0, st, nc, c->tc_Ac.p, c->tc_As.p);
-    hipLaunchKernelGGL(k_tc_invert, dim3(1), dim3(1024), 0, st, nc, c->tc_As.p, c->tc_Ainv.p, c->tc_ds.p, c->tc_dl.p, c->tc_col.p, c->tc_keep.p, c->tc_info.p, c->tc_info.p + 1);
+    if (c->tc_coarse_solver == 1) c->tc_last_launches = launch_tcb_invert(st, nc, c->tc_As.p, c->tc_Ainv.p, c->tc_ds.p, c->tc_keep.p, c->tc_info.p, c->tcb_Linv.p, c->tcb_W.p);
+    else {
+        hipLaunchKernelGGL(k_tc_invert, dim3(1), dim3(1024), 0, st, nc, c->tc_As.p, c->tc_Ainv.p, c->tc_ds.p, c->tc_dl.p, c->tc_col.p, c->tc_keep.p, c->tc_info.p, c->tc_info.p + 1);
+        c->tc_last_launches = 1;
+    }
     c->tc_last_nc = nc;
 }
 // r = nw_rhs on the free rows, y = 0, p = z = M^-1 r and the scalars of iteration 0 (the stop word is 0 on entry)
@@ -4362,6 +4403,51 @@ int admm_hip_tangent_precond_apply(admm_hip_ctx *c, const double *x, const doubl
     HIP_TRY(hipGetLastError());
     if (c->n3) HIP_TRY(hipMemcpyAsync(z_out, c->nw_p.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return ADMM_HIP_OK;
+}
+// The dense inverse behind the two-level preconditioner: 0 one block (k_tc_invert), 1 blocked over the chip (tangent_coarse.hpp)
+int admm_hip_set_tangent_coarse(admm_hip_ctx *c, int32_t solver) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "set_tangent_coarse: NULL context");
+    if (solver < 0 || solver > 1) return fail(ADMM_HIP_ERR_ARG, "set_tangent_coarse: solver is 0 (one block) or 1 (blocked)");
+    if (int rc = mon_refuse(c, "set_tangent_coarse")) return rc;
+    c->tc_coarse_solver = solver;
+    return ADMM_HIP_OK;
+}
+int admm_hip_get_tangent_coarse(admm_hip_ctx *c, int32_t *solver, int32_t *tile, int32_t *last_launches) {
+    if (!c) return fail(ADMM_HIP_ERR_ARG, "get_tangent_coarse: NULL context");
+    if (solver) *solver = c->tc_coarse_solver;
+    if (tile) *tile = admm_dev::kTcbT;
+    if (last_launches) *last_launches = c->tc_last_launches;
+    return ADMM_HIP_OK;
+}
+// X = A^-1 by the selected inverse on the device (tests), in scratch of its own: no tc_ buffer of the context is touched
+int admm_hip_tangent_coarse_invert(admm_hip_ctx *c, int32_t n, const double *A_host, double *X_host, int32_t *ok, int32_t *dropped) {
+    if (!c || !A_host || !X_host || !ok || !dropped) return fail(ADMM_HIP_ERR_ARG, "tangent_coarse_invert: NULL argument");
+    if (n < 1 || n > kTcMaxAgg * kTcPer) return fail(ADMM_HIP_ERR_ARG, "tangent_coarse_invert: n in 1 .. 768");
+    if (int rc = mon_refuse(c, "tangent_coarse_invert")) return rc;
+    if (int rc = quiesce(c)) return rc;
+    hipStream_t st = c->stream;
+    const size_t nn = (size_t)n * n;
+    DevBuf<double> A, X, ds, dl, col, Linv, Wm;
+    DevBuf<int> keep, info;
+    HIP_TRY(A.alloc(nn)); HIP_TRY(X.alloc_zeroed(nn, st));
+    for (DevBuf<double> *b : {&ds, &dl, &col}) HIP_TRY(b->alloc_zeroed((size_t)n, st));
+    HIP_TRY(keep.alloc_zeroed((size_t)n, st)); HIP_TRY(info.alloc_zeroed(3, st));
+    HIP_TRY(hipMemcpyAsync(A.p, A_host, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    if (c->tc_coarse_solver == 1) {
+        HIP_TRY(Wm.alloc_zeroed(nn, st));
+        HIP_TRY(Linv.alloc_zeroed((size_t)admm_dev::tcb_tiles(n) * admm_dev::kTcbT * admm_dev::kTcbT, st));
+        c->tc_last_launches = launch_tcb_invert(st, n, A.p, X.p, ds.p, keep.p, info.p, Linv.p, Wm.p);
+    } else {
+        hipLaunchKernelGGL(k_tc_invert, dim3(1), dim3(1024), 0, st, n, A.p, X.p, ds.p, dl.p, col.p, keep.p, info.p, info.p + 1);
+        c->tc_last_launches = 1;
+    }
+    HIP_TRY(hipGetLastError());
+    int h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(X_host, X.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *ok = h[1]; *dropped = h[2];
     return ADMM_HIP_OK;
 }
 int admm_host_tangent_plan(int32_t n_verts, const double *xyz, int32_t G, int32_t *agg_ptr, int32_t *agg_vert) {

@@ -12,6 +12,7 @@
 //   k_tc_restrict_block   grid = aggregates x columns: the 12 entries (aggregate's rows, column) of P^T (A P), summed in agg_vert order
 //   k_tc_sym              A_c <- (A_c + A_c^T) / 2
 //   k_tc_invert           one block of 1024 threads, the matrix in global memory: device_math.hpp: tc_invert -- dropped columns, the verdict
+//                         (or, with admm_hip_set_tangent_coarse(1), the k_tcb_ chain of tangent_coarse.hpp: the same contract in 64 x 64 tiles)
 // and per CG iteration, behind the unchanged frozen pass on p (z = D^-1 r + P y_c is not stored):
 //   k_tc_cg_step          k_nw_cg_step's arithmetic: alpha; y, r; partials of r . D^-1 r and r . r
 //   k_tc_restrict         block = aggregate: c = P^T r

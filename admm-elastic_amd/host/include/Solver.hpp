@@ -141,6 +141,12 @@ public:
     struct TangentPrecondInfo { TangentPrecond kind; int aggregates, coarse_dim, coarse_dropped; bool coarse_ok; int setup_passes; };      // the last four: of the last solve
     void set_tangent_precond(TangentPrecond kind, int aggregates = 0);
     TangentPrecondInfo tangent_precond();
+    // The dense inverse of the coarse matrix behind the two-level preconditioner (admm_hip_set_tangent_coarse): one workgroup (the
+    // default), or blocked in 64 x 64 tiles over the chip; launches: of the last inverse
+    enum class TangentCoarse { OneBlock = 0, Blocked = 1 };
+    struct TangentCoarseInfo { TangentCoarse solver; int tile, launches; };
+    void set_tangent_coarse(TangentCoarse solver);
+    TangentCoarseInfo tangent_coarse();
     // Projected Newton with a backtracking line search on the objective of the last step(), applied to its result; m_x and m_v are
     // updated (admm_hip_newton_polish).  One record per iterate, the first is the state the step left
     struct NewtonRecord { double objective, grad_norm, cg_iterations, step, energy; };

@@ -728,6 +728,18 @@ Solver::TangentPrecondInfo Solver::tangent_precond() {
     return TangentPrecondInfo{v[0] == 1 ? TangentPrecond::TwoLevel : TangentPrecond::Jacobi, (int)v[1], (int)v[2], (int)v[3], v[4] != 0, (int)v[5]};
 }
 
+void Solver::set_tangent_coarse(TangentCoarse solver) {
+    if (!initialized) throw std::runtime_error("Solver::set_tangent_coarse: initialize() first");
+    check(admm_hip_set_tangent_coarse((admm_hip_ctx *)m_ctx, (int32_t)solver), "Solver::set_tangent_coarse");
+}
+
+Solver::TangentCoarseInfo Solver::tangent_coarse() {
+    if (!initialized) throw std::runtime_error("Solver::tangent_coarse: initialize() first");
+    int32_t v[3] = {0, 0, 0};
+    check(admm_hip_get_tangent_coarse((admm_hip_ctx *)m_ctx, &v[0], &v[1], &v[2]), "Solver::tangent_coarse");
+    return TangentCoarseInfo{v[0] == 1 ? TangentCoarse::Blocked : TangentCoarse::OneBlock, (int)v[1], (int)v[2]};
+}
+
 std::vector<Solver::NewtonRecord> Solver::newton_polish(int max_iters, double grad_tol, double cg_tol, int cg_max) {
     if (!initialized) throw std::runtime_error("Solver::newton_polish: initialize() first");
     admm_hip_ctx *ctx = (admm_hip_ctx *)m_ctx;

@@ -753,6 +753,37 @@ class Solver:
         check(lib().admm_hip_tangent_precond_apply(self._ctx, dptr(xc), dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0), dptr(z)))
         return z.reshape(-1, 3)
 
+    def set_tangent_coarse(self, solver="one_block"):
+        """admm_hip_set_tangent_coarse: the dense inverse of the coarse matrix behind the two-level preconditioner, from the next solve on.
+        "one_block" (the default): one workgroup on the matrix in global memory.  "blocked": a tiled Cholesky and a tiled L^-T L^-1 in
+        64 x 64 tiles held in LDS, one launch per phase spread over the chip; the same rules for dropped columns and for a matrix that is
+        not positive definite, the two inverses differ by rounding.  Single-GPU contexts."""
+        self._need_ctx()
+        solvers = {"one_block": 0, "blocked": 1}
+        if solver not in solvers:
+            raise ValueError("set_tangent_coarse: solver is 'one_block' or 'blocked'")
+        check(lib().admm_hip_set_tangent_coarse(self._ctx, solvers[solver]))
+
+    def tangent_coarse(self):
+        """admm_hip_get_tangent_coarse: dict(solver, tile (of the blocked inverse), launches (kernel launches of the last inverse: the
+        setup of the last two-level solve, or a later tangent_coarse_invert)))."""
+        self._need_ctx()
+        v = [C.c_int32(0) for _ in range(3)]
+        check(lib().admm_hip_get_tangent_coarse(self._ctx, *[C.byref(q) for q in v]))
+        return dict(solver=("one_block", "blocked")[v[0].value], tile=v[1].value, launches=v[2].value)
+
+    def tangent_coarse_invert(self, A):
+        """admm_hip_tangent_coarse_invert (tests): the selected inverse on the device of a symmetric A [n, n], 1 <= n <= 768 ->
+        (X, ok, dropped); ok False: A is not positive definite (or not finite) and X = 0."""
+        self._need_ctx()
+        Ac = np.ascontiguousarray(f64(A))
+        if Ac.ndim != 2 or Ac.shape[0] != Ac.shape[1] or not 1 <= Ac.shape[0] <= 768:
+            raise ValueError("tangent_coarse_invert: A must be [n, n] with 1 <= n <= 768")
+        X = np.zeros_like(Ac)
+        ok = C.c_int32(0); dropped = C.c_int32(0)
+        check(lib().admm_hip_tangent_coarse_invert(self._ctx, int(Ac.shape[0]), dptr(Ac), dptr(X), C.byref(ok), C.byref(dropped)))
+        return X, bool(ok.value), int(dropped.value)
+
     @staticmethod
     def tangent_plan(xyz, aggregates):
         """admm_host_tangent_plan (no GPU): the aggregates of the two-level tangent preconditioner for the rest positions xyz

@@ -386,6 +386,21 @@ int admm_hip_get_tangent_precond(admm_hip_ctx *ctx, int32_t *kind, int32_t *aggr
  * of a solve, then one application.  x, shift, flags as admm_hip_tangent_solve; r, z_out [3 n_verts] host (r is ignored and z is 0 on
  * held vertices).  admm_hip_get_tangent_precond then describes this setup. */
 int admm_hip_tangent_precond_apply(admm_hip_ctx *ctx, const double *x, const double *r, double shift, int32_t flags, double *z_out);
+/* The dense inverse of the coarse matrix P^T A P behind the two-level preconditioner, in effect from the next solve.  solver 0 (the
+ * default): one workgroup on the matrix in global memory.  solver 1: BLOCKED, a tiled Cholesky and a tiled L^-T L^-1 in 64 x 64 tiles
+ * held in LDS, one launch per phase spread over the chip (about 40 launches at 64 aggregates), with the same rules for dropped columns
+ * and for a matrix that is not positive definite; the two inverses differ by rounding.  Bit-reproducible; with solver 0 every call
+ * returns the bits it returned before this entry point existed.  Refused (ADMM_HIP_ERR_ARG): solver outside 0 .. 1, multi-GPU contexts. */
+int admm_hip_set_tangent_coarse(admm_hip_ctx *ctx, int32_t solver);
+/* The setting, the tile size of the blocked inverse, and the kernel launches of the LAST inverse (1 with solver 0; 0 before the first).
+ * The last inverse is the setup of the last two-level solve or application, OR a later call of admm_hip_tangent_coarse_invert: the test
+ * hook counts here too.  Any pointer may be NULL. */
+int admm_hip_get_tangent_coarse(admm_hip_ctx *ctx, int32_t *solver, int32_t *tile, int32_t *last_launches);
+/* Tests: X = A^-1 by the selected inverse, on the device, of a caller's symmetric A [n][n] (host, row-major), 1 <= n <= 768 (n need not be
+ * a multiple of 12 or of the tile).  *ok = 1 and *dropped = the columns with a diagonal <= 2^-40 of the largest (their rows and columns
+ * of X are zero, the rest is the inverse of the rest), or *ok = 0 and X = 0 for a matrix that is not positive definite or not finite.
+ * Runs in scratch of its own: a tangent solve after it returns the bits it would have returned without it.  Synchronises the stream. */
+int admm_hip_tangent_coarse_invert(admm_hip_ctx *ctx, int32_t n, const double *A_host, double *X_host, int32_t *ok, int32_t *dropped);
 
 /* Projected Newton on the objective of the LAST step, Phi(x) = |x - x_bar|_M^2 / (2 dt^2) + E(x) (what monitor mode 2 sums), applied to
  * the device-resident state: per iteration g = (m o x - M x_bar) / dt^2 - f(x) with the pinned rows zeroed; stop at |g| <= grad_tol;
