@@ -96,6 +96,8 @@ SYMBOLS = [
     ("admm_hip_stiffness_apply", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.c_double, c_double_p]),
     ("admm_hip_stiffness_apply_ex", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.c_double, C.c_int32, c_double_p]),
     ("admm_hip_tangent_solve", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p]),
+    ("admm_hip_tangent_solve_block", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p,
+                                               c_double_p, c_double_p]),
     ("admm_hip_modes", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p,
                                  c_double_p, c_double_p]),
     ("admm_hip_set_tangent_precond", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -107,6 +109,7 @@ SYMBOLS = [
     ("admm_hip_newton_polish", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, c_int_p, c_double_p]),
     ("admm_hip_param_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_step_adjoint", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_int32] + [c_double_p] * 9),
+    ("admm_hip_step_adjoint_block", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_int32] + [c_double_p] * 10),
     ("admm_hip_rest_sensitivity", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     ("admm_hip_adjoint_held", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("admm_hip_residuals", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

@@ -434,6 +434,12 @@ struct admm_hip_ctx {
     // the frozen pass on a block of directions (newton.hpp: k_tangent_frozen_block; admm_hip_stiffness_apply_ex with ADMM_HIP_TANGENT_BLOCK,
     // admm_hip_modes): the scratch of up to kModalNb directions and the columns of a blocked stiffness_apply_ex, allocated by the first call
     ElemScratch bk_el; DevBuf<double> bk_d, bk_out;      // [n_vec][3 nv] each
+    // block PCG (newton.hpp; admm_hip_tangent_solve_block, admm_hip_step_adjoint_block): buffers of their own for bp_cols <= kNwBlkCols
+    // columns, allocated by the first call and again by a call with a wider slab -- never per call
+    int bp_cols = 0;
+    DevBuf<double> bp_rhs, bp_y, bp_r, bp_p, bp_ap, bp_part, bp_rr;      // [bp_cols][3 nv] five times; partials [bp_cols][3][blocks]; true residuals [kNwBlkCols]
+    DevBuf<NwCg> bp_st; DevBuf<NwBlockCtl> bp_ctl;                       // the scalars [kNwBlkCols][3]; the column lists and counters
+    DevBuf<double> adj_bl, adj_bout;                                     // the adjoint's stacks: Lx, Lv [2][bp_cols][3 nv]; the gradients [bp_cols][4][3 nv]
     // block eigensolver (modal.hpp; admm_hip_modes): buffers of their own, allocated by the first call
     DevBuf<double> md_S, md_AS, md_theta, md_rpart, md_gpart, md_GA, md_GM, md_C;
     DevBuf<ModalSt> md_st; int md_nbg = 0, md_tpb = 0;
@@ -917,17 +923,128 @@ DirStrides block_strides(const admm_hip_ctx *c) {      // (the sizes of ElemScra
 }
 // out_j = K_frozen d_j + shift m o d_j (rows of held vertices zero), j < n_vec <= kModalNb; d, out: [n_vec][3 nv].  Column j has the bits
 // of launch_frozen on d_j.
-void launch_frozen_block(admm_hip_ctx *c, const double *d, double *out, int n_vec, double shift, const int *pin, const int *stop) {
+// With `cols` (device: {n, columns}) only the listed columns are applied; with `part` the gather leaves the partials of d_j . out_j at
+// part[j][0][blocks] of [n_vec][3][blocks] and adds the list's length to *passes (the block PCG, below).
+void launch_frozen_block(admm_hip_ctx *c, const double *d, double *out, int n_vec, double shift, const int *pin, const int *stop,
+                         const int *cols = nullptr, double *part = nullptr, int *passes = nullptr) {
     FrozenBlockArgs b{};
     b.fa = frozen_args(c, nullptr, d, 0, stop);
     b.fa.f.rec = c->bk_el.rec.p; b.fa.f.r_cf = c->bk_el.rcf.p; b.fa.f.h_cf = c->bk_el.hcf.p;
-    b.n_vec = n_vec; b.s = block_strides(c);
+    b.n_vec = n_vec; b.s = block_strides(c); b.cols = cols;
     const int nb = b.fa.f.nb_r + blocks_for(c->nbend);
     if (nb > 0) hipLaunchKernelGGL(k_tangent_frozen_block, dim3(nb), dim3(256), 0, c->stream, b);
     NewtonGatherBlockArgs q{};
     q.n = newton_gather_args(c, b.fa, d, out, shift, pin, stop);
-    q.s = b.s;
-    hipLaunchKernelGGL(k_newton_gather_block, dim3(nw_blocks(c), n_vec), dim3(256), 0, c->stream, q);
+    q.s = b.s; q.cols = cols; q.spart = (size_t)3 * nw_blocks(c); q.passes = passes;
+    if (part) {
+        q.n.part = part;
+        hipLaunchKernelGGL(k_newton_gather_block<true>, dim3(nw_blocks(c), n_vec), dim3(256), 0, c->stream, q);
+    } else hipLaunchKernelGGL(k_newton_gather_block<false>, dim3(nw_blocks(c), n_vec), dim3(256), 0, c->stream, q);
+}
+static_assert(kNwBlkCols == kModalNb, "newton.hpp and modal.hpp disagree on the widest block");
+static_assert(kNwBlkCols <= kSensCols, "one k_param_sens pass takes a slab of the block adjoint");
+// room for a slab of `cols` <= kNwBlkCols columns of the block PCG
+hipError_t block_pcg_ensure(admm_hip_ctx *c, int cols) {
+    hipError_t e;
+    hipStream_t st = c->stream;
+    if ((e = c->bk_el.ensure(c, cols)) != hipSuccess) return e;
+    if (!c->bp_st.p && (e = c->bp_st.alloc_zeroed((size_t)3 * kNwBlkCols, st)) != hipSuccess) return e;
+    if (!c->bp_ctl.p && (e = c->bp_ctl.alloc_zeroed(1, st)) != hipSuccess) return e;
+    if (!c->bp_rr.p && (e = c->bp_rr.alloc_zeroed(kNwBlkCols, st)) != hipSuccess) return e;
+    if (cols <= c->bp_cols) return hipSuccess;
+    c->bp_cols = 0;
+    const size_t n = (size_t)cols * std::max(1, c->n3);
+    for (DevBuf<double> *b : {&c->bp_rhs, &c->bp_y, &c->bp_r, &c->bp_p, &c->bp_ap})
+        if ((e = b->alloc_zeroed(n, st)) != hipSuccess) return e;
+    if ((e = c->bp_part.alloc_zeroed((size_t)cols * 3 * nw_blocks(c), st)) != hipSuccess) return e;
+    c->bp_cols = cols;
+    return hipSuccess;
+}
+NwBlockArgs block_pcg_args(admm_hip_ctx *c, int k, const int *pin, double tol, int max_iters) {
+    NwBlockArgs a{};
+    a.nv = c->nv; a.nb = nw_blocks(c); a.k = k; a.sv = (size_t)c->n3;
+    a.rhs = c->bp_rhs.p; a.dinv = c->nw_dinv.p; a.pin = pin;
+    a.y = c->bp_y.p; a.r = c->bp_r.p; a.p = c->bp_p.p; a.ap = c->bp_ap.p; a.part = c->bp_part.p; a.rr = c->bp_rr.p;
+    a.st = c->bp_st.p; a.ctl = c->bp_ctl.p; a.stop = c->nw_stop.p; a.tol2 = tol * tol; a.max_iters = max_iters;
+    return a;
+}
+// The block Jacobi-PCG on the k <= kNwBlkCols columns of bp_rhs (newton.hpp): the frames and nw_dinv are in place (the caller ran the
+// setup of tangent_solve_device once for all slabs).  The host loop of tangent_solve_device: chunks of 8 iterations of four launches, one
+// chunk ahead, one pinned stop word per chunk.  Leaves y in bp_y, the verdicts in bp_st[j][2], the true residuals in bp_rr, the column
+// passes in bp_ctl; the caller synchronises.
+int tangent_solve_block_device(admm_hip_ctx *c, int k, double shift, const int *pin, double tol, int max_iters) {
+    hipStream_t st = c->stream;
+    const int nb = nw_blocks(c);
+    const NwBlockArgs a = block_pcg_args(c, k, pin, tol, max_iters);
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_nw_cg_init_block, dim3(nb, k), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_nw_cg_init2_block, dim3(1), dim3(256), 0, st, a);
+    constexpr int chunk = 8;
+    int launched = 0, chunks = 0;
+    while (launched < max_iters) {
+        const int n = std::min(chunk, max_iters - launched);
+        for (int it = launched; it < launched + n; ++it) {
+            launch_frozen_block(c, a.p, a.ap, k, shift, pin, c->nw_stop.p, a.ctl->list[it & 1], a.part, a.ctl->passes);
+            hipLaunchKernelGGL(k_nw_cg_step_block, dim3(nb, k), dim3(256), 0, st, it, a);
+            hipLaunchKernelGGL(k_nw_cg_dir_block, dim3(nb, k), dim3(256), 0, st, it, a);
+        }
+        launched += n;
+        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
+        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
+            if (c->nw_hstop[(chunks - 1) & 1]) break;
+        }
+        ++chunks;
+    }
+    launch_frozen_block(c, a.y, a.ap, k, shift, pin, nullptr);      // the TRUE residuals of the returned iterates (tangent_solve_device), every column
+    hipLaunchKernelGGL(k_nw_true_resid_block, dim3(nb, k), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_nw_resid_final_block, dim3(k), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return ADMM_HIP_OK;
+}
+struct BlockVerdict { NwCg st[kNwBlkCols]; double rr[kNwBlkCols]; int passes = 0, iters = 0; };
+// the setup all slabs of a blocked call share (that of tangent_solve_device); -> the pin mask in effect
+const int *block_solve_setup(admm_hip_ctx *c, const double *xd, double shift, int flags) {
+    c->tc_last_nc = 0; c->tc_last_passes = 0;
+    const int *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, pin);
+    return pin;
+}
+// One slab: the k <= kNwBlkCols columns of bp_rhs -> bp_y, bp_st[j][2], bp_rr.  blocked: the block PCG behind block_solve_setup; else
+// column after column through tangent_solve_device (the two-level preconditioner has no block form): the launches and the bits of
+// single calls.  Enqueues only.
+int block_solve_slab(admm_hip_ctx *c, const double *xd, int k, double shift, int flags, const int *pin, double tol, int max_iters, bool blocked) {
+    if (blocked) return tangent_solve_block_device(c, k, shift, pin, tol, max_iters);
+    hipStream_t st = c->stream;
+    const size_t n3 = (size_t)c->n3;
+    for (int j = 0; j < k; ++j) {
+        if (n3) HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, c->bp_rhs.p + j * n3, n3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if (int rc = tangent_solve_device(c, xd, shift, flags, tol, max_iters)) return rc;
+        if (n3) HIP_TRY(hipMemcpyAsync(c->bp_y.p + j * n3, c->nw_y.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->bp_st.p + 3 * j + 2, c->nw_st.p + 2, sizeof(NwCg), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->bp_rr.p + j, c->nw_part.p + (size_t)3 * nw_blocks(c) + 2, sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    return ADMM_HIP_OK;
+}
+// the verdicts of a slab to the host, on the stream; the caller synchronises, then block_verdict_finish
+hipError_t block_verdict_download(admm_hip_ctx *c, int k, bool blocked, std::vector<NwCg> &st3, BlockVerdict *v, NwBlockCtl *ctl) {
+    st3.resize((size_t)3 * k);
+    if (hipError_t e = hipMemcpyAsync(st3.data(), c->bp_st.p, st3.size() * sizeof(NwCg), hipMemcpyDeviceToHost, c->stream)) return e;
+    if (hipError_t e = hipMemcpyAsync(v->rr, c->bp_rr.p, k * sizeof(double), hipMemcpyDeviceToHost, c->stream)) return e;
+    if (blocked)
+        if (hipError_t e = hipMemcpyAsync(ctl, c->bp_ctl.p, sizeof(NwBlockCtl), hipMemcpyDeviceToHost, c->stream)) return e;
+    return hipSuccess;
+}
+void block_verdict_finish(int k, bool blocked, const std::vector<NwCg> &st3, const NwBlockCtl &ctl, BlockVerdict *v) {
+    v->passes = 0; v->iters = 0;
+    for (int j = 0; j < k; ++j) {
+        v->st[j] = st3[(size_t)3 * j + 2];
+        if (!blocked) { v->passes += v->st[j].it; v->iters = std::max(v->iters, v->st[j].it); }
+    }
+    if (blocked) { v->passes = ctl.passes[0]; v->iters = ctl.passes[1]; }
 }
 hipError_t modal_ensure(admm_hip_ctx *c) {
     if (c->md_ready) return hipSuccess;
@@ -4355,6 +4472,47 @@ int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, 
     return ADMM_HIP_OK;
 }
 
+// ---- tangent solves for a stack of right-hand sides (newton.hpp: the block PCG) ----
+
+// admm_hip_tangent_solve for k right-hand sides on one frozen operator: one setup, one diagonal, and the block PCG in slabs of
+// kNwBlkCols columns.  info: [k][4] as admm_hip_tangent_solve; block_info3: block iterations (the longest column; of the longest slab),
+// column passes, blocked 0 / 1
+int admm_hip_tangent_solve_block(admm_hip_ctx *c, const double *x, int32_t k, const double *rhs, double shift, int32_t flags, double tol,
+                                 int32_t max_iters, double *y, double *info, double *block_info3) {
+    if (!c || !rhs || !y || !info || !block_info3) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: NULL argument");
+    if (k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: k < 1 or k > 65535");
+    if (int rc = newton_args_ok("tangent_solve_block", shift, flags)) return rc;
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: tol must be finite and >= 0, max_iters >= 1");
+    const double *xd;
+    if (int rc = eval_begin(c, "tangent_solve_block", x, &xd)) return rc;
+    HIP_TRY(newton_ensure(c));
+    HIP_TRY(block_pcg_ensure(c, std::min<int>(k, kNwBlkCols)));
+    hipStream_t st = c->stream;
+    const size_t n3 = (size_t)c->n3;
+    const bool blocked = c->tc_kind == 0;
+    const int *pin = blocked ? block_solve_setup(c, xd, shift, flags) : nullptr;
+    std::vector<NwCg> st3;
+    BlockVerdict v;
+    NwBlockCtl ctl{};
+    block_info3[0] = 0.0; block_info3[1] = 0.0; block_info3[2] = blocked ? 1.0 : 0.0;
+    for (int j0 = 0; j0 < k; j0 += kNwBlkCols) {
+        const int kk = std::min<int>(kNwBlkCols, k - j0);
+        if (n3) HIP_TRY(hipMemcpyAsync(c->bp_rhs.p, rhs + (size_t)j0 * n3, (size_t)kk * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (int rc = block_solve_slab(c, xd, kk, shift, flags, pin, tol, max_iters, blocked)) return rc;
+        if (n3) HIP_TRY(hipMemcpyAsync(y + (size_t)j0 * n3, c->bp_y.p, (size_t)kk * n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(block_verdict_download(c, kk, blocked, st3, &v, &ctl));
+        HIP_TRY(hipStreamSynchronize(st));
+        block_verdict_finish(kk, blocked, st3, ctl, &v);
+        for (int j = 0; j < kk; ++j) {
+            const NwCg &h = v.st[j];
+            double *i4 = info + (size_t)4 * (j0 + j);
+            i4[0] = h.it; i4[1] = h.conv; i4[2] = h.bb > 0.0 ? std::sqrt(v.rr[j] / h.bb) : 0.0; i4[3] = std::sqrt(h.bb);
+        }
+        block_info3[0] = std::max(block_info3[0], (double)v.iters); block_info3[1] += v.passes;
+    }
+    return ADMM_HIP_OK;
+}
+
 // The preconditioner of admm_hip_tangent_solve, admm_hip_newton_polish and admm_hip_step_adjoint
 int admm_hip_set_tangent_precond(admm_hip_ctx *c, int32_t kind, int32_t aggregates) {
     if (!c) return fail(ADMM_HIP_ERR_ARG, "set_tangent_precond: NULL context");
@@ -4663,6 +4821,89 @@ int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL
     if (params) param_sens_unpermute(c, hp, 1, out_tets, out_tris, out_bends);
     info6[0] = h.it; info6[1] = h.conv; info6[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info6[3] = std::sqrt(h.bb);
     info6[4] = std::sqrt(g2); info6[5] = idt2;
+    return ADMM_HIP_OK;
+}
+
+// admm_hip_step_adjoint for k losses at the same state: |r_free| once, k_adj_rhs / k_adj_out per column, the solves by the block PCG
+// (block_solve_slab), one k_param_sens pass per slab over the stack of lambda.  info: [k][6] as admm_hip_step_adjoint; block_info3 as
+// admm_hip_tangent_solve_block
+int admm_hip_step_adjoint_block(admm_hip_ctx *c, int32_t k, const double *dL_dx, const double *dL_dv, int32_t flags, double tol, int32_t max_iters,
+                                double *out_lambda, double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass, double *out_tets,
+                                double *out_tris, double *out_bends, double *info, double *block_info3) {
+    if (!c || !dL_dx || !info || !block_info3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: NULL argument");
+    if (k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: k < 1 or k > 65535");
+    if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: flags must be a combination of 1 (positive semi-definite projection) and 2 (parameter sensitivities)");
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: tol must be finite and >= 0, max_iters >= 1");
+    if (int rc = mon_refuse(c, "step_adjoint_block")) return rc;      // (the rules of step_adjoint)
+    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has colliders; contact is not part of the problem the adjoint differentiates");
+    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has strain-limited triangles; the forces ignore the limits");
+    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has slide pins");
+    if (int rc = quiesce(c)) return rc;
+    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    HIP_TRY(newton_ensure(c));
+    HIP_TRY(force_ensure(c, false, 0));
+    HIP_TRY(adjoint_ensure(c));
+    const int slab = std::min<int>(k, kNwBlkCols);
+    HIP_TRY(block_pcg_ensure(c, slab));
+    hipStream_t st = c->stream;
+    const int nv = c->nv, nb = nw_blocks(c);
+    const size_t n3 = (size_t)c->n3, ld = std::max<size_t>(1, n3);
+    if (c->adj_bl.n < 2 * slab * ld) HIP_TRY(c->adj_bl.alloc_zeroed(2 * slab * ld, st));
+    if (c->adj_bout.n < 4 * slab * ld) HIP_TRY(c->adj_bout.alloc_zeroed(4 * slab * ld, st));
+    const double idt = 1.0 / c->dt, idt2 = 1.0 / (c->dt * c->dt);
+    const bool params = (flags & 2) != 0, blocked = c->tc_kind == 0;
+    const int sflags = (flags & 1) | 2;
+    double *Lx = c->adj_bl.p, *Lv = dL_dv ? c->adj_bl.p + slab * ld : nullptr;
+    double *sums = c->nw_part.p + (size_t)3 * nb;      // [0] |r_free|^2
+    launch_pin_mask(c);
+    // |r_free| of the state, once (admm_hip_step_adjoint: the polish's own figure)
+    launch_forces(c, c->x.p, false, nullptr);
+    hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->adj_out.p, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+    double g2 = 0.0;
+    HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
+    const int *pin = blocked ? block_solve_setup(c, c->x.p, idt2, sflags) : nullptr;
+    std::vector<NwCg> st3;
+    std::vector<double> hp(params ? c->adj_ps.n : 0);
+    BlockVerdict v;
+    NwBlockCtl ctl{};
+    double *outs[4] = {out_xbar, out_xprev, out_vprev, out_mass};
+    block_info3[0] = 0.0; block_info3[1] = 0.0; block_info3[2] = blocked ? 1.0 : 0.0;
+    for (int j0 = 0; j0 < k; j0 += kNwBlkCols) {
+        const int kk = std::min<int>(kNwBlkCols, k - j0);
+        if (n3) {
+            HIP_TRY(hipMemcpyAsync(Lx, dL_dx + (size_t)j0 * n3, (size_t)kk * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+            if (Lv) HIP_TRY(hipMemcpyAsync(Lv, dL_dv + (size_t)j0 * n3, (size_t)kk * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        for (int j = 0; j < kk; ++j)
+            hipLaunchKernelGGL(k_adj_rhs, dim3(nb), dim3(256), 0, st, nv, Lx + j * n3, Lv ? Lv + j * n3 : nullptr, idt, c->nw_pin.p, c->bp_rhs.p + j * n3);
+        if (int rc = block_solve_slab(c, c->x.p, kk, idt2, sflags, pin, tol, max_iters, blocked)) return rc;
+        for (int j = 0; j < kk; ++j)
+            hipLaunchKernelGGL(k_adj_out, dim3(nb), dim3(256), 0, st, nv, n3, c->bp_y.p + j * n3, c->m.p, c->Mxbar.p, c->x.p, Lv ? Lv + j * n3 : nullptr, idt,
+                               c->nw_pin.p, c->adj_bout.p + 4 * j * n3);
+        if (params) launch_param_sens(c, c->x.p, c->bp_y.p, n3, kk);
+        HIP_TRY(hipGetLastError());
+        if (n3) {
+            if (out_lambda) HIP_TRY(hipMemcpyAsync(out_lambda + (size_t)j0 * n3, c->bp_y.p, (size_t)kk * n3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            for (int q = 0; q < 4; ++q)
+                if (outs[q])      // [kk] rows of n3 doubles, 4 n3 apart on the device
+                    HIP_TRY(hipMemcpy2DAsync(outs[q] + (size_t)j0 * n3, n3 * sizeof(double), c->adj_bout.p + q * n3, 4 * n3 * sizeof(double), n3 * sizeof(double),
+                                             (size_t)kk, hipMemcpyDeviceToHost, st));
+        }
+        if (params) HIP_TRY(param_sens_download(c, hp, kk));
+        HIP_TRY(block_verdict_download(c, kk, blocked, st3, &v, &ctl));
+        HIP_TRY(hipStreamSynchronize(st));
+        block_verdict_finish(kk, blocked, st3, ctl, &v);
+        if (params) param_sens_unpermute(c, hp, kk, out_tets ? out_tets + (size_t)j0 * c->nt_total * 4 : nullptr, out_tris ? out_tris + (size_t)j0 * c->ntri_total : nullptr,
+                                         out_bends ? out_bends + (size_t)j0 * c->nbend_total : nullptr);
+        for (int j = 0; j < kk; ++j) {
+            const NwCg &h = v.st[j];
+            double *i6 = info + (size_t)6 * (j0 + j);
+            i6[0] = h.it; i6[1] = h.conv; i6[2] = h.bb > 0.0 ? std::sqrt(v.rr[j] / h.bb) : 0.0; i6[3] = std::sqrt(h.bb);
+            i6[4] = std::sqrt(g2); i6[5] = idt2;
+        }
+        block_info3[0] = std::max(block_info3[0], (double)v.iters); block_info3[1] += v.passes;
+    }
     return ADMM_HIP_OK;
 }
 

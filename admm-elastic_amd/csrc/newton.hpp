@@ -23,6 +23,10 @@
 // (two slots: the one behind the final one still says "running") -- not at the stop word (kernels.hpp: the rule of kCntAdmmStop).  The stop
 // test reads the RECURSIVE residual; what the solve reports is the true one, rhs - A y formed once more after the last iteration.
 //
+// The BLOCK PCG (admm_hip_tangent_solve_block, admm_hip_step_adjoint_block; described where it stands, below k_nw_true_resid): up to
+// kNwBlkCols of these recurrences on one frozen tangent, independent of each other, sharing the four launches of an iteration; column j
+// has the bits of the single solve.
+//
 // REPRODUCIBLE to the bit: fixed summation orders, ordinary vector stores, no floating-point atomics.
 #pragma once
 #include "tangent.hpp"
@@ -290,7 +294,11 @@ struct FrozenBlockArgs {
     FrozenArgs fa;            // fa.d: [n_vec][s.d]; f.rec, f.r_cf, f.h_cf: direction 0
     int n_vec;
     DirStrides s;
+    const int *cols;          // nullptr: the directions 0 .. n_vec; else cols[0] directions, cols[1 ..] (the block PCG's column list, below)
 };
+// the q-th direction of a block launch and their number
+__device__ __forceinline__ int block_dirs(const int *cols, int n_vec) { return cols ? cols[0] : n_vec; }
+__device__ __forceinline__ int block_dir(const int *cols, int q) { return cols ? cols[1 + q] : q; }
 __global__ __launch_bounds__(256) void k_tangent_frozen_block(FrozenBlockArgs ba) {
     __shared__ double sLm[12 * kChunkLdK];
     const FrozenArgs &fa = ba.fa;
@@ -307,12 +315,14 @@ __global__ __launch_bounds__(256) void k_tangent_frozen_block(FrozenBlockArgs ba
         tet_frame_load(fa.t_fr, (size_t)v.ldt, t, U, N, Hs, ca, cb);
         const int4 id = v.t_idx[t];
         const int vid[4] = {id.x, id.y, id.z, id.w};
+        const int nd = block_dirs(ba.cols, ba.n_vec);
 #pragma unroll 1
-        for (int dir = 0; dir < ba.n_vec; ++dir) {
+        for (int q = 0; q < nd; ++q) {
+            const int dir = block_dir(ba.cols, q);
             double Ds[9], f[12];
             tet_edge_matrix(fa.d + (size_t)dir * ba.s.d, vid, Ds);
             tet_frozen_apply(U, N, Hs, ca, cb, Ds, f);
-            if (dir > 0) __syncthreads();      // the previous direction's reduction has read rows 0..11
+            if (q > 0) __syncthreads();        // the previous direction's reduction has read rows 0..11
             chunk_out_store(co, sL, f, a.rec + (size_t)dir * ba.s.rec);
         }
     } else if (blk < a.nb_r) {
@@ -329,8 +339,10 @@ __global__ __launch_bounds__(256) void k_tangent_frozen_block(FrozenBlockArgs ba
 #pragma unroll
         for (int c = 0; c < 3; ++c) Si[c] = fr[(6 + c) * ld];
         const double itr = fr[9 * ld], w2 = fr[10 * ld];
+        const int nd = block_dirs(ba.cols, ba.n_vec);
 #pragma unroll 1
-        for (int dir = 0; dir < ba.n_vec; ++dir) {
+        for (int q = 0; q < nd; ++q) {
+            const int dir = block_dir(ba.cols, q);
             double dF[6], G[6];
             tri_F(R, id, fa.d + (size_t)dir * ba.s.d, dF);
             tri_tangent_apply(Q, Si, itr, dF, G);
@@ -344,38 +356,61 @@ __global__ __launch_bounds__(256) void k_tangent_frozen_block(FrozenBlockArgs ba
         int vid[4];
         double c[4], ks;
         hinge_load(v, t, c, vid, ks);
+        const int nd = block_dirs(ba.cols, ba.n_vec);
 #pragma unroll 1
-        for (int dir = 0; dir < ba.n_vec; ++dir) {
+        for (int q = 0; q < nd; ++q) {
+            const int dir = block_dir(ba.cols, q);
             double Dx[3];
             hinge_Dx(c, vid, fa.d + (size_t)dir * ba.s.d, Dx);
             hinge_corner_store(c, ks, Dx, a.h_cf + (size_t)dir * ba.s.hcf, v.ldb, t);
         }
     }
 }
-// k_newton_gather<false> on a block: blockIdx.y = direction; out_j = K d_j + shift m o d_j, rows of held vertices zero; no d . Kd partials
+// k_newton_gather<false> on a block: blockIdx.y = direction; out_j = K d_j + shift m o d_j, rows of held vertices zero.  DOT = false: no
+// d . Kd partials.  DOT = true (the block PCG): the partial of direction j at part[j spart + xcd_block()], in the block shape and the
+// block_sum order of k_newton_gather<false> -- nw_reduce then returns the single solve's bits.  With `cols` blockIdx.y indexes that list
+// and a block beyond it returns; block (0, 0) adds the list's length to passes[0] and 1 to passes[1].
 struct NewtonGatherBlockArgs {
-    NewtonGatherArgs n;       // g.t_rec, g.r_cf, g.h_cf, g.f, d: direction 0 (part unused)
+    NewtonGatherArgs n;       // g.t_rec, g.r_cf, g.h_cf, g.f, d: direction 0; part: direction 0 (DOT only)
     DirStrides s;
+    const int *cols;          // as FrozenBlockArgs::cols, or nullptr
+    size_t spart;             // doubles between the partials of two directions
+    int *passes;              // [2]: columns, launches applied (needs cols), or nullptr
 };
+template <bool DOT>
 __global__ __launch_bounds__(256) void k_newton_gather_block(NewtonGatherBlockArgs ba) {
+    __shared__ double lds[4];
     const NewtonGatherArgs &na = ba.n;
     if (na.stop && *na.stop) return;
+    if (ba.cols && (int)blockIdx.y >= ba.cols[0]) return;
+    if (ba.passes && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { ba.passes[0] += ba.cols[0]; ba.passes[1] += 1; }
     const ForceGatherArgs &a = na.g;
     const int lane = threadIdx.x & 63;
     const int s = wave_slice();
-    if (s >= a.n_slices) return;
-    const size_t dir = blockIdx.y;
-    double acc[3] = {0.0, 0.0, 0.0};
-    const int v = gather_vertex(a, s, lane, acc, dir, ba.s);
-    if (v < a.nv) {
-        const bool held = na.pin && na.pin[v] != 0;
-        const double *dv = na.d + dir * ba.s.d;
-        double *out = a.f + dir * ba.s.d;
+    if (!DOT && s >= a.n_slices) return;
+    const size_t dir = (size_t)block_dir(ba.cols, (int)blockIdx.y);
+    double q[1] = {0.0};
+    if (s < a.n_slices) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        const int v = gather_vertex(a, s, lane, acc, dir, ba.s);
+        if (v < a.nv) {
+            const bool held = na.pin && na.pin[v] != 0;
+            const double *dv = na.d + dir * ba.s.d;
+            double *out = a.f + dir * ba.s.d;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const size_t i = 3 * (size_t)v + j;
-            out[i] = held ? 0.0 : fma(na.shift * na.m[i], dv[i], acc[j]);
+            for (int j = 0; j < 3; ++j) {
+                const size_t i = 3 * (size_t)v + j;
+                if (DOT) {
+                    const double di = dv[i], o = held ? 0.0 : fma(na.shift * na.m[i], di, acc[j]);
+                    out[i] = o;
+                    q[0] = fma(di, o, q[0]);
+                } else out[i] = held ? 0.0 : fma(na.shift * na.m[i], dv[i], acc[j]);
+            }
         }
+    }
+    if (DOT) {
+        block_sum<1>(q, lds);
+        if (threadIdx.x == 0) na.part[dir * ba.spart + xcd_block()] = q[0];
     }
 }
 // d_j = 0 on the held vertices, in place; blockIdx.y = direction (k_nw_mask on a block)
@@ -446,7 +481,7 @@ __global__ __launch_bounds__(256) void k_nw_cg_init2(int nb, const double *__res
         s.rz = q[0]; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
         s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(q[0] > 0.0) || !nw_finite(q[0]);
         s.conv = q[1] == 0.0;
-        st[0] = s; st[2] = s;
+        st[0] = s; st[1] = s; st[2] = s;      // (slot 1 too: what an earlier solve left there must not pass k_nw_cg_dir(1)'s test when this one ends here)
         *stop = s.done;
     }
 }
@@ -520,6 +555,175 @@ __global__ __launch_bounds__(256) void k_nw_true_resid(int nv, const double *__r
     }
     block_sum<1>(q, lds);
     if (threadIdx.x == 0) part[blk] = q[0];
+}
+
+// ---- the block PCG (admm_hip_tangent_solve_block, admm_hip_step_adjoint_block): k <= kNwBlkCols INDEPENDENT recurrences on one frozen
+// tangent that share every launch -- not a block-Krylov method.  Column j owns y_j, r_j, p_j, Ap_j [k][sv], its partials part[j][3][nb]
+// and its scalars st[j][3], and runs the rules of k_nw_cg_step / k_nw_cg_dir on them with the arithmetic and the summation orders of
+// the single solve: column j is the single solve of rhs_j, bit for bit.  grid = (blocks_for(nv), k); blockIdx.y selects the column.
+// THE COLUMN LIST: list[it & 1] = {n, columns still running at iteration it}.  k_tangent_frozen_block loops over it, the gather and the
+// vector kernels index it with blockIdx.y (a block beyond it returns), so a finished column costs nothing from the next iteration on.
+// WHO WRITES WHAT, per column as in the single solve; the list of iteration it + 1 and the stop word (set when that list is empty) are
+// written in k_nw_cg_dir_block(it) by the LAST of the running columns' blocks 0 to arrive at an integer ticket (every column's verdict is
+// in memory by then; the list is filled in the order of the old one, so its content does not depend on who arrives last) and read by
+// later launches only.  A launch enqueued behind the end sees the stop word, an empty list, or a column slot of another iteration.
+constexpr int kNwBlkCols = 16;      // == kModalNb (modal.hpp)
+struct NwBlockCtl { int list[2][kNwBlkCols + 1]; int arrive, passes[2]; };      // passes: columns, iterations applied in the iteration loop
+struct NwBlockArgs {
+    int nv, nb, k;            // vertices, their blocks, columns
+    size_t sv;                // doubles between two columns of a block vector
+    const double *rhs, *dinv;
+    const int *pin;
+    double *y, *r, *p, *ap;   // [k][sv] each
+    double *part;             // [k][3][nb]
+    double *rr;               // [k]: |rhs_j - A y_j|^2 over the free rows (k_nw_resid_final_block)
+    NwCg *st;                 // [k][3]
+    NwBlockCtl *ctl;
+    int *stop;
+    double tol2;
+    int max_iters;
+};
+// k_nw_cg_init per column
+__global__ __launch_bounds__(256) void k_nw_cg_init_block(NwBlockArgs a) {
+    __shared__ double lds[8];
+    const size_t col = blockIdx.y;
+    const double *rhs = a.rhs + col * a.sv;
+    double *y = a.y + col * a.sv, *r = a.r + col * a.sv, *p = a.p + col * a.sv, *part = a.part + col * 3 * a.nb;
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[2] = {0.0, 0.0};
+    if (v < a.nv) {
+        const bool held = a.pin && a.pin[v] != 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            const double ri = held ? 0.0 : rhs[i], zi = a.dinv[i] * ri;
+            y[i] = 0.0; r[i] = ri; p[i] = zi;
+            q[0] = fma(ri, zi, q[0]); q[1] = fma(ri, ri, q[1]);
+        }
+    }
+    block_sum<2>(q, lds);
+    if (threadIdx.x == 0) { part[a.nb + blk] = q[0]; part[2 * (size_t)a.nb + blk] = q[1]; }
+}
+// one block: k_nw_cg_init2 per column (all three slots), the list of iteration 0, the counters and the stop word
+__global__ __launch_bounds__(256) void k_nw_cg_init2_block(NwBlockArgs a) {
+    __shared__ double lds[8];
+    int n = 0;
+    for (int col = 0; col < a.k; ++col) {
+        double q[2];
+        nw_reduce<2>(a.part + (size_t)col * 3 * a.nb + a.nb, a.nb, q, lds);
+        if (threadIdx.x == 0) {
+            NwCg s;
+            s.rz = q[0]; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
+            s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(q[0] > 0.0) || !nw_finite(q[0]);
+            s.conv = q[1] == 0.0;
+            NwCg *st = a.st + 3 * col;
+            st[0] = s; st[1] = s; st[2] = s;
+            if (!s.done) a.ctl->list[0][1 + n++] = col;
+        }
+    }
+    if (threadIdx.x == 0) {
+        a.ctl->list[0][0] = n; a.ctl->list[1][0] = 0; a.ctl->arrive = 0; a.ctl->passes[0] = 0; a.ctl->passes[1] = 0;
+        *a.stop = n == 0;
+    }
+}
+// k_nw_cg_step per running column
+__global__ __launch_bounds__(256) void k_nw_cg_step_block(int it, NwBlockArgs a) {
+    __shared__ double lds[8];
+    if (*a.stop) return;
+    const int *ls = a.ctl->list[it & 1];
+    if ((int)blockIdx.y >= ls[0]) return;
+    const size_t col = (size_t)ls[1 + blockIdx.y];
+    const NwCg s = a.st[3 * col + (it & 1)];
+    double *part = a.part + col * 3 * a.nb;
+    double pap[1];
+    nw_reduce<1>(part, a.nb, pap, lds);
+    if (!(pap[0] > 0.0) || !nw_finite(pap[0])) return;
+    const double alpha = s.rz / pap[0];
+    const double *p = a.p + col * a.sv, *ap = a.ap + col * a.sv;
+    double *y = a.y + col * a.sv, *r = a.r + col * a.sv;
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[2] = {0.0, 0.0};
+    if (v < a.nv) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const size_t i = 3 * (size_t)v + j;
+            y[i] = fma(alpha, p[i], y[i]);
+            const double ri = fma(-alpha, ap[i], r[i]);
+            r[i] = ri;
+            q[0] = fma(ri * a.dinv[i], ri, q[0]); q[1] = fma(ri, ri, q[1]);
+        }
+    }
+    block_sum<2>(q, lds);
+    if (threadIdx.x == 0) { part[a.nb + blk] = q[0]; part[2 * (size_t)a.nb + blk] = q[1]; }
+}
+// k_nw_cg_dir per running column; the list of iteration it + 1 and the stop word (above)
+__global__ __launch_bounds__(256) void k_nw_cg_dir_block(int it, NwBlockArgs a) {
+    __shared__ double lds[12];
+    const int *ls = a.ctl->list[it & 1];
+    const int nl = ls[0];
+    if ((int)blockIdx.y >= nl) return;
+    const size_t col = (size_t)ls[1 + blockIdx.y];
+    NwCg *st = a.st + 3 * col;
+    const NwCg s = st[it & 1];
+    if (s.done || s.it != it) return;      // ended, or a launch behind the end (k_nw_cg_dir)
+    double q[3];
+    nw_reduce<3>(a.part + col * 3 * a.nb, a.nb, q, lds);
+    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);
+    NwCg n = s;
+    if (broke) { n.done = 1; n.conv = 0; }
+    else {
+        n.rz = q[1]; n.rr = q[2]; n.it = s.it + 1;
+        n.conv = q[2] <= a.tol2 * s.bb;
+        n.done = n.conv || n.it >= a.max_iters || !nw_finite(q[1]) || !nw_finite(q[2]) || !(q[1] > 0.0);
+    }
+    if (!n.done) {
+        const double beta = q[1] / s.rz;
+        const double *r = a.r + col * a.sv;
+        double *p = a.p + col * a.sv;
+        const int v = xcd_block() * 256 + (int)threadIdx.x;
+        if (v < a.nv) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; p[i] = fma(beta, p[i], a.dinv[i] * r[i]); }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st[(it + 1) & 1] = n; st[2] = n;
+        __threadfence();
+        if (atomicAdd(&a.ctl->arrive, 1) == nl - 1) {      // the last column to arrive: every verdict of this iteration is in memory
+            __threadfence();
+            int *nx = a.ctl->list[(it + 1) & 1];
+            int m = 0;
+            for (int j = 0; j < nl; ++j) {
+                const int cj = ls[1 + j];
+                if (!__hip_atomic_load(&a.st[3 * cj + 2].done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) nx[1 + m++] = cj;
+            }
+            nx[0] = m;
+            a.ctl->arrive = 0;
+            if (m == 0) *a.stop = 1;
+        }
+    }
+}
+// k_nw_true_resid per column (ay_j in a.ap), and one block per column that sums its partials in the order of k_stat_final
+__global__ __launch_bounds__(256) void k_nw_true_resid_block(NwBlockArgs a) {
+    __shared__ double lds[4];
+    const size_t col = blockIdx.y;
+    const double *rhs = a.rhs + col * a.sv, *ay = a.ap + col * a.sv;
+    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
+    double q[1] = {0.0};
+    if (v < a.nv && !(a.pin && a.pin[v] != 0)) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; const double r = rhs[i] - ay[i]; q[0] = fma(r, r, q[0]); }
+    }
+    block_sum<1>(q, lds);
+    if (threadIdx.x == 0) a.part[col * 3 * a.nb + blk] = q[0];
+}
+__global__ __launch_bounds__(256) void k_nw_resid_final_block(NwBlockArgs a) {
+    __shared__ double lds[4];
+    const double *part = a.part + (size_t)blockIdx.x * 3 * a.nb;
+    double q[1] = {0.0};
+    for (int b = (int)threadIdx.x; b < a.nb; b += 256) q[0] += part[b];
+    block_sum<1>(q, lds);
+    if (threadIdx.x == 0) a.rr[blockIdx.x] = q[0];
 }
 
 // ---- the vector kernels of the Newton polish ----

@@ -135,6 +135,12 @@ public:
     struct SolveInfo { int iterations; bool converged; double residual, rhs_norm; };
     VecX tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info = nullptr, double shift = -1.0, bool psd = true, bool hold_pins = true,
                        double tol = 1e-10, int max_iters = 1000);
+    // tangent_solve for a stack of right-hand sides on the same frozen operator (admm_hip_tangent_solve_block): one setup, k independent
+    // CG recurrences that share every launch; y[j] and info->columns[j] have the bits of tangent_solve(rhs[j]).  block_iterations: of
+    // the longest column; column_passes: the columns applied over all iterations; blocked: false with the two-level preconditioner
+    struct BlockSolveInfo { std::vector<SolveInfo> columns; int block_iterations, column_passes; bool blocked; };
+    std::vector<VecX> tangent_solve_block(const std::vector<VecX> &rhs, const VecX &x, BlockSolveInfo *info = nullptr, double shift = -1.0, bool psd = true,
+                                          bool hold_pins = true, double tol = 1e-10, int max_iters = 1000);
     // The preconditioner of the CG behind tangent_solve, newton_polish and step_adjoint (admm_hip_set_tangent_precond): Jacobi (the
     // default), or two-level with the affine displacements of `aggregates` compact aggregates (0: n_verts / 256 in 1 .. 64) as coarse space
     enum class TangentPrecond { Jacobi = 0, TwoLevel = 1 };
@@ -165,6 +171,11 @@ public:
     };
     StepAdjoint step_adjoint(const VecX &dL_dx, const VecX &dL_dv = VecX(), bool psd = false, double tol = 1e-10, int max_iters = 2000,
                              bool params = true);
+    // step_adjoint for k losses at the same state (admm_hip_step_adjoint_block): dL_dv empty or one vector per loss; entry j has the
+    // bits of step_adjoint(dL_dx[j], dL_dv[j]); the solves are tangent_solve_block's
+    struct StepAdjointBlock { std::vector<StepAdjoint> columns; int block_iterations, column_passes; bool blocked; };
+    StepAdjointBlock step_adjoint_block(const std::vector<VecX> &dL_dx, const std::vector<VecX> &dL_dv = std::vector<VecX>(), bool psd = false,
+                                        double tol = 1e-10, int max_iters = 2000, bool params = true);
     // d(a . forces)/dX per rest vertex at x, X the rest positions of the tets, masses and material constants held fixed
     // (admm_hip_rest_sensitivity); three values per node.  Refused for scenes with triangles or hinges
     VecX rest_sensitivity(const VecX &a, const VecX &x);

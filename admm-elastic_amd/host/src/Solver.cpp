@@ -716,6 +716,31 @@ VecX Solver::tangent_solve(const VecX &rhs, const VecX &x, SolveInfo *info, doub
     return y;
 }
 
+std::vector<VecX> Solver::tangent_solve_block(const std::vector<VecX> &rhs, const VecX &x, BlockSolveInfo *info, double shift, bool psd, bool hold_pins,
+                                              double tol, int max_iters) {
+    if (!initialized) throw std::runtime_error("Solver::tangent_solve_block: initialize() first");
+    const size_t k = rhs.size(), n = (size_t)m_x.rows();
+    if (k < 1 || (size_t)x.rows() != n) throw std::runtime_error("Solver::tangent_solve_block: at least one right-hand side; x must hold three values per node");
+    std::vector<double> R(k * n), Y(k * n, 0.0), i4(4 * k, 0.0);
+    for (size_t j = 0; j < k; ++j) {
+        if ((size_t)rhs[j].rows() != n) throw std::runtime_error("Solver::tangent_solve_block: every right-hand side must hold three values per node");
+        std::copy(rhs[j].data(), rhs[j].data() + n, R.begin() + j * n);
+    }
+    double b3[3] = {0.0, 0.0, 0.0};
+    const int32_t flags = (psd ? ADMM_HIP_TANGENT_PSD : 0) | (hold_pins ? ADMM_HIP_TANGENT_HOLD_PINS : 0);
+    if (shift < 0.0) shift = 1.0 / (m_settings.timestep_s * m_settings.timestep_s);
+    check(admm_hip_tangent_solve_block((admm_hip_ctx *)m_ctx, x.data(), (int32_t)k, R.data(), shift, flags, tol, (int32_t)max_iters, Y.data(), i4.data(), b3),
+          "Solver::tangent_solve_block");
+    std::vector<VecX> out(k, VecX(m_x.rows()));
+    for (size_t j = 0; j < k; ++j) std::copy(Y.begin() + j * n, Y.begin() + (j + 1) * n, out[j].data());
+    if (info) {
+        info->columns.resize(k);
+        for (size_t j = 0; j < k; ++j) info->columns[j] = SolveInfo{(int)i4[4 * j], i4[4 * j + 1] != 0.0, i4[4 * j + 2], i4[4 * j + 3]};
+        info->block_iterations = (int)b3[0]; info->column_passes = (int)b3[1]; info->blocked = b3[2] != 0.0;
+    }
+    return out;
+}
+
 void Solver::set_tangent_precond(TangentPrecond kind, int aggregates) {
     if (!initialized) throw std::runtime_error("Solver::set_tangent_precond: initialize() first");
     check(admm_hip_set_tangent_precond((admm_hip_ctx *)m_ctx, (int32_t)kind, (int32_t)aggregates), "Solver::set_tangent_precond");
@@ -775,6 +800,43 @@ Solver::StepAdjoint Solver::step_adjoint(const VecX &dL_dx, const VecX &dL_dv, b
                                 params ? r.params.tris.data() : nullptr, params ? r.params.hinges.data() : nullptr, i6), "Solver::step_adjoint");
     r.iterations = (int)i6[0]; r.converged = i6[1] != 0.0; r.residual = i6[2]; r.rhs_norm = i6[3]; r.stationarity = i6[4]; r.shift = i6[5];
     return r;
+}
+
+Solver::StepAdjointBlock Solver::step_adjoint_block(const std::vector<VecX> &dL_dx, const std::vector<VecX> &dL_dv, bool psd, double tol, int max_iters,
+                                                    bool params) {
+    if (!initialized) throw std::runtime_error("Solver::step_adjoint_block: initialize() first");
+    const size_t k = dL_dx.size(), n = (size_t)m_x.rows();
+    if (k < 1 || (!dL_dv.empty() && dL_dv.size() != k)) throw std::runtime_error("Solver::step_adjoint_block: at least one loss; dL_dv empty or one vector per loss");
+    std::vector<double> Gx(k * n), Gv(dL_dv.empty() ? 0 : k * n), V(5 * k * n, 0.0), i6(6 * k, 0.0);
+    for (size_t j = 0; j < k; ++j) {
+        if ((size_t)dL_dx[j].rows() != n || (!dL_dv.empty() && (size_t)dL_dv[j].rows() != n))
+            throw std::runtime_error("Solver::step_adjoint_block: dL_dx and dL_dv must hold three values per node");
+        std::copy(dL_dx[j].data(), dL_dx[j].data() + n, Gx.begin() + j * n);
+        if (!dL_dv.empty()) std::copy(dL_dv[j].data(), dL_dv[j].data() + n, Gv.begin() + j * n);
+    }
+    const size_t nt = (size_t)4 * m_n_tets, nr = (size_t)m_n_tris, nh = (size_t)m_n_bends;
+    std::vector<double> T(params ? k * nt : 0, 0.0), R(params ? k * nr : 0, 0.0), H(params ? k * nh : 0, 0.0);
+    double b3[3] = {0.0, 0.0, 0.0};
+    const int32_t flags = (psd ? ADMM_HIP_ADJOINT_PSD : 0) | (params ? ADMM_HIP_ADJOINT_PARAMS : 0);
+    double *v = V.data();
+    check(admm_hip_step_adjoint_block((admm_hip_ctx *)m_ctx, (int32_t)k, Gx.data(), dL_dv.empty() ? nullptr : Gv.data(), flags, tol, (int32_t)max_iters, v,
+                                      v + k * n, v + 2 * k * n, v + 3 * k * n, v + 4 * k * n, params ? T.data() : nullptr, params ? R.data() : nullptr,
+                                      params ? H.data() : nullptr, i6.data(), b3), "Solver::step_adjoint_block");
+    StepAdjointBlock out;
+    out.columns.resize(k);
+    for (size_t j = 0; j < k; ++j) {
+        StepAdjoint &r = out.columns[j];
+        VecX *dst[5] = {&r.lam, &r.xbar, &r.x_prev, &r.v_prev, &r.masses};
+        for (int q = 0; q < 5; ++q) { *dst[q] = VecX(m_x.rows()); std::copy(v + (q * k + j) * n, v + (q * k + j + 1) * n, dst[q]->data()); }
+        if (params) {
+            r.params.tets.assign(T.begin() + j * nt, T.begin() + (j + 1) * nt); r.params.tris.assign(R.begin() + j * nr, R.begin() + (j + 1) * nr);
+            r.params.hinges.assign(H.begin() + j * nh, H.begin() + (j + 1) * nh);
+        }
+        const double *i = &i6[6 * j];
+        r.iterations = (int)i[0]; r.converged = i[1] != 0.0; r.residual = i[2]; r.rhs_norm = i[3]; r.stationarity = i[4]; r.shift = i[5];
+    }
+    out.block_iterations = (int)b3[0]; out.column_passes = (int)b3[1]; out.blocked = b3[2] != 0.0;
+    return out;
 }
 
 VecX Solver::rest_sensitivity(const VecX &a, const VecX &x) {

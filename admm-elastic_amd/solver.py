@@ -717,6 +717,33 @@ class Solver:
                                            int(max_iters), dptr(y), dptr(info)))
         return y.reshape(-1, 3), dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]))
 
+    @staticmethod
+    def _block_info(cols, binfo):
+        return dict(columns=cols, block_iterations=int(binfo[0]), column_passes=int(binfo[1]), blocked=bool(binfo[2]))
+
+    def tangent_solve_block(self, rhs, x=None, shift=None, psd=True, hold_pins=True, tol=1e-10, max_iters=1000):
+        """admm_hip_tangent_solve_block: tangent_solve for a stack rhs [k, n_verts, 3] on the same frozen operator -- one setup, one
+        diagonal, and k independent CG recurrences that share every launch (csrc/newton.hpp: the block PCG; not a block-Krylov method).
+        Column j of the result is tangent_solve(rhs[j]) bit for bit, its info included; a column that has ended costs nothing from the
+        next iteration on.  Arguments as tangent_solve.  Returns (Y [k, n_verts, 3], info) with info = dict(columns = [tangent_solve's
+        info dict per column], block_iterations = the iterations of the longest column, column_passes = the columns applied over all
+        iterations, counted on the device, blocked).  More than 16 columns run in slabs of 16.  With set_tangent_precond("two_level")
+        the columns are solved one after the other as tangent_solve solves them and blocked is False."""
+        self._need_ctx()
+        xc = self._state_arg(x, "tangent_solve_block")
+        rc = f64(rhs).copy()
+        nv = self.m_x.size // 3
+        if rc.ndim != 3 or rc.shape[0] < 1 or rc.shape[1:] != (nv, 3):
+            raise ValueError("tangent_solve_block: rhs must be [k, n_verts, 3] with k >= 1")
+        k = rc.shape[0]
+        if shift is None:
+            shift = 1.0 / (self._settings.timestep_s ** 2)
+        y = np.zeros(rc.shape); info = np.zeros((k, 4)); binfo = np.zeros(3)
+        check(lib().admm_hip_tangent_solve_block(self._ctx, dptr(xc), k, dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0),
+                                                 float(tol), int(max_iters), dptr(y), dptr(info), dptr(binfo)))
+        cols = [dict(iterations=int(i[0]), converged=bool(i[1]), residual=float(i[2]), rhs_norm=float(i[3])) for i in info]
+        return y, self._block_info(cols, binfo)
+
     def set_tangent_precond(self, kind="jacobi", aggregates=None):
         """admm_hip_set_tangent_precond: the preconditioner of the CG behind tangent_solve, newton_polish and step_adjoint, from the next
         solve on.  "jacobi" (the default) or "two_level": D^-1 + P (P^T A P)^-1 P^T with the affine displacements of `aggregates` compact
@@ -898,6 +925,43 @@ class Solver:
             h = np.zeros(n3)
             check(lib().admm_hip_adjoint_held(self._ctx, dptr(vec[0]), dptr(gx), dptr(gv), dptr(h)))
             out["held"] = h.reshape(-1, 3)
+        return out
+
+    def step_adjoint_block(self, dL_dx, dL_dv=None, psd=False, tol=1e-10, max_iters=2000, params=True, rest=False, held=False):
+        """admm_hip_step_adjoint_block: step_adjoint for k losses at the same state, dL_dx and dL_dv (None: 0) [k, n_verts, 3].  |r_free|
+        of the state is formed once, the k solves are tangent_solve_block's, the parameter sensitivities come from one pass over the
+        stack of lam.  Returns step_adjoint's dict with a leading axis k on every array (lam, xbar, x_prev, v_prev, masses
+        [k, n_verts, 3]; tets [k, n_tets, 4], tris [k, n_tris], hinges [k, n_bends], or None without params) and info = dict(columns =
+        [step_adjoint's info dict per loss], block_iterations, column_passes, blocked) as tangent_solve_block reports them.  Entry j
+        equals step_adjoint(dL_dx[j], dL_dv[j]) bit for bit.  rest=True adds rest = rest_sensitivity of the lam stack, held=True adds
+        held [k, n_verts, 3] through admm_hip_adjoint_held per loss.  Refused as step_adjoint."""
+        self._need_ctx()
+        nv = self.m_x.size // 3
+        gx = f64(dL_dx).copy()
+        gv = None if dL_dv is None else f64(dL_dv).copy()
+        if gx.ndim != 3 or gx.shape[0] < 1 or gx.shape[1:] != (nv, 3) or (gv is not None and gv.shape != gx.shape):
+            raise ValueError("step_adjoint_block: dL_dx and dL_dv must be [k, n_verts, 3] with k >= 1")
+        k = gx.shape[0]
+        f = getattr(self, "_flat", None) or self.flatten()
+        vec = [np.zeros(gx.shape) for _ in range(5)]
+        tets = np.zeros((k, f["tet_idx"].shape[0], 4)) if params else None
+        tris = np.zeros((k, f["tri_idx"].shape[0])) if params else None
+        hinges = np.zeros((k, f["bend_idx"].shape[0])) if params else None
+        info = np.zeros((k, 6)); binfo = np.zeros(3)
+        check(lib().admm_hip_step_adjoint_block(self._ctx, k, dptr(gx), dptr(gv), (1 if psd else 0) | (2 if params else 0), float(tol),
+                                                int(max_iters), dptr(vec[0]), dptr(vec[1]), dptr(vec[2]), dptr(vec[3]), dptr(vec[4]), dptr(tets),
+                                                dptr(tris), dptr(hinges), dptr(info), dptr(binfo)))
+        cols = [dict(iterations=int(i[0]), converged=bool(i[1]), residual=float(i[2]), rhs_norm=float(i[3]), stationarity=float(i[4]),
+                     shift=float(i[5])) for i in info]
+        out = dict(lam=vec[0], xbar=vec[1], x_prev=vec[2], v_prev=vec[3], masses=vec[4], tets=tets, tris=tris, hinges=hinges,
+                   info=self._block_info(cols, binfo))
+        if rest:
+            out["rest"] = self.rest_sensitivity(vec[0])
+        if held:
+            h = np.zeros(gx.shape)
+            for j in range(k):
+                check(lib().admm_hip_adjoint_held(self._ctx, dptr(vec[0][j]), dptr(gx[j]), None if gv is None else dptr(gv[j]), dptr(h[j])))
+            out["held"] = h
         return out
 
     def residuals(self, x, z, z_prev):

@@ -366,6 +366,20 @@ int admm_hip_modes(admm_hip_ctx *ctx, const double *x, int32_t k, int32_t guard,
 int admm_hip_tangent_solve(admm_hip_ctx *ctx, const double *x, const double *rhs, double shift, int32_t flags, double tol, int32_t max_iters,
                            double *y, double *info4);
 
+/* admm_hip_tangent_solve for a STACK of k >= 1 right-hand sides rhs [k][3 n_verts] on the same frozen operator (host; y [k][3 n_verts]):
+ * one setup and one diagonal per call, then k INDEPENDENT CG recurrences that share every launch (csrc/newton.hpp: the block PCG; not a
+ * block-Krylov method).  Each column keeps its own alpha, beta, stop decision and breakdown rule: column j is the single solve of rhs_j,
+ * bit for bit -- y, and info [k][4], laid out per column as info4 above.  A column that has ended drops out of the launches from the
+ * next iteration on (a column list kept on the device); one stop word ends the solve with its last column; chunks of 8 iterations, one
+ * pinned word per chunk, one synchronisation per slab: no host decision inside the solve.  More than 16 columns run in slabs of 16.
+ * block_info3 = {block iterations: those of the longest column (of the longest slab), column_passes: the columns applied over all
+ * iterations, counted on the device (sum_j iterations_j, + 1 for a column that ended in a breakdown), blocked (1)}.
+ * With the two-level preconditioner selected (admm_hip_set_tangent_precond) the columns are solved one after the other as
+ * admm_hip_tangent_solve solves them -- the two-level preconditioner has no block form -- and blocked = 0 (block iterations: the longest
+ * column's, column_passes: their sum).  Refused as admm_hip_tangent_solve, with the same codes, and for k < 1. */
+int admm_hip_tangent_solve_block(admm_hip_ctx *ctx, const double *x, int32_t k, const double *rhs, double shift, int32_t flags, double tol,
+                                 int32_t max_iters, double *y, double *info, double *block_info3);
+
 /* The preconditioner of the CG behind admm_hip_tangent_solve, admm_hip_newton_polish and admm_hip_step_adjoint, in effect from the next
  * solve.  kind 0 (the default): Jacobi, D^-1 with D the diagonal of A = K(x) + shift M.  kind 1: two-level, M^-1 = D^-1 + P (P^T A P)^-1 P^T
  * with P the affine displacements {1, (x - mean) / h} (x) {e_x, e_y, e_z} of `aggregates` compact aggregates of vertices (12 columns each;
@@ -451,6 +465,15 @@ int admm_hip_param_sensitivity(admm_hip_ctx *ctx, const double *x, int32_t k, co
 int admm_hip_step_adjoint(admm_hip_ctx *ctx, const double *dL_dx, const double *dL_dv, int32_t flags, double tol, int32_t max_iters,
                           double *out_lambda, double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass, double *out_tets,
                           double *out_tris, double *out_bends, double *info6);
+/* admm_hip_step_adjoint for k >= 1 losses at the same state: dL_dx, dL_dv (NULL: 0) and the five vector outputs are [k][3 n_verts],
+ * out_tets [k][n_tets][4], out_tris [k][n_tris], out_bends [k][n_bends], info [k][6] laid out per column as info6 above.  |r_free| of
+ * the state is formed once; the right-hand sides and the outputs are formed per column with the single call's arithmetic; the k solves
+ * are admm_hip_tangent_solve_block's (block_info3 as there; the same fallback with the two-level preconditioner); the parameter
+ * sensitivities come from one pass over the stack of lambda per slab of 16.  Column j has the bits of admm_hip_step_adjoint on loss j.
+ * Refused as admm_hip_step_adjoint, and for k < 1. */
+int admm_hip_step_adjoint_block(admm_hip_ctx *ctx, int32_t k, const double *dL_dx, const double *dL_dv, int32_t flags, double tol,
+                                int32_t max_iters, double *out_lambda, double *out_xbar, double *out_xprev, double *out_vprev, double *out_mass,
+                                double *out_tets, double *out_tris, double *out_bends, double *info, double *block_info3);
 
 /* The derivative of the internal forces in the REST positions X of the tets (the verts behind add_tets), contracted with k vectors
  * a [k][3 n_verts] (host): out [k][3 n_verts] = d(a_j . f)/dX per rest vertex at x (host positions, or NULL for the device-resident
