@@ -872,51 +872,33 @@ void launch_pin_mask(admm_hip_ctx *c) {
     hipLaunchKernelGGL(k_nw_pin_mask, dim3(nw_blocks(c)), dim3(256), 0, c->stream, c->nv, (!gs && c->npin_terms > 0) ? c->vert_pin.p : nullptr,
                        c->pin_active.p, gs ? c->gs_pin_flag.p : nullptr, c->nw_pin.p);
 }
-// Jacobi-PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device; leaves y in nw_y and the verdict in nw_st[2].
-// Iterations are enqueued in chunks, one chunk ahead of the device; the host reads the stop word of the chunk before (pinned, behind an
-// event) and stops enqueueing.  The caller synchronises.
-int tangent_solve_two_level(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters);
-int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
-    if (c->tc_kind == 1) return tangent_solve_two_level(c, xd, shift, flags, tol, max_iters);      // (tangent_precond.hpp; below)
-    c->tc_last_nc = 0; c->tc_last_passes = 0;
-    hipStream_t st = c->stream;
-    const int nv = c->nv, nb = nw_blocks(c);
-    const int *pin = nullptr;
-    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
-    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
-    launch_tangent_setup(c, xd, flags & 1);
-    launch_frozen_diag(c, shift, pin);
-    hipLaunchKernelGGL(k_nw_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_p.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_nw_cg_init2, dim3(1), dim3(256), 0, st, nb, c->nw_part.p, c->nw_st.p, c->nw_stop.p);
+// THE CHUNK PROTOCOL of every iterative solve on the frozen tangent (tangent_solve_device, tangent_solve_block_device, modes_device):
+// iterations are enqueued in chunks of 8, one chunk ahead of the device; behind each chunk the stop word goes to one of two pinned words,
+// followed by an event.  The host waits for the chunk BEFORE the one just enqueued and stops enqueueing when that chunk left the stop word
+// set; the launches of a chunk enqueued behind the stop are no-ops.  enqueue_iteration(it) launches iteration it.
+template <class F>
+int run_chunked(admm_hip_ctx *c, int max_iters, F enqueue_iteration) {
     constexpr int chunk = 8;
+    hipStream_t st = c->stream;
     int launched = 0, chunks = 0;
     while (launched < max_iters) {
         const int n = std::min(chunk, max_iters - launched);
-        for (int it = launched; it < launched + n; ++it) {
-            launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
-            hipLaunchKernelGGL(k_nw_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
-                               c->nw_y.p, c->nw_r.p, c->nw_part.p);
-            hipLaunchKernelGGL(k_nw_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
-                               c->nw_r.p, c->nw_p.p, c->nw_part.p);
-        }
+        for (int it = launched; it < launched + n; ++it) enqueue_iteration(it);
         launched += n;
         HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
-        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
+        if (chunks >= 1) {
             HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
             if (c->nw_hstop[(chunks - 1) & 1]) break;
         }
         ++chunks;
     }
-    // the TRUE residual rhs - (K + shift M) y of the iterate the solve returns, over the free rows: what info4 reports.  The recursive residual
-    // the stop test reads drifts from it by about eps cond(A) |rhs| -- 7e-4 of a residual of 1e-12 |rhs|.  (The launches of a chunk enqueued
-    // behind the stop are no-ops; this one carries no stop word.)
-    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);
-    hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
-    HIP_TRY(hipGetLastError());
     return ADMM_HIP_OK;
 }
+// PCG for (K(x) [psd] + shift M) y = nw_rhs on the free vertices, x on the device, with the preconditioner selected (Jacobi, or the
+// two-level one of tangent_precond.hpp); leaves y in nw_y and the verdict in nw_st[2].  The caller synchronises.  (Defined behind the
+// two-level launches it needs.)
+int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters);
 // ---- the frozen pass on a block of directions (newton.hpp), the block eigensolver (modal.hpp) ----
 DirStrides block_strides(const admm_hip_ctx *c) {      // (the sizes of ElemScratch::ensure)
     return DirStrides{(size_t)c->n3, (size_t)4 * (c->n_rec + 1), (size_t)12 * c->ldr, (size_t)12 * c->ldb};
@@ -969,9 +951,8 @@ NwBlockArgs block_pcg_args(admm_hip_ctx *c, int k, const int *pin, double tol, i
     return a;
 }
 // The block Jacobi-PCG on the k <= kNwBlkCols columns of bp_rhs (newton.hpp): the frames and nw_dinv are in place (the caller ran the
-// setup of tangent_solve_device once for all slabs).  The host loop of tangent_solve_device: chunks of 8 iterations of four launches, one
-// chunk ahead, one pinned stop word per chunk.  Leaves y in bp_y, the verdicts in bp_st[j][2], the true residuals in bp_rr, the column
-// passes in bp_ctl; the caller synchronises.
+// head of tangent_solve_device once for all slabs).  Four launches per iteration under run_chunked.  Leaves y in bp_y, the verdicts in
+// bp_st[j][2], the true residuals in bp_rr, the column passes in bp_ctl; the caller synchronises.
 int tangent_solve_block_device(admm_hip_ctx *c, int k, double shift, const int *pin, double tol, int max_iters) {
     hipStream_t st = c->stream;
     const int nb = nw_blocks(c);
@@ -979,24 +960,11 @@ int tangent_solve_block_device(admm_hip_ctx *c, int k, double shift, const int *
     HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
     hipLaunchKernelGGL(k_nw_cg_init_block, dim3(nb, k), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_nw_cg_init2_block, dim3(1), dim3(256), 0, st, a);
-    constexpr int chunk = 8;
-    int launched = 0, chunks = 0;
-    while (launched < max_iters) {
-        const int n = std::min(chunk, max_iters - launched);
-        for (int it = launched; it < launched + n; ++it) {
+    if (int rc = run_chunked(c, max_iters, [&](int it) {
             launch_frozen_block(c, a.p, a.ap, k, shift, pin, c->nw_stop.p, a.ctl->list[it & 1], a.part, a.ctl->passes);
             hipLaunchKernelGGL(k_nw_cg_step_block, dim3(nb, k), dim3(256), 0, st, it, a);
             hipLaunchKernelGGL(k_nw_cg_dir_block, dim3(nb, k), dim3(256), 0, st, it, a);
-        }
-        launched += n;
-        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
-        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
-            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
-            if (c->nw_hstop[(chunks - 1) & 1]) break;
-        }
-        ++chunks;
-    }
+        })) return rc;
     launch_frozen_block(c, a.y, a.ap, k, shift, pin, nullptr);      // the TRUE residuals of the returned iterates (tangent_solve_device), every column
     hipLaunchKernelGGL(k_nw_true_resid_block, dim3(nb, k), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_nw_resid_final_block, dim3(k), dim3(256), 0, st, a);
@@ -1004,16 +972,7 @@ int tangent_solve_block_device(admm_hip_ctx *c, int k, double shift, const int *
     return ADMM_HIP_OK;
 }
 struct BlockVerdict { NwCg st[kNwBlkCols]; double rr[kNwBlkCols]; int passes = 0, iters = 0; };
-// the setup all slabs of a blocked call share (that of tangent_solve_device); -> the pin mask in effect
-const int *block_solve_setup(admm_hip_ctx *c, const double *xd, double shift, int flags) {
-    c->tc_last_nc = 0; c->tc_last_passes = 0;
-    const int *pin = nullptr;
-    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
-    launch_tangent_setup(c, xd, flags & 1);
-    launch_frozen_diag(c, shift, pin);
-    return pin;
-}
-// One slab: the k <= kNwBlkCols columns of bp_rhs -> bp_y, bp_st[j][2], bp_rr.  blocked: the block PCG behind block_solve_setup; else
+// One slab: the k <= kNwBlkCols columns of bp_rhs -> bp_y, bp_st[j][2], bp_rr.  blocked: the block PCG behind tangent_solve_head; else
 // column after column through tangent_solve_device (the two-level preconditioner has no block form): the launches and the bits of
 // single calls.  Enqueues only.
 int block_solve_slab(admm_hip_ctx *c, const double *xd, int k, double shift, int flags, const int *pin, double tol, int max_iters, bool blocked) {
@@ -1084,9 +1043,8 @@ void launch_modal_rr0(admm_hip_ctx *c, const ModalArgs &a, int init) {
     hipLaunchKernelGGL(k_modal_rr, dim3(1), dim3(256), 0, st, a, 0, 0, init);
     hipLaunchKernelGGL(k_modal_update, dim3(std::max(1, blocks_for(a.n3))), dim3(256), 0, st, a, 0, 0);
 }
-// LOBPCG on the device; X (md_S) holds the start block on entry.  The host loop of tangent_solve_device: iterations in chunks of 8, one
-// chunk ahead of the device, one pinned word read per chunk.  Leaves X, Theta, the true residual partials (md_rpart) and the state st[2];
-// the caller synchronises.
+// LOBPCG on the device; X (md_S) holds the start block on entry.  The iterations run under run_chunked.  Leaves X, Theta, the true
+// residual partials (md_rpart) and the state st[2]; the caller synchronises.
 int modes_device(admm_hip_ctx *c, const double *xd, int k, int nb, double shift, int flags, double tol, int max_iters, const int *pin) {
     hipStream_t st = c->stream;
     const ModalArgs a = modal_args(c, k, nb, tol, max_iters);
@@ -1098,26 +1056,13 @@ int modes_device(admm_hip_ctx *c, const double *xd, int k, int nb, double shift,
     launch_frozen_block(c, a.S, a.AS, nb, shift, pin, nullptr);
     launch_modal_rr0(c, a, 1);
     const int nrow = std::max(1, blocks_for(a.n3));
-    constexpr int chunk = 8;
-    int launched = 0, chunks = 0;
-    while (launched < max_iters) {
-        const int n = std::min(chunk, max_iters - launched);
-        for (int it = launched; it < launched + n; ++it) {
+    if (int rc = run_chunked(c, max_iters, [&](int it) {
             hipLaunchKernelGGL(k_modal_resid, dim3(a.nbk), dim3(256), 0, st, a, 1);
             launch_frozen_block(c, a.S + (size_t)nb * n3, a.AS + (size_t)nb * n3, nb, shift, pin, c->nw_stop.p);
             hipLaunchKernelGGL(k_modal_gram, dim3(a.nbg), dim3(256), 0, st, a, 1);
             hipLaunchKernelGGL(k_modal_rr, dim3(1), dim3(256), 0, st, a, it, 1, 0);
             hipLaunchKernelGGL(k_modal_update, dim3(nrow), dim3(256), 0, st, a, it, 1);
-        }
-        launched += n;
-        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
-        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
-            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
-            if (c->nw_hstop[(chunks - 1) & 1]) break;
-        }
-        ++chunks;
-    }
+        })) return rc;
     // the returned X once more through the Rayleigh-Ritz (M-orthonormal to rounding) and the block pass: the TRUE residuals
     launch_modal_rr0(c, a, 0);
     launch_frozen_block(c, a.S, a.AS, nb, shift, pin, nullptr);
@@ -1215,42 +1160,49 @@ void launch_tc_start(admm_hip_ctx *c, const int *pin) {
     hipLaunchKernelGGL(k_tc_cg_init2, dim3(nb), dim3(256), 0, st, nv, nb, c->tc_ncb, c->nw_part.p, c->tc_cpart.p, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_r.p,
                        c->tc_phi.p, c->tc_agg_of.p, c->tc_yc.p, c->nw_p.p);
 }
-// tangent_solve_device with the two-level preconditioner: the same chunks, the same stop protocol, the same true-residual tail; six
-// launches per iteration
-int tangent_solve_two_level(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
-    if (int rc = tc_ensure(c)) return rc;
+// The head every solve on the frozen tangent shares: the pin mask in effect (flags bit 1) -> *pin, the stop word cleared, the frames of the
+// tangent at xd (flags bit 0: projected), nw_dinv and, two_level, A_c^-1
+int tangent_solve_head(admm_hip_ctx *c, const double *xd, double shift, int flags, bool two_level, const int **pin) {
+    if (two_level) { if (int rc = tc_ensure(c)) return rc; }
+    else { c->tc_last_nc = 0; c->tc_last_passes = 0; }
+    *pin = nullptr;
+    if (flags & 2) { launch_pin_mask(c); *pin = c->nw_pin.p; }
+    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), c->stream));
+    launch_tangent_setup(c, xd, flags & 1);
+    launch_frozen_diag(c, shift, *pin);
+    if (two_level) launch_tc_setup(c, xd, shift, *pin);
+    return ADMM_HIP_OK;
+}
+// (declared above)  Four launches per iteration with Jacobi, six with the two-level preconditioner: the frozen pass on p (two launches) and
+// k_nw_cg_step are common, the direction kernel differs.
+int tangent_solve_device(admm_hip_ctx *c, const double *xd, double shift, int flags, double tol, int max_iters) {
     hipStream_t st = c->stream;
     const int nv = c->nv, nb = nw_blocks(c);
-    const int *pin = nullptr;
-    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
-    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
-    launch_tangent_setup(c, xd, flags & 1);
-    launch_frozen_diag(c, shift, pin);
-    launch_tc_setup(c, xd, shift, pin);
-    launch_tc_start(c, pin);
-    constexpr int chunk = 8;
-    int launched = 0, chunks = 0;
-    while (launched < max_iters) {
-        const int n = std::min(chunk, max_iters - launched);
-        for (int it = launched; it < launched + n; ++it) {
+    const bool two_level = c->tc_kind == 1;
+    const int *pin;
+    if (int rc = tangent_solve_head(c, xd, shift, flags, two_level, &pin)) return rc;
+    if (two_level) launch_tc_start(c, pin);
+    else {
+        hipLaunchKernelGGL(k_nw_cg_init, dim3(nb), dim3(256), 0, st, nv, nb, c->nw_rhs.p, pin, c->nw_dinv.p, c->nw_y.p, c->nw_r.p, c->nw_p.p, c->nw_part.p);
+        hipLaunchKernelGGL(k_nw_cg_init2, dim3(1), dim3(256), 0, st, nb, c->nw_part.p, c->nw_st.p, c->nw_stop.p);
+    }
+    if (int rc = run_chunked(c, max_iters, [&](int it) {
             launch_frozen(c, c->nw_p.p, c->nw_ap.p, shift, pin, c->nw_stop.p);
-            hipLaunchKernelGGL(k_tc_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
+            hipLaunchKernelGGL(k_nw_cg_step, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, c->nw_dinv.p, c->nw_p.p, c->nw_ap.p,
                                c->nw_y.p, c->nw_r.p, c->nw_part.p);
+            if (!two_level) {
+                hipLaunchKernelGGL(k_nw_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
+                                   c->nw_r.p, c->nw_p.p, c->nw_part.p);
+                return;
+            }      // two-level: r . z needs c = P^T r and y_c = A_c^-1 c first
             hipLaunchKernelGGL(k_tc_restrict, dim3(c->tc_G), dim3(256), 0, st, c->nw_stop.p, c->tc_agg_ptr.p, c->tc_agg_vert.p, c->tc_phi.p, c->nw_r.p, c->tc_c.p);
             hipLaunchKernelGGL(k_tc_coarse, dim3(c->tc_ncb), dim3(256), 0, st, c->nw_stop.p, c->tc_nc, c->tc_Ainv.p, c->tc_c.p, c->tc_yc.p, c->tc_cpart.p);
             hipLaunchKernelGGL(k_tc_cg_dir, dim3(nb), dim3(256), 0, st, it, nv, nb, c->tc_ncb, c->nw_st.p, c->nw_stop.p, tol * tol, max_iters, c->nw_dinv.p,
                                c->nw_r.p, c->nw_p.p, c->nw_part.p, c->tc_cpart.p, c->tc_phi.p, c->tc_agg_of.p, c->tc_yc.p);
-        }
-        launched += n;
-        HIP_TRY(hipMemcpyAsync(c->nw_hstop + (chunks & 1), c->nw_stop.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(c->nw_ev[chunks & 1], st));
-        if (chunks >= 1) {      // the chunk BEFORE the one just enqueued
-            HIP_TRY(hipEventSynchronize(c->nw_ev[(chunks - 1) & 1]));
-            if (c->nw_hstop[(chunks - 1) & 1]) break;
-        }
-        ++chunks;
-    }
-    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);      // the TRUE residual of the returned iterate (tangent_solve_device)
+        })) return rc;
+    // the TRUE residual rhs - (K + shift M) y of the iterate the solve returns, over the free rows: what info4 reports.  The recursive residual
+    // the stop test reads drifts from it by about eps cond(A) |rhs| -- 7e-4 of a residual of 1e-12 |rhs|.  (This pass carries no stop word.)
+    launch_frozen(c, c->nw_y.p, c->nw_ap.p, shift, pin, nullptr);
     hipLaunchKernelGGL(k_nw_true_resid, dim3(nb), dim3(256), 0, st, nv, c->nw_rhs.p, pin, c->nw_ap.p, c->nw_part.p);
     hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb + 2, nullptr);
     HIP_TRY(hipGetLastError());
@@ -1261,6 +1213,21 @@ int newton_args_ok(const char *who, double shift, int32_t flags, int32_t flag_ma
     if (flag_max == 7 && (flags < 0 || flags > 7)) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection), 2 (hold pinned vertices) and 4 (block pass)");
     if (flags < 0 || flags > flag_max) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": flags must be a combination of 1 (positive semi-definite projection) and 2 (hold pinned vertices)");
     return ADMM_HIP_OK;
+}
+int solve_args_ok(const char *who, double tol, int32_t max_iters) {
+    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, std::string(who) + ": tol must be finite and >= 0, max_iters >= 1");
+    return ADMM_HIP_OK;
+}
+// out4 = iterations, converged, |rhs - A y| / |rhs| from the true residual rr_true, |rhs|
+void fill_solve_info(const NwCg &h, double rr_true, double *out4) {
+    out4[0] = h.it; out4[1] = h.conv; out4[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; out4[3] = std::sqrt(h.bb);
+}
+// nw_part[3 blocks] = |g_free|^2 of the step's objective at the device-resident state, dst = -g (k_nw_grad): the polish's figure; needs nw_pin
+void launch_state_residual(admm_hip_ctx *c, double idt2, double *dst) {
+    const int nb = nw_blocks(c);
+    launch_forces(c, c->x.p, false, nullptr);
+    hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, c->stream, c->nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, dst, c->nw_part.p);
+    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, c->stream, c->nw_part.p, nb, c->nw_part.p + (size_t)3 * nb, nullptr);
 }
 
 // ---- adjoint of a step (adjoint.hpp) ----
@@ -1323,17 +1290,17 @@ hipError_t param_sens_download(const admm_hip_ctx *c, std::vector<double> &h, in
             if (hipError_t e = hipMemcpyAsync(h.data() + o[q], c->adj_ps.p + o[q], n[q] * sizeof(double), hipMemcpyDeviceToHost, c->stream)) return e;
     return hipSuccess;
 }
-// the k columns of adj_ps (downloaded into h) in the caller's term order; any output may be NULL
-void param_sens_unpermute(const admm_hip_ctx *c, const std::vector<double> &h, int k, double *out_tets, double *out_tris, double *out_bends) {
+// the k columns of adj_ps (downloaded into h) into the columns j0 .. j0 + k of the outputs, in the caller's term order; any output may be NULL
+void param_sens_unpermute(const admm_hip_ctx *c, const std::vector<double> &h, int j0, int k, double *out_tets, double *out_tris, double *out_bends) {
     const double *ht = h.data(), *hr = ht + (size_t)kSensCols * 4 * c->ldt, *hh = hr + (size_t)kSensCols * c->ldr;
     for (int j = 0; j < k; ++j) {
         if (out_tets)
             for (int n = 0; n < c->nt; ++n)
-                for (int q = 0; q < 4; ++q) out_tets[((size_t)j * c->nt_total + c->tet_perm[n]) * 4 + q] = ht[((size_t)j * 4 + q) * c->ldt + n];
+                for (int q = 0; q < 4; ++q) out_tets[((size_t)(j0 + j) * c->nt_total + c->tet_perm[n]) * 4 + q] = ht[((size_t)j * 4 + q) * c->ldt + n];
         if (out_tris)
-            for (int t = 0; t < c->ntri; ++t) out_tris[(size_t)j * c->ntri_total + c->tri_perm[t]] = hr[(size_t)j * c->ldr + t];
+            for (int t = 0; t < c->ntri; ++t) out_tris[(size_t)(j0 + j) * c->ntri_total + c->tri_perm[t]] = hr[(size_t)j * c->ldr + t];
         if (out_bends)
-            for (int t = 0; t < c->nbend; ++t) out_bends[(size_t)j * c->nbend_total + c->bend_perm[t]] = hh[(size_t)j * c->ldb + t];
+            for (int t = 0; t < c->nbend; ++t) out_bends[(size_t)(j0 + j) * c->nbend_total + c->bend_perm[t]] = hh[(size_t)j * c->ldb + t];
     }
 }
 template <bool REF = false>
@@ -4347,6 +4314,21 @@ static int eval_begin(admm_hip_ctx *c, const char *who, const double *x, const d
     return ADMM_HIP_OK;
 }
 
+// The common entry of the calls that minimise (newton_polish) or differentiate (step_adjoint, step_adjoint_block, adjoint_held) the step's
+// objective at the device-resident state: single-GPU contexts only (the rules of energy(), forces() and stiffness_apply()), nothing in the
+// scene that the objective leaves out, the stream idle, and a step behind the state (its x_bar)
+static int step_problem_begin(admm_hip_ctx *c, const char *who, bool polish) {
+    const std::string w(who);
+    if (int rc = mon_refuse(c, who)) return rc;
+    if (c->obst.n > 0 || !c->dyn.empty())
+        return fail(ADMM_HIP_ERR_ARG, w + ": the context has colliders; contact is not part of the " + (polish ? "objective the polish minimises" : "problem the adjoint differentiates"));
+    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, w + ": the context has strain-limited triangles; the " + (polish ? "energy ignores" : "forces ignore") + " the limits");
+    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, w + ": the context has slide pins");
+    if (int rc = quiesce(c)) return rc;
+    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, w + ": no step has run on this state yet (the " + (polish ? "objective" : "adjoint") + " needs the step's x_bar)");
+    return ADMM_HIP_OK;
+}
+
 int admm_hip_energy(admm_hip_ctx *c, const double *x, double *totals4, double *per_term) {
     if (!c || !totals4) return fail(ADMM_HIP_ERR_ARG, "energy: NULL argument");
     const double *xd;
@@ -4455,7 +4437,7 @@ int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, 
                            double *y, double *info4) {
     if (!c || !rhs || !y || !info4) return fail(ADMM_HIP_ERR_ARG, "tangent_solve: NULL argument");
     if (int rc = newton_args_ok("tangent_solve", shift, flags)) return rc;
-    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "tangent_solve: tol must be finite and >= 0, max_iters >= 1");
+    if (int rc = solve_args_ok("tangent_solve", tol, max_iters)) return rc;
     const double *xd;
     if (int rc = eval_begin(c, "tangent_solve", x, &xd)) return rc;
     HIP_TRY(newton_ensure(c));
@@ -4468,7 +4450,7 @@ int admm_hip_tangent_solve(admm_hip_ctx *c, const double *x, const double *rhs, 
     HIP_TRY(hipMemcpyAsync(&h, c->nw_st.p + 2, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&rr_true, c->nw_part.p + (size_t)3 * nw_blocks(c) + 2, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    info4[0] = h.it; info4[1] = h.conv; info4[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info4[3] = std::sqrt(h.bb);
+    fill_solve_info(h, rr_true, info4);
     return ADMM_HIP_OK;
 }
 
@@ -4482,7 +4464,7 @@ int admm_hip_tangent_solve_block(admm_hip_ctx *c, const double *x, int32_t k, co
     if (!c || !rhs || !y || !info || !block_info3) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: NULL argument");
     if (k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: k < 1 or k > 65535");
     if (int rc = newton_args_ok("tangent_solve_block", shift, flags)) return rc;
-    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "tangent_solve_block: tol must be finite and >= 0, max_iters >= 1");
+    if (int rc = solve_args_ok("tangent_solve_block", tol, max_iters)) return rc;
     const double *xd;
     if (int rc = eval_begin(c, "tangent_solve_block", x, &xd)) return rc;
     HIP_TRY(newton_ensure(c));
@@ -4490,7 +4472,9 @@ int admm_hip_tangent_solve_block(admm_hip_ctx *c, const double *x, int32_t k, co
     hipStream_t st = c->stream;
     const size_t n3 = (size_t)c->n3;
     const bool blocked = c->tc_kind == 0;
-    const int *pin = blocked ? block_solve_setup(c, xd, shift, flags) : nullptr;
+    const int *pin = nullptr;
+    if (blocked)
+        if (int rc = tangent_solve_head(c, xd, shift, flags, false, &pin)) return rc;
     std::vector<NwCg> st3;
     BlockVerdict v;
     NwBlockCtl ctl{};
@@ -4503,11 +4487,7 @@ int admm_hip_tangent_solve_block(admm_hip_ctx *c, const double *x, int32_t k, co
         HIP_TRY(block_verdict_download(c, kk, blocked, st3, &v, &ctl));
         HIP_TRY(hipStreamSynchronize(st));
         block_verdict_finish(kk, blocked, st3, ctl, &v);
-        for (int j = 0; j < kk; ++j) {
-            const NwCg &h = v.st[j];
-            double *i4 = info + (size_t)4 * (j0 + j);
-            i4[0] = h.it; i4[1] = h.conv; i4[2] = h.bb > 0.0 ? std::sqrt(v.rr[j] / h.bb) : 0.0; i4[3] = std::sqrt(h.bb);
-        }
+        for (int j = 0; j < kk; ++j) fill_solve_info(v.st[j], v.rr[j], info + (size_t)4 * (j0 + j));
         block_info3[0] = std::max(block_info3[0], (double)v.iters); block_info3[1] += v.passes;
     }
     return ADMM_HIP_OK;
@@ -4548,15 +4528,10 @@ int admm_hip_tangent_precond_apply(admm_hip_ctx *c, const double *x, const doubl
     const double *xd;
     if (int rc = eval_begin(c, "tangent_precond_apply", x, &xd)) return rc;
     HIP_TRY(newton_ensure(c));
-    if (int rc = tc_ensure(c)) return rc;
     hipStream_t st = c->stream;
     if (c->n3) HIP_TRY(hipMemcpyAsync(c->nw_rhs.p, r, c->n3 * sizeof(double), hipMemcpyHostToDevice, st));
-    const int *pin = nullptr;
-    if (flags & 2) { launch_pin_mask(c); pin = c->nw_pin.p; }
-    HIP_TRY(hipMemsetAsync(c->nw_stop.p, 0, sizeof(int), st));
-    launch_tangent_setup(c, xd, flags & 1);
-    launch_frozen_diag(c, shift, pin);
-    launch_tc_setup(c, xd, shift, pin);
+    const int *pin;
+    if (int rc = tangent_solve_head(c, xd, shift, flags, true, &pin)) return rc;
     launch_tc_start(c, pin);
     HIP_TRY(hipGetLastError());
     if (c->n3) HIP_TRY(hipMemcpyAsync(z_out, c->nw_p.p, c->n3 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4624,7 +4599,7 @@ int admm_hip_modes(admm_hip_ctx *c, const double *x, int32_t k, int32_t guard, d
     if (!c || !lambda || !phi || !info) return fail(ADMM_HIP_ERR_ARG, "modes: NULL argument");
     if (int rc = newton_args_ok("modes", shift, flags)) return rc;
     if (k < 1 || guard < 0 || k + guard > kModalNb) return fail(ADMM_HIP_ERR_ARG, "modes: k >= 1, guard >= 0 and k + guard <= 16");
-    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "modes: tol must be finite and >= 0, max_iters >= 1");
+    if (int rc = solve_args_ok("modes", tol, max_iters)) return rc;
     const double *xd;
     if (int rc = eval_begin(c, "modes", x, &xd)) return rc;
     HIP_TRY(newton_ensure(c));
@@ -4677,13 +4652,8 @@ int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol,
     if (!c || !n || cap < 0 || (cap > 0 && !records)) return fail(ADMM_HIP_ERR_ARG, "newton_polish: bad argument");
     if (max_newton < 0 || !(grad_tol >= 0.0) || !(cg_tol >= 0.0) || !std::isfinite(cg_tol) || cg_max < 1)
         return fail(ADMM_HIP_ERR_ARG, "newton_polish: max_newton >= 0, grad_tol >= 0, cg_tol finite and >= 0, cg_max >= 1");
-    if (int rc = mon_refuse(c, "newton_polish")) return rc;      // (single-GPU contexts only: the rules of energy(), forces() and stiffness_apply())
-    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has colliders; contact is not part of the objective the polish minimises");
-    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has strain-limited triangles; the energy ignores the limits");
-    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "newton_polish: the context has slide pins");
-    if (int rc = quiesce(c)) return rc;
+    if (int rc = step_problem_begin(c, "newton_polish", true)) return rc;
     hipStream_t st = c->stream;
-    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "newton_polish: no step has run on this state yet (the objective needs the step's x_bar)");
     HIP_TRY(newton_ensure(c));
     HIP_TRY(force_ensure(c, false, 0));
     HIP_TRY(mon_ensure(c, false, false));
@@ -4705,9 +4675,7 @@ int admm_hip_newton_polish(admm_hip_ctx *c, int32_t max_newton, double grad_tol,
     if (int rc = objective(c->x.p, &phi, &el)) return rc;
     *n = 0;
     for (int k = 0; ; ++k) {
-        launch_forces(c, c->x.p, false, nullptr);
-        hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->nw_rhs.p, c->nw_part.p);
-        hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+        launch_state_residual(c, idt2, c->nw_rhs.p);
         double g2 = 0.0;
         HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -4759,8 +4727,7 @@ int admm_hip_param_sensitivity(admm_hip_ctx *c, const double *x, int32_t k, cons
         HIP_TRY(hipGetLastError());
         HIP_TRY(param_sens_download(c, h, kk));
         HIP_TRY(hipStreamSynchronize(st));
-        param_sens_unpermute(c, h, kk, out_tets ? out_tets + (size_t)j0 * c->nt_total * 4 : nullptr, out_tris ? out_tris + (size_t)j0 * c->ntri_total : nullptr,
-                             out_bends ? out_bends + (size_t)j0 * c->nbend_total : nullptr);
+        param_sens_unpermute(c, h, j0, kk, out_tets, out_tris, out_bends);
     }
     return ADMM_HIP_OK;
 }
@@ -4773,13 +4740,8 @@ int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL
                           double *out_bends, double *info6) {
     if (!c || !dL_dx || !info6) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: NULL argument");
     if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: flags must be a combination of 1 (positive semi-definite projection) and 2 (parameter sensitivities)");
-    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: tol must be finite and >= 0, max_iters >= 1");
-    if (int rc = mon_refuse(c, "step_adjoint")) return rc;      // (the rules of newton_polish: the adjoint is of the problem the polish solves)
-    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has colliders; contact is not part of the problem the adjoint differentiates");
-    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has strain-limited triangles; the forces ignore the limits");
-    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: the context has slide pins");
-    if (int rc = quiesce(c)) return rc;
-    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "step_adjoint: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    if (int rc = solve_args_ok("step_adjoint", tol, max_iters)) return rc;
+    if (int rc = step_problem_begin(c, "step_adjoint", false)) return rc;      // (the rules of newton_polish: the adjoint is of the problem the polish solves)
     HIP_TRY(newton_ensure(c));
     HIP_TRY(force_ensure(c, false, 0));
     HIP_TRY(adjoint_ensure(c));
@@ -4796,9 +4758,7 @@ int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL
     }
     launch_pin_mask(c);
     // |r_free| of the state: the polish's own figure (its kernels, its bits); k_nw_grad's vector goes to adj_out, overwritten below
-    launch_forces(c, c->x.p, false, nullptr);
-    hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->adj_out.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+    launch_state_residual(c, idt2, c->adj_out.p);
     hipLaunchKernelGGL(k_adj_rhs, dim3(nb), dim3(256), 0, st, nv, Lx, Lv, idt, c->nw_pin.p, c->nw_rhs.p);
     if (int rc = tangent_solve_device(c, c->x.p, idt2, (flags & 1) | 2, tol, max_iters)) return rc;
     hipLaunchKernelGGL(k_adj_out, dim3(nb), dim3(256), 0, st, nv, n3, c->nw_y.p, c->m.p, c->Mxbar.p, c->x.p, Lv, idt, c->nw_pin.p, c->adj_out.p);
@@ -4818,8 +4778,8 @@ int admm_hip_step_adjoint(admm_hip_ctx *c, const double *dL_dx, const double *dL
     HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&rr_true, sums + 2, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (params) param_sens_unpermute(c, hp, 1, out_tets, out_tris, out_bends);
-    info6[0] = h.it; info6[1] = h.conv; info6[2] = h.bb > 0.0 ? std::sqrt(rr_true / h.bb) : 0.0; info6[3] = std::sqrt(h.bb);
+    if (params) param_sens_unpermute(c, hp, 0, 1, out_tets, out_tris, out_bends);
+    fill_solve_info(h, rr_true, info6);
     info6[4] = std::sqrt(g2); info6[5] = idt2;
     return ADMM_HIP_OK;
 }
@@ -4833,13 +4793,8 @@ int admm_hip_step_adjoint_block(admm_hip_ctx *c, int32_t k, const double *dL_dx,
     if (!c || !dL_dx || !info || !block_info3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: NULL argument");
     if (k < 1 || k > 65535) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: k < 1 or k > 65535");
     if (flags < 0 || flags > 3) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: flags must be a combination of 1 (positive semi-definite projection) and 2 (parameter sensitivities)");
-    if (!(tol >= 0.0) || !std::isfinite(tol) || max_iters < 1) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: tol must be finite and >= 0, max_iters >= 1");
-    if (int rc = mon_refuse(c, "step_adjoint_block")) return rc;      // (the rules of step_adjoint)
-    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has colliders; contact is not part of the problem the adjoint differentiates");
-    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has strain-limited triangles; the forces ignore the limits");
-    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: the context has slide pins");
-    if (int rc = quiesce(c)) return rc;
-    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "step_adjoint_block: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    if (int rc = solve_args_ok("step_adjoint_block", tol, max_iters)) return rc;
+    if (int rc = step_problem_begin(c, "step_adjoint_block", false)) return rc;      // (the rules of step_adjoint)
     HIP_TRY(newton_ensure(c));
     HIP_TRY(force_ensure(c, false, 0));
     HIP_TRY(adjoint_ensure(c));
@@ -4857,12 +4812,12 @@ int admm_hip_step_adjoint_block(admm_hip_ctx *c, int32_t k, const double *dL_dx,
     double *sums = c->nw_part.p + (size_t)3 * nb;      // [0] |r_free|^2
     launch_pin_mask(c);
     // |r_free| of the state, once (admm_hip_step_adjoint: the polish's own figure)
-    launch_forces(c, c->x.p, false, nullptr);
-    hipLaunchKernelGGL(k_nw_grad, dim3(nb), dim3(256), 0, st, nv, c->x.p, c->m.p, c->Mxbar.p, c->f_out.p, idt2, c->nw_pin.p, c->adj_out.p, c->nw_part.p);
-    hipLaunchKernelGGL(k_stat_final, dim3(1), dim3(256), 0, st, c->nw_part.p, nb, sums, nullptr);
+    launch_state_residual(c, idt2, c->adj_out.p);
     double g2 = 0.0;
     HIP_TRY(hipMemcpyAsync(&g2, sums, sizeof(double), hipMemcpyDeviceToHost, st));
-    const int *pin = blocked ? block_solve_setup(c, c->x.p, idt2, sflags) : nullptr;
+    const int *pin = nullptr;
+    if (blocked)
+        if (int rc = tangent_solve_head(c, c->x.p, idt2, sflags, false, &pin)) return rc;
     std::vector<NwCg> st3;
     std::vector<double> hp(params ? c->adj_ps.n : 0);
     BlockVerdict v;
@@ -4894,12 +4849,10 @@ int admm_hip_step_adjoint_block(admm_hip_ctx *c, int32_t k, const double *dL_dx,
         HIP_TRY(block_verdict_download(c, kk, blocked, st3, &v, &ctl));
         HIP_TRY(hipStreamSynchronize(st));
         block_verdict_finish(kk, blocked, st3, ctl, &v);
-        if (params) param_sens_unpermute(c, hp, kk, out_tets ? out_tets + (size_t)j0 * c->nt_total * 4 : nullptr, out_tris ? out_tris + (size_t)j0 * c->ntri_total : nullptr,
-                                         out_bends ? out_bends + (size_t)j0 * c->nbend_total : nullptr);
+        if (params) param_sens_unpermute(c, hp, j0, kk, out_tets, out_tris, out_bends);
         for (int j = 0; j < kk; ++j) {
-            const NwCg &h = v.st[j];
             double *i6 = info + (size_t)6 * (j0 + j);
-            i6[0] = h.it; i6[1] = h.conv; i6[2] = h.bb > 0.0 ? std::sqrt(v.rr[j] / h.bb) : 0.0; i6[3] = std::sqrt(h.bb);
+            fill_solve_info(v.st[j], v.rr[j], i6);
             i6[4] = std::sqrt(g2); i6[5] = idt2;
         }
         block_info3[0] = std::max(block_info3[0], (double)v.iters); block_info3[1] += v.passes;
@@ -4933,12 +4886,7 @@ int admm_hip_rest_sensitivity(admm_hip_ctx *c, const double *x, int32_t k, const
 // (the exact tangent, no mass shift, pins not masked), the pin mask, k_adj_held
 int admm_hip_adjoint_held(admm_hip_ctx *c, const double *lam, const double *dL_dx, const double *dL_dv, double *out_held) {
     if (!c || !lam || !dL_dx || !out_held) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: NULL argument");
-    if (int rc = mon_refuse(c, "adjoint_held")) return rc;      // (the rules of step_adjoint: lam is its multiplier)
-    if (c->obst.n > 0 || !c->dyn.empty()) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has colliders; contact is not part of the problem the adjoint differentiates");
-    if (c->tri_limited) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has strain-limited triangles; the forces ignore the limits");
-    if (c->has_slide) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: the context has slide pins");
-    if (int rc = quiesce(c)) return rc;
-    if (!c->xbar_of_state) return fail(ADMM_HIP_ERR_ARG, "adjoint_held: no step has run on this state yet (the adjoint needs the step's x_bar)");
+    if (int rc = step_problem_begin(c, "adjoint_held", false)) return rc;      // (the rules of step_adjoint: lam is its multiplier)
     HIP_TRY(newton_ensure(c));
     HIP_TRY(adjoint_ensure(c));
     HIP_TRY(tangent_ensure(c, 1));

@@ -452,10 +452,13 @@ __global__ __launch_bounds__(256) void k_nw_mask(int nv, const int *__restrict__
 #pragma unroll
     for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; out[i] = held ? 0.0 : in[i]; }
 }
-// y = 0, r = rhs on the free rows, p = z = D^-1 r; partials of r . z and r . r
-__global__ __launch_bounds__(256) void k_nw_cg_init(int nv, int nb, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ dinv,
-                                                    double *__restrict__ y, double *__restrict__ r, double *__restrict__ p, double *__restrict__ part) {
-    __shared__ double lds[8];
+
+// ---- the stages of the PCG, one body each: the single (k_nw_cg_*), block (k_nw_cg_*_block) and two-level (k_tc_cg_*, tangent_precond.hpp)
+// kernels call them on their own column, so the three paths cannot drift apart ----
+// y = 0, r = rhs on the free rows, p = z = D^-1 r (P; the two-level start forms its p later); partials of r . D^-1 r and r . r
+template <bool P>
+__device__ __forceinline__ void nw_cg_init_col(int nv, int nb, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ dinv,
+                                               double *__restrict__ y, double *__restrict__ r, double *__restrict__ p, double *__restrict__ part, double *lds) {
     const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
     double q[2] = {0.0, 0.0};
     if (v < nv) {
@@ -464,35 +467,29 @@ __global__ __launch_bounds__(256) void k_nw_cg_init(int nv, int nb, const double
         for (int j = 0; j < 3; ++j) {
             const size_t i = 3 * (size_t)v + j;
             const double ri = held ? 0.0 : rhs[i], zi = dinv[i] * ri;
-            y[i] = 0.0; r[i] = ri; p[i] = zi;
+            y[i] = 0.0; r[i] = ri;
+            if (P) p[i] = zi;
             q[0] = fma(ri, zi, q[0]); q[1] = fma(ri, ri, q[1]);
         }
     }
     block_sum<2>(q, lds);
     if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
 }
-// one block: the scalars of iteration 0 and the stop word (a zero or non-finite right-hand side ends the solve here)
-__global__ __launch_bounds__(256) void k_nw_cg_init2(int nb, const double *__restrict__ part, NwCg *__restrict__ st, int *__restrict__ stop) {
-    __shared__ double lds[8];
-    double q[2];
-    nw_reduce<2>(part + nb, nb, q, lds);
-    if (threadIdx.x == 0) {
-        NwCg s;
-        s.rz = q[0]; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
-        s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(q[0] > 0.0) || !nw_finite(q[0]);
-        s.conv = q[1] == 0.0;
-        st[0] = s; st[1] = s; st[2] = s;      // (slot 1 too: what an earlier solve left there must not pass k_nw_cg_dir(1)'s test when this one ends here)
-        *stop = s.done;
-    }
+// the scalars of iteration 0 from r . z and r . r (a zero or non-finite right-hand side ends the solve here), into ALL THREE slots: what
+// an earlier solve left in slot 1 must not pass the test of k_nw_cg_dir(it odd) when this solve ends at once
+__device__ __forceinline__ NwCg nw_cg_start(double rz, double rr, NwCg *st) {
+    NwCg s;
+    s.rz = rz; s.rr = rr; s.bb = rr; s.it = 0; s.pad_ = 0;
+    s.done = !(rr > 0.0) || !nw_finite(rr) || !(rz > 0.0) || !nw_finite(rz);
+    s.conv = rr == 0.0;
+    st[0] = s; st[1] = s; st[2] = s;
+    return s;
 }
-// alpha = r.z / p.Ap; y += alpha p, r -= alpha Ap; partials of the new r . z (z = D^-1 r) and r . r.  A breakdown (p.Ap <= 0 or a
-// non-finite scalar) leaves y and r as they are; k_nw_cg_dir reaches the same verdict from the same numbers and ends the solve.
-__global__ __launch_bounds__(256) void k_nw_cg_step(int it, int nv, int nb, const NwCg *__restrict__ st, const int *stop, const double *__restrict__ dinv,
-                                                    const double *__restrict__ p, const double *__restrict__ ap, double *__restrict__ y,
-                                                    double *__restrict__ r, double *__restrict__ part) {
-    __shared__ double lds[8];
-    if (*stop) return;
-    const NwCg s = st[it & 1];
+// alpha = s.rz / p.Ap (part[0 .. nb)); y += alpha p, r -= alpha Ap; partials of the new r . D^-1 r and r . r.  A breakdown (p.Ap <= 0 or a
+// non-finite scalar) leaves y and r as they are; nw_cg_next reaches the same verdict from the same numbers and ends the solve.
+__device__ __forceinline__ void nw_cg_step_col(const NwCg &s, int nv, int nb, const double *__restrict__ dinv, const double *__restrict__ p,
+                                               const double *__restrict__ ap, double *__restrict__ y, double *__restrict__ r, double *__restrict__ part,
+                                               double *lds) {
     double pap[1];
     nw_reduce<1>(part, nb, pap, lds);
     if (!(pap[0] > 0.0) || !nw_finite(pap[0])) return;
@@ -512,6 +509,42 @@ __global__ __launch_bounds__(256) void k_nw_cg_step(int it, int nv, int nb, cons
     block_sum<2>(q, lds);
     if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
 }
+// the verdict of iteration s.it: the scalars of iteration s.it + 1 from p.Ap and the new r . z and r . r, or the end of the solve
+// (k_nw_cg_dir_block, k_tc_cg_dir; k_nw_cg_dir writes the same lines out, see there)
+__device__ __forceinline__ NwCg nw_cg_next(const NwCg &s, double pap, double rz_new, double rr_new, double tol2, int max_iters) {
+    const bool broke = !(pap > 0.0) || !nw_finite(pap);
+    NwCg n = s;
+    if (broke) { n.done = 1; n.conv = 0; }
+    else {
+        n.rz = rz_new; n.rr = rr_new; n.it = s.it + 1;
+        n.conv = rr_new <= tol2 * s.bb;
+        n.done = n.conv || n.it >= max_iters || !nw_finite(rz_new) || !nw_finite(rr_new) || !(rz_new > 0.0);
+    }
+    return n;
+}
+
+// y = 0, r = rhs on the free rows, p = z = D^-1 r; partials of r . z and r . r
+__global__ __launch_bounds__(256) void k_nw_cg_init(int nv, int nb, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ dinv,
+                                                    double *__restrict__ y, double *__restrict__ r, double *__restrict__ p, double *__restrict__ part) {
+    __shared__ double lds[8];
+    nw_cg_init_col<true>(nv, nb, rhs, pin, dinv, y, r, p, part, lds);
+}
+// one block: the scalars of iteration 0 and the stop word
+__global__ __launch_bounds__(256) void k_nw_cg_init2(int nb, const double *__restrict__ part, NwCg *__restrict__ st, int *__restrict__ stop) {
+    __shared__ double lds[8];
+    double q[2];
+    nw_reduce<2>(part + nb, nb, q, lds);
+    if (threadIdx.x == 0) *stop = nw_cg_start(q[0], q[1], st).done;
+}
+// nw_cg_step_col on the one column of the single solve
+__global__ __launch_bounds__(256) void k_nw_cg_step(int it, int nv, int nb, const NwCg *__restrict__ st, const int *stop, const double *__restrict__ dinv,
+                                                    const double *__restrict__ p, const double *__restrict__ ap, double *__restrict__ y,
+                                                    double *__restrict__ r, double *__restrict__ part) {
+    __shared__ double lds[8];
+    if (*stop) return;
+    const NwCg s = st[it & 1];
+    nw_cg_step_col(s, nv, nb, dinv, p, ap, y, r, part, lds);
+}
 // beta = r.z new / r.z old; p = D^-1 r + beta p; block 0 writes the scalars of iteration it + 1, the verdict and the stop word
 __global__ __launch_bounds__(256) void k_nw_cg_dir(int it, int nv, int nb, NwCg *st, int *stop, double tol2, int max_iters, const double *__restrict__ dinv,
                                                    const double *__restrict__ r, double *__restrict__ p, const double *__restrict__ part) {
@@ -520,7 +553,7 @@ __global__ __launch_bounds__(256) void k_nw_cg_dir(int it, int nv, int nb, NwCg 
     if (s.done || s.it != it) return;      // ended, or a launch behind the end: st[it & 1] is then the slot of iteration it - 2
     double q[3];
     nw_reduce<3>(part, nb, q, lds);
-    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);
+    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);      // nw_cg_next, written out: through the call the compiler schedules this kernel differently
     NwCg n = s;
     if (broke) { n.done = 1; n.conv = 0; }
     else {
@@ -586,23 +619,8 @@ struct NwBlockArgs {
 // k_nw_cg_init per column
 __global__ __launch_bounds__(256) void k_nw_cg_init_block(NwBlockArgs a) {
     __shared__ double lds[8];
-    const size_t col = blockIdx.y;
-    const double *rhs = a.rhs + col * a.sv;
-    double *y = a.y + col * a.sv, *r = a.r + col * a.sv, *p = a.p + col * a.sv, *part = a.part + col * 3 * a.nb;
-    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
-    double q[2] = {0.0, 0.0};
-    if (v < a.nv) {
-        const bool held = a.pin && a.pin[v] != 0;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const size_t i = 3 * (size_t)v + j;
-            const double ri = held ? 0.0 : rhs[i], zi = a.dinv[i] * ri;
-            y[i] = 0.0; r[i] = ri; p[i] = zi;
-            q[0] = fma(ri, zi, q[0]); q[1] = fma(ri, ri, q[1]);
-        }
-    }
-    block_sum<2>(q, lds);
-    if (threadIdx.x == 0) { part[a.nb + blk] = q[0]; part[2 * (size_t)a.nb + blk] = q[1]; }
+    const size_t col = blockIdx.y, o = col * a.sv;
+    nw_cg_init_col<true>(a.nv, a.nb, a.rhs + o, a.pin, a.dinv, a.y + o, a.r + o, a.p + o, a.part + col * 3 * a.nb, lds);
 }
 // one block: k_nw_cg_init2 per column (all three slots), the list of iteration 0, the counters and the stop word
 __global__ __launch_bounds__(256) void k_nw_cg_init2_block(NwBlockArgs a) {
@@ -611,15 +629,7 @@ __global__ __launch_bounds__(256) void k_nw_cg_init2_block(NwBlockArgs a) {
     for (int col = 0; col < a.k; ++col) {
         double q[2];
         nw_reduce<2>(a.part + (size_t)col * 3 * a.nb + a.nb, a.nb, q, lds);
-        if (threadIdx.x == 0) {
-            NwCg s;
-            s.rz = q[0]; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
-            s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(q[0] > 0.0) || !nw_finite(q[0]);
-            s.conv = q[1] == 0.0;
-            NwCg *st = a.st + 3 * col;
-            st[0] = s; st[1] = s; st[2] = s;
-            if (!s.done) a.ctl->list[0][1 + n++] = col;
-        }
+        if (threadIdx.x == 0 && !nw_cg_start(q[0], q[1], a.st + 3 * col).done) a.ctl->list[0][1 + n++] = col;
     }
     if (threadIdx.x == 0) {
         a.ctl->list[0][0] = n; a.ctl->list[1][0] = 0; a.ctl->arrive = 0; a.ctl->passes[0] = 0; a.ctl->passes[1] = 0;
@@ -634,27 +644,8 @@ __global__ __launch_bounds__(256) void k_nw_cg_step_block(int it, NwBlockArgs a)
     if ((int)blockIdx.y >= ls[0]) return;
     const size_t col = (size_t)ls[1 + blockIdx.y];
     const NwCg s = a.st[3 * col + (it & 1)];
-    double *part = a.part + col * 3 * a.nb;
-    double pap[1];
-    nw_reduce<1>(part, a.nb, pap, lds);
-    if (!(pap[0] > 0.0) || !nw_finite(pap[0])) return;
-    const double alpha = s.rz / pap[0];
-    const double *p = a.p + col * a.sv, *ap = a.ap + col * a.sv;
-    double *y = a.y + col * a.sv, *r = a.r + col * a.sv;
-    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
-    double q[2] = {0.0, 0.0};
-    if (v < a.nv) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const size_t i = 3 * (size_t)v + j;
-            y[i] = fma(alpha, p[i], y[i]);
-            const double ri = fma(-alpha, ap[i], r[i]);
-            r[i] = ri;
-            q[0] = fma(ri * a.dinv[i], ri, q[0]); q[1] = fma(ri, ri, q[1]);
-        }
-    }
-    block_sum<2>(q, lds);
-    if (threadIdx.x == 0) { part[a.nb + blk] = q[0]; part[2 * (size_t)a.nb + blk] = q[1]; }
+    const size_t o = col * a.sv;
+    nw_cg_step_col(s, a.nv, a.nb, a.dinv, a.p + o, a.ap + o, a.y + o, a.r + o, a.part + col * 3 * a.nb, lds);
 }
 // k_nw_cg_dir per running column; the list of iteration it + 1 and the stop word (above)
 __global__ __launch_bounds__(256) void k_nw_cg_dir_block(int it, NwBlockArgs a) {
@@ -668,14 +659,7 @@ __global__ __launch_bounds__(256) void k_nw_cg_dir_block(int it, NwBlockArgs a) 
     if (s.done || s.it != it) return;      // ended, or a launch behind the end (k_nw_cg_dir)
     double q[3];
     nw_reduce<3>(a.part + col * 3 * a.nb, a.nb, q, lds);
-    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);
-    NwCg n = s;
-    if (broke) { n.done = 1; n.conv = 0; }
-    else {
-        n.rz = q[1]; n.rr = q[2]; n.it = s.it + 1;
-        n.conv = q[2] <= a.tol2 * s.bb;
-        n.done = n.conv || n.it >= a.max_iters || !nw_finite(q[1]) || !nw_finite(q[2]) || !(q[1] > 0.0);
-    }
+    const NwCg n = nw_cg_next(s, q[0], q[1], q[2], a.tol2, a.max_iters);
     if (!n.done) {
         const double beta = q[1] / s.rz;
         const double *r = a.r + col * a.sv;

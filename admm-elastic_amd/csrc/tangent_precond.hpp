@@ -13,8 +13,8 @@
 //   k_tc_sym              A_c <- (A_c + A_c^T) / 2
 //   k_tc_invert           one block of 1024 threads, the matrix in global memory: device_math.hpp: tc_invert -- dropped columns, the verdict
 //                         (or, with admm_hip_set_tangent_coarse(1), the k_tcb_ chain of tangent_coarse.hpp: the same contract in 64 x 64 tiles)
-// and per CG iteration, behind the unchanged frozen pass on p (z = D^-1 r + P y_c is not stored):
-//   k_tc_cg_step          k_nw_cg_step's arithmetic: alpha; y, r; partials of r . D^-1 r and r . r
+// and per CG iteration, behind the unchanged frozen pass on p and the unchanged k_nw_cg_step (alpha; y, r; partials of r . D^-1 r and r . r;
+// z = D^-1 r + P y_c is not stored):
 //   k_tc_restrict         block = aggregate: c = P^T r
 //   k_tc_coarse           a wave per row: y_c = A_c^-1 c, and per block the partial of c . y_c
 //   k_tc_cg_dir           r . z = r . D^-1 r + c . y_c (exact algebra: no second pass over r); beta; p = D^-1 r + P y_c + beta p; the
@@ -136,20 +136,7 @@ __global__ __launch_bounds__(1024) void k_tc_invert(int nc, double *As, double *
 __global__ __launch_bounds__(256) void k_tc_cg_init(int nv, int nb, const double *__restrict__ rhs, const int *__restrict__ pin, const double *__restrict__ dinv,
                                                     double *__restrict__ y, double *__restrict__ r, double *__restrict__ part) {
     __shared__ double lds[8];
-    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
-    double q[2] = {0.0, 0.0};
-    if (v < nv) {
-        const bool held = pin && pin[v] != 0;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const size_t i = 3 * (size_t)v + j;
-            const double ri = held ? 0.0 : rhs[i], zi = dinv[i] * ri;
-            y[i] = 0.0; r[i] = ri;
-            q[0] = fma(ri, zi, q[0]); q[1] = fma(ri, ri, q[1]);
-        }
-    }
-    block_sum<2>(q, lds);
-    if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
+    nw_cg_init_col<false>(nv, nb, rhs, pin, dinv, y, r, nullptr, part, lds);
 }
 // c = P^T r, block = aggregate
 __global__ __launch_bounds__(256) void k_tc_restrict(const int *stop, const int *__restrict__ agg_ptr, const int *__restrict__ agg_vert,
@@ -204,43 +191,10 @@ __global__ __launch_bounds__(256) void k_tc_cg_init2(int nv, int nb, int ncb, co
 #pragma unroll
         for (int j = 0; j < 3; ++j) { const size_t i = 3 * (size_t)v + j; p[i] = fma(dinv[i], r[i], tc_prolong(phi, yc, (size_t)v, g, j)); }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        NwCg s;
-        s.rz = rz; s.rr = q[1]; s.bb = q[1]; s.it = 0; s.pad_ = 0;
-        s.done = !(q[1] > 0.0) || !nw_finite(q[1]) || !(rz > 0.0) || !nw_finite(rz);
-        s.conv = q[1] == 0.0;
-        st[0] = s; st[2] = s;
-        *stop = s.done;
-    }
-}
-// k_nw_cg_step's arithmetic: alpha = r.z / p.Ap; y += alpha p, r -= alpha Ap; partials of the new r . D^-1 r and r . r
-__global__ __launch_bounds__(256) void k_tc_cg_step(int it, int nv, int nb, const NwCg *__restrict__ st, const int *stop, const double *__restrict__ dinv,
-                                                    const double *__restrict__ p, const double *__restrict__ ap, double *__restrict__ y,
-                                                    double *__restrict__ r, double *__restrict__ part) {
-    __shared__ double lds[8];
-    if (*stop) return;
-    const NwCg s = st[it & 1];
-    double pap[1];
-    nw_reduce<1>(part, nb, pap, lds);
-    if (!(pap[0] > 0.0) || !nw_finite(pap[0])) return;
-    const double alpha = s.rz / pap[0];
-    const int blk = xcd_block(), v = blk * 256 + (int)threadIdx.x;
-    double q[2] = {0.0, 0.0};
-    if (v < nv) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const size_t i = 3 * (size_t)v + j;
-            y[i] = fma(alpha, p[i], y[i]);
-            const double ri = fma(-alpha, ap[i], r[i]);
-            r[i] = ri;
-            q[0] = fma(ri * dinv[i], ri, q[0]); q[1] = fma(ri, ri, q[1]);
-        }
-    }
-    block_sum<2>(q, lds);
-    if (threadIdx.x == 0) { part[nb + blk] = q[0]; part[2 * (size_t)nb + blk] = q[1]; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *stop = nw_cg_start(rz, q[1], st).done;
 }
 // beta = r.z new / r.z old with r . z = r . D^-1 r + c . y_c; p = D^-1 r + P y_c + beta p; block 0 writes the scalars of iteration it + 1,
-// the verdict and the stop word (k_nw_cg_dir).  After a breakdown in k_tc_cg_step, c and y_c are those of the unchanged r: not used.
+// the verdict and the stop word (k_nw_cg_dir).  After a breakdown in k_nw_cg_step, c and y_c are those of the unchanged r: not used.
 __global__ __launch_bounds__(256) void k_tc_cg_dir(int it, int nv, int nb, int ncb, NwCg *st, int *stop, double tol2, int max_iters, const double *__restrict__ dinv,
                                                    const double *__restrict__ r, double *__restrict__ p, const double *__restrict__ part,
                                                    const double *__restrict__ cpart, const double *__restrict__ phi, const int *__restrict__ agg_of,
@@ -251,15 +205,8 @@ __global__ __launch_bounds__(256) void k_tc_cg_dir(int it, int nv, int nb, int n
     double q[3], cy[1];
     nw_reduce<3>(part, nb, q, lds);
     nw_reduce<1>(cpart, ncb, cy, lds);
-    const bool broke = !(q[0] > 0.0) || !nw_finite(q[0]);
     const double rz = q[1] + cy[0];
-    NwCg n = s;
-    if (broke) { n.done = 1; n.conv = 0; }
-    else {
-        n.rz = rz; n.rr = q[2]; n.it = s.it + 1;
-        n.conv = q[2] <= tol2 * s.bb;
-        n.done = n.conv || n.it >= max_iters || !nw_finite(rz) || !nw_finite(q[2]) || !(rz > 0.0);
-    }
+    const NwCg n = nw_cg_next(s, q[0], rz, q[2], tol2, max_iters);
     if (!n.done) {
         const double beta = rz / s.rz;
         const int v = xcd_block() * 256 + (int)threadIdx.x;

@@ -710,12 +710,23 @@ class Solver:
         rc = f64(rhs).ravel().copy()
         if rc.size != self.m_x.size:
             raise ValueError("tangent_solve: rhs must hold 3 values per node")
-        if shift is None:
-            shift = 1.0 / (self._settings.timestep_s ** 2)
+        shift = self._shift_or_default(shift)
         y = np.zeros(rc.size); info = np.zeros(4)
         check(lib().admm_hip_tangent_solve(self._ctx, dptr(xc), dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0), float(tol),
                                            int(max_iters), dptr(y), dptr(info)))
-        return y.reshape(-1, 3), dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]))
+        return y.reshape(-1, 3), self._solve_info(info)
+
+    def _shift_or_default(self, shift):
+        """shift=None: 1 / dt^2, the Hessian of the implicit-Euler objective"""
+        return 1.0 / (self._settings.timestep_s ** 2) if shift is None else shift
+
+    @staticmethod
+    def _solve_info(row):
+        """one row of a solve's info: [iterations, converged, residual, rhs_norm(, stationarity, shift)]"""
+        d = dict(iterations=int(row[0]), converged=bool(row[1]), residual=float(row[2]), rhs_norm=float(row[3]))
+        if len(row) > 4:
+            d.update(stationarity=float(row[4]), shift=float(row[5]))
+        return d
 
     @staticmethod
     def _block_info(cols, binfo):
@@ -736,13 +747,11 @@ class Solver:
         if rc.ndim != 3 or rc.shape[0] < 1 or rc.shape[1:] != (nv, 3):
             raise ValueError("tangent_solve_block: rhs must be [k, n_verts, 3] with k >= 1")
         k = rc.shape[0]
-        if shift is None:
-            shift = 1.0 / (self._settings.timestep_s ** 2)
+        shift = self._shift_or_default(shift)
         y = np.zeros(rc.shape); info = np.zeros((k, 4)); binfo = np.zeros(3)
         check(lib().admm_hip_tangent_solve_block(self._ctx, dptr(xc), k, dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0),
                                                  float(tol), int(max_iters), dptr(y), dptr(info), dptr(binfo)))
-        cols = [dict(iterations=int(i[0]), converged=bool(i[1]), residual=float(i[2]), rhs_norm=float(i[3])) for i in info]
-        return y, self._block_info(cols, binfo)
+        return y, self._block_info([self._solve_info(i) for i in info], binfo)
 
     def set_tangent_precond(self, kind="jacobi", aggregates=None):
         """admm_hip_set_tangent_precond: the preconditioner of the CG behind tangent_solve, newton_polish and step_adjoint, from the next
@@ -774,8 +783,7 @@ class Solver:
         rc = f64(r).ravel().copy()
         if rc.size != self.m_x.size:
             raise ValueError("tangent_precond_apply: r must hold 3 values per node")
-        if shift is None:
-            shift = 1.0 / (self._settings.timestep_s ** 2)
+        shift = self._shift_or_default(shift)
         z = np.zeros(rc.size)
         check(lib().admm_hip_tangent_precond_apply(self._ctx, dptr(xc), dptr(rc), float(shift), (1 if psd else 0) | (2 if hold_pins else 0), dptr(z)))
         return z.reshape(-1, 3)
@@ -917,8 +925,7 @@ class Solver:
                                           dptr(hinges), dptr(info)))
         lam, xbar, xprev, vprev, mass = (q.reshape(-1, 3) for q in vec)
         out = dict(lam=lam, xbar=xbar, x_prev=xprev, v_prev=vprev, masses=mass, tets=tets, tris=tris, hinges=hinges,
-                   info=dict(iterations=int(info[0]), converged=bool(info[1]), residual=float(info[2]), rhs_norm=float(info[3]),
-                             stationarity=float(info[4]), shift=float(info[5])))
+                   info=self._solve_info(info))
         if rest:
             out["rest"] = self.rest_sensitivity(lam)
         if held:
@@ -951,8 +958,7 @@ class Solver:
         check(lib().admm_hip_step_adjoint_block(self._ctx, k, dptr(gx), dptr(gv), (1 if psd else 0) | (2 if params else 0), float(tol),
                                                 int(max_iters), dptr(vec[0]), dptr(vec[1]), dptr(vec[2]), dptr(vec[3]), dptr(vec[4]), dptr(tets),
                                                 dptr(tris), dptr(hinges), dptr(info), dptr(binfo)))
-        cols = [dict(iterations=int(i[0]), converged=bool(i[1]), residual=float(i[2]), rhs_norm=float(i[3]), stationarity=float(i[4]),
-                     shift=float(i[5])) for i in info]
+        cols = [self._solve_info(i) for i in info]
         out = dict(lam=vec[0], xbar=vec[1], x_prev=vec[2], v_prev=vec[3], masses=vec[4], tets=tets, tris=tris, hinges=hinges,
                    info=self._block_info(cols, binfo))
         if rest:

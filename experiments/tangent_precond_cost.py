@@ -2,7 +2,7 @@
 at the state of experiments/newton_cost.py -- the run to put under rocprofv3 --kernel-trace.  In this order:
   phase J            1 call of tangent_solve(tol=0, max_iters=23), Jacobi           k_nw_cg_step, k_nw_cg_dir, the frozen pass: 23 dispatches
   phase G, G = 32    23 calls of tangent_solve(max_iters=1), two-level              the setup kernels: 23 solves (ceil(12 G / 16) passes each)
-                     1 call of tangent_solve(tol=0, max_iters=23)                   k_tc_cg_step, k_tc_restrict, k_tc_coarse, k_tc_cg_dir
+                     1 call of tangent_solve(tol=0, max_iters=23)                   k_nw_cg_step, k_tc_restrict, k_tc_coarse, k_tc_cg_dir
   phase G, G = 64    the same
 then, timed on the host (three times each, kind by kind): tangent_solve(tol=1e-8) with Jacobi, G = 32 and G = 64; tangent_precond_apply
 (the setup and one application); and, in a context each after one step of 5 ADMM iterations, newton_polish(max_iters=1) each way.
@@ -42,7 +42,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "parse":
         if k in dur and len(dur[k]) >= per:
             print(line(k, dur[k][:per][WARM:N]))
     off = {k: 0 for k in dur}
-    off.update({"k_tangent_frozen": N + 1, "k_newton_gather<false>": N + 1})
+    off.update({"k_tangent_frozen": N + 1, "k_newton_gather<false>": N + 1, "k_nw_cg_step": N})      # (phase J's)
     for G in GS:
         passes = -(-12 * G // 16)
         solves = N + 1
@@ -58,7 +58,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "parse":
                     print(line(k + ", one pass", d.reshape(solves, passes)[WARM:N].ravel()))
                 off[k] += solves * passes
         for k, per_small, per_big in (("k_tc_cg_init", 1, 1), ("k_tc_cg_init2", 1, 1), ("k_tc_restrict", 2, N + 1), ("k_tc_coarse", 2, N + 1),
-                                      ("k_tc_cg_step", 1, N), ("k_tc_cg_dir", 1, N), ("k_tangent_frozen", 2, N + 1), ("k_newton_gather<false>", 2, N + 1)):
+                                      ("k_nw_cg_step", 1, N), ("k_tc_cg_dir", 1, N), ("k_tangent_frozen", 2, N + 1), ("k_newton_gather<false>", 2, N + 1)):
             if k in dur:
                 tot = N * per_small + per_big
                 d = dur[k][off[k]:off[k] + tot]

@@ -370,6 +370,30 @@ def test_jacobi_bits_before_and_after_and_two_level_repeats():
 
 
 @gpu
+def test_a_zero_solve_after_a_two_level_solve_that_ended_on_an_odd_iteration():
+    """test_tangent_block's test of the same name with the two-level preconditioner: a right-hand side of zero ends at the set-up of the
+    solve -- 0 iterations, y = 0, residual 0, rhs_norm 0 -- whatever parity the solve before it left its scalars at (solves of 1 .. 6
+    iterations before it), as a single call and as the columns of a block call (which goes column by column here: blocked is False)."""
+    s, flat, c, tab = open_case("mixed162")
+    s.set_tangent_precond("two_level", aggregates=AGG["mixed162"])
+    rhs = _rhs(c)
+    zero = np.zeros_like(rhs)
+    want = dict(iterations=0, converged=True, residual=0.0, rhs_norm=0.0)
+    for n in range(1, 7):
+        _, i0 = s.tangent_solve(rhs, c["x"], tol=1e-12, max_iters=n)
+        assert i0["iterations"] == n
+        y, i1 = s.tangent_solve(zero, c["x"])
+        print("two-level, %d iterations, then zero: %s" % (n, i1))
+        assert i1 == want and not y.any(), (n, i1)
+        s.tangent_solve_block(np.stack([rhs, 0.5 * rhs]), c["x"], tol=1e-12, max_iters=n)
+        Y, ib = s.tangent_solve_block(np.stack([zero, zero]), c["x"])
+        print("two-level, block of two, %d iterations, then zeros: %s" % (n, ib))
+        assert ib["columns"] == [want, want] and not Y.any(), (n, ib)
+        assert not ib["blocked"] and ib["column_passes"] == 0 and ib["block_iterations"] == 0, (n, ib)
+    s.close()
+
+
+@gpu
 @pytest.mark.parametrize("linsolver", [0, 1])
 def test_two_level_solves_do_not_disturb_a_run(linsolver):
     """3 steps (linsolver 0: the on-chip PCG; 1: the GS sweeps) with two-level solves and applications at an explicit x between the steps:
